@@ -72,6 +72,11 @@ def parse(argv=None):
                     help="skip the one-rank-RCCL-group leg of the training step (the data-parallel step form on a single GPU)")
     ap.add_argument("--no-telemetry", action="store_true", help="do not sample clocks / power / temperature beside the timed legs")
     ap.add_argument("--dump-ops", type=str, default="")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed PC iteration computed -- the state x and its mean x_mean, "
+                         "(batch, 3, R, R) float32 -- as DIR/<name>.npy (rank 0; at most 64 MB in all, a fixed seeded sample of a larger "
+                         "output).  The timed steps start from the same seeded prior sample at the first iteration of the schedule in "
+                         "every run, so two builds given the same arguments can be compared output for output.  Sampler workloads only")
     ap.add_argument("--no-train", action="store_true", help="skip the DSM training-step measurement")
     ap.add_argument("--train-only", action="store_true",
                     help="only the DSM training step (the leg that has a collective): what a multi-GPU scaling run needs per N")
@@ -97,7 +102,12 @@ def parse(argv=None):
                     help="rank r uses GPU r %% (visible GPUs): N ranks on fewer GPUs -- a functional run of the multi-rank branches "
                          "(self-launch, rank census, bucketed gradient exchange, exposed-exchange leg, parameter broadcast), NOT a "
                          "scaling measurement; needs --dist-backend gloo (RCCL refuses two ranks on one device)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.train_only or args.workload not in ("cifar10", "ffhq256")):
+        ap.error("--dump-outputs writes the outputs of the PC sampler: --workload cifar10 or ffhq256, without --train-only")
+    return args
 
 
 def bench_train(args, cfg, dev, dist, world, rank, sync_all, leg="train"):
@@ -679,8 +689,55 @@ def roofline_of(prog, E, L, reps=3):
                 achieved_exec=achieved_exec, achieved_alg=achieved_alg, alg_bytes_wino=alg_bytes_wino)
 
 
-def bench_pc(args, cfg_name, B, N, dev, dist, world, rank, steps, warmup, detail, leg=None):
-    """PC sampler of a VE NCSN++ config: one hipGraph replay per iteration; returns (result dict, engine, model, sd, cfg)."""
+class ScheduleRunner:
+    """PC iterations of a sampler engine that keep its step index inside the N-iteration schedule (the kernels read the step
+    tables at that index): a sampler run that has taken its last iteration starts over from the prior sample x0."""
+
+    def __init__(self, eng, prog, x0, N, use_graph):
+        self.eng, self.prog, self.x0, self.N, self.use_graph = eng, prog, x0, N, use_graph
+        self.pos = 0                                  # the engine's step index (host copy; the engine was just reset to x0)
+
+    def restart(self):
+        self.eng.reset(self.x0)
+        self.pos = 0
+
+    def run(self, k):
+        while k > 0:
+            if self.pos == self.N:
+                self.restart()
+            n = min(k, self.N - self.pos)
+            self.eng.run_steps(self.prog, n, self.use_graph)
+            self.pos += n
+            k -= n
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """arrays {name: tensor or array} -> path/<name>.npy in float32 (float64 stays float64).  Above `budget` bytes in all, every
+    array is cut to its share of the budget by a fixed seeded sample of its flattened elements (sorted indices, the same for a
+    given size in every run).  Returns {name: shape written}."""
+    arrays = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for k, v in arrays.items():
+        if total > budget:
+            keep = max(1, int(budget * (v.nbytes / total)) // v.itemsize)
+            if keep < v.size:
+                idx = np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))
+                v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+        shapes[k] = list(v.shape)
+    return shapes
+
+
+def bench_pc(args, cfg_name, B, N, dev, dist, world, rank, steps, warmup, detail, leg=None, keep_outputs=False):
+    """PC sampler of a VE NCSN++ config: one hipGraph replay per iteration; returns (result dict, engine, model, sd, cfg).
+    The timed steps are the first `steps` iterations of a sampler run from the seeded prior sample, whatever ran before them;
+    keep_outputs: the result carries "_outputs", the state (x, x_mean) after the last timed step, on the host."""
     import _util
     from score_sde_pytorch_amd import sde_lib, sampling, engine as E, _lib as L
     from score_sde_pytorch_amd.models import utils as mutils
@@ -702,14 +759,19 @@ def bench_pc(args, cfg_name, B, N, dev, dist, world, rank, steps, warmup, detail
     prog = eng.step_program(with_rng=True)
     use_graph = not args.no_graph
     sync_all = _sync_factory(dev, dist)
-    eng.run_steps(prog, warmup, use_graph)
+    runner = ScheduleRunner(eng, prog, x_T.to(dev), N, use_graph)
+    runner.run(warmup)
     sync_all()
-    warm_s = prewarm(lambda: eng.run_steps(prog, 10, use_graph), sync_all, args.prewarm_s, dev, dist)
+    warm_s = prewarm(lambda: runner.run(10), sync_all, args.prewarm_s, dev, dist)
+    # (the time-based pre-warm takes a different number of iterations in every run: the timed ones start the schedule afresh)
+    runner.restart()
+    sync_all()
     with tele_leg(leg or ("sampler " + cfg_name)):
         t0 = time.perf_counter()
-        eng.run_steps(prog, steps, use_graph)
+        runner.run(steps)
         sync_all()
         dt_own = time.perf_counter() - t0
+    outputs = {"x": eng.x.view(eng.shape).cpu(), "x_mean": eng.x_mean.view(eng.shape).cpu()} if keep_outputs else None
     per_rank = []
     dt = _max_over_ranks(dt_own, dev, dist, per_rank)
     ms_per_step = dt / steps * 1e3
@@ -728,6 +790,8 @@ def bench_pc(args, cfg_name, B, N, dev, dist, world, rank, steps, warmup, detail
         if upd:
             roof["by_class"]["pc_update"] = upd
         res["_roof"] = roof
+    if outputs is not None:
+        res["_outputs"] = outputs
     return res, eng, model, sd, cfg
 
 
@@ -1048,9 +1112,11 @@ def main():
         return
     with matrix_mode(args.matrix):
         res, eng, model, sd, cfg = bench_pc(args, cfg_name, args.batch, args.sde_steps, dev, dist, world, rank, args.steps, args.warmup, True,
-                                            leg="sampler")
+                                            leg="sampler", keep_outputs=bool(args.dump_outputs) and rank == 0)
     B, R = args.batch, cfg.data.image_size
     roof = res.pop("_roof", None)
+    outputs = res.pop("_outputs", None)
+    dumped = dump_outputs(args.dump_outputs, outputs) if outputs is not None else None
     out = {
         "metric": "pc_sampler_images_per_sec", "value": res["value"], "unit": "images/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_s": res["prewarm_s"], "ms_per_step": res["ms_per_step"],
@@ -1063,6 +1129,8 @@ def main():
                    "direct_form_ceiling_images_per_sec": res["direct_form_ceiling_images_per_sec"],
                    "matrix_mode": args.matrix, "parallelism": "replicas x%d (no collectives)" % world},
     }
+    if dumped is not None:
+        out["config"]["dumped_outputs"] = dumped
 
     if roof is not None:
         # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process; the figure is the
