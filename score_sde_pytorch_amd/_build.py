@@ -56,7 +56,7 @@ def build(force=False, verbose=False):
 
 def build_variant(name, defines):
     """A/B timing only: libssde_hip_<name>.so under csrc/build/variants, every source compiled with the given -D flags
-    (e.g. ["-DSSDE_WINO_SCHED=0"]); loaded through SSDE_LIB_PATH.  Not part of build()."""
+    (e.g. ["-DSSDE_WINO_TRACE"]); loaded through SSDE_LIB_PATH.  Not part of build()."""
     vdir = os.path.join(CSRC, "build", "variants", name)
     os.makedirs(vdir, exist_ok=True)
 

@@ -264,9 +264,6 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv
 //     store, which spreads the 64 lanes of a store over the 64 banks;
 //   * the four workgroups of an image run on ONE XCD (they read the same K and V: L2 hits).
 // L == 256 and C % 64 == 0, C <= 256 only (the 16x16 attention of every shipped config); anything else stays on attn_kernel.
-#ifndef SSDE_ATTN_X6_SCORE_TERMS
-#define SSDE_ATTN_X6_SCORE_TERMS 8          // (6: an A/B variant)
-#endif
 namespace x6 {
 constexpr int kT = 512, kRows = 64, kL = 256;
 constexpr int kKStage = 3 * kL * 32;                      // bytes of one K stage: [3 pieces][256 keys][16 channels] bf16
@@ -350,7 +347,7 @@ __global__ __launch_bounds__(x6::kT) void attn_x6_kernel(const float* __restrict
                                                               __builtin_bit_cast(ssde_bf16x8, f.B[b][TJ[t]]), acc[a][b], 0, 0, 0);
   };
   using Six = std::integral_constant<int, 6>;
-  using ScoreTerms = std::integral_constant<int, SSDE_ATTN_X6_SCORE_TERMS>;
+  using Eight = std::integral_constant<int, 8>;
 
   // ---- the streamed operands (producers): K in nst stages of 16 channels, then V in 16 stages of 16 tokens, ONE stream through a
   // register ring of four elements.  Element u + 4 is requested at the top of stage u -- the first V stages during the last K
@@ -472,7 +469,7 @@ __global__ __launch_bounds__(x6::kT) void attn_x6_kernel(const float* __restrict
     for (int u = 0; u < nst; ++u) {
       Frags f;
       read_frags(f, lds + u * (kRows * 32), qplane, (u & 1) ? stage1 : stage0, kL * 32);
-      mfmas(ScoreTerms{}, f);
+      mfmas(Eight{}, f);
       SSDE_LDS_BARRIER();
     }
   } else {

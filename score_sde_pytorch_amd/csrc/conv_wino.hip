@@ -37,37 +37,18 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Schedule of the asynchronous issue work (A/B-timed on the MI355X with tools/ab_bench.sh, round 2):
-//   0  weight-DMA pieces / halo loads ride between the MFMAs of the matrix phases (round 1)        203-229 TF/s
-//   1  matrix phases are pure MFMA + fragment reads, waves 4-7 issue every VMEM instruction in their staging phase:
-//      SLOWER (176-208 TF/s) -- the burst of 32 KB of LDS-DMA plus the halo loads, issued at once beside the other
-//      waves' fragment reads, costs more than the issue slots it frees (an MFMA wave has idle issue slots anyway)
-//   2  schedule 0, and waves 4-7 read their first fragments before the barrier that opens their matrix phase
-#ifndef SSDE_WINO_SCHED
-#define SSDE_WINO_SCHED 0
-#endif
-// Issue priority (s_setprio) of the two waves of a SIMD: 1 = the wave in its matrix phase runs at priority 1 (round 1);
-// 0 = no priorities; 2 = the STAGING wave's short VALU / LDS bursts outrank the matrix wave's MFMA stream.
-// s_memtime traces (tools/wino_trace.py) showed why 2 wins: at 1 the staging wave is starved until the matrix wave has
-// issued its last MFMA, so the prologue (GroupNorm + SiLU, ~900 VALU cycles) ran AFTER the 2750-cycle matrix phase
-// instead of inside it (phase 1: 3880 -> 3500 cycles); fp32 MFMA and VALU do not co-execute, so the VALU cycles are
-// paid either way, but their LDS / VMEM latencies now hide under the other wave's MFMAs.
-#ifndef SSDE_WINO_PRIO
-#define SSDE_WINO_PRIO 2
-#endif
-// GroupNorm parameters of the prologue: 0 = global loads issued between the MFMAs of the staging waves' matrix phase
-// (round 1: 10 extra VMEM instructions + their address arithmetic per stage in the matrix stream);
-// 1 = mean / rstd of the tile's images and gamma / beta parked in LDS once per workgroup, read in store_stage.
-// Together with priority 2: +3..5 % on every BASELINE shape (gpurun_out/conv_ab_r2e.txt).
-#ifndef SSDE_WINO_GNLDS
-#define SSDE_WINO_GNLDS 1
-#endif
-// s_sleep argument (units of 64 cycles) between the 8 LDS groups of the input transform; 0 = one burst (round 1).
-// A/B on the MI355X (gpurun_out/conv_ab_r2g.txt): 1 = +3 % on every shape, 2 = neutral, 3 = slower (the transform itself
-// becomes the critical path of the phase).
-#ifndef SSDE_WINO_TSLEEP
-#define SSDE_WINO_TSLEEP 1
-#endif
+// Measured choices (A/B on the MI355X, tools/ab_bench.sh):
+// - The asynchronous issue work (weight-DMA pieces, halo loads) rides between the MFMAs of the matrix phases.  Matrix
+//   phases of pure MFMA, with the staging waves issuing every VMEM instruction in a burst, were slower
+//   (profiles/r2_ab_pure_matrix_phase.txt).
+// - The STAGING wave's short VALU / LDS bursts run at issue priority 2, above the matrix wave's MFMA stream.  At the
+//   opposite priority the staging wave starved until the matrix wave's last MFMA, and the prologue (GroupNorm + SiLU)
+//   ran after the matrix phase instead of inside it (tools/wino_trace.py, profiles/r2_wino_trace_final.txt).
+// - The GroupNorm parameters are parked in LDS once per workgroup.  Together with the priority: +3..5 % on every
+//   BASELINE shape (profiles/r2_ab_prio_gnlds_sched.txt).
+// - One s_sleep of 64 cycles between the 8 LDS groups of the input transform: +3 % on every shape
+//   (profiles/r2_ab_transform_sleep.txt).
+constexpr int kTransformSleep = 1;
 
 // -DSSDE_WINO_TRACE (tools/wino_trace.py, a variant library only): s_memtime stamps of waves 0 and 4 of the first and of
 // the last workgroup, to see where a workgroup's cycles go (fill, the two phases of a stage, barriers, epilogue).
@@ -110,7 +91,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
   SSDE_LDS(smem);
   float* Vb = smem;                          // [2][kStageFloats]
   float* Ub = smem + 2 * kStageFloats;       // [2][kStageFloats]
-  float* raw = smem + 4 * kStageFloats;      // [4 pairs][halo_px][2]; then (SSDE_WINO_GNLDS) the GroupNorm tables
+  float* raw = smem + 4 * kStageFloats;      // [4 pairs][halo_px][2]; then the GroupNorm tables
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, lq = lane >> 4;
 
@@ -172,7 +153,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
   }
   const int t_vcol = ((t_tile ^ ((t_pair & 1) << 4)) + t_pair * 64) * 2;
 
-#if SSDE_WINO_GNLDS
   // GroupNorm tables in LDS: (mean, rstd) of every (tile image, group), gamma and beta of every channel
   float* gn_tab = raw + 8 * halo_px;         // [IMGS][groups][2]
   float* gb_tab = gn_tab + 2 * IMGS * (kGn ? s.gn_groups : 0);   // [2][Ctot]
@@ -187,7 +167,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
   int gil[kMaxRaw];
 #pragma unroll
   for (int it = 0; it < kMaxRaw; ++it) gil[it] = (goff[it] >= 0 ? gimg[it] - img0 : 0) * (kGn ? s.gn_groups : 0);
-#endif
   float4 rv[kMaxRaw];
   float mu[kMaxRaw], rs[kMaxRaw];
   float4 gam = make_float4(1.f, 1.f, 1.f, 1.f), bet = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -197,7 +176,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
   // The loads of a stage are BRANCH-FREE (items outside the image / halo / channel range read a clamped, valid address
   // and are zeroed in store_stage) and cut into 8 PIECES that mfma_stage issues between the MFMAs of its 8 positions:
   // as exec-masked blocks in front of the matrix phase they cost ~870 cycles of every stage.
-  const float* ld_bp = nullptr; int ld_C = 0, ld_cg = 0;
+  const float* ld_bp = nullptr; int ld_C = 0;
   auto load_piece = [&](int st, int k) {
     const int half = sid & 1;
     if (k == 0) {
@@ -209,31 +188,9 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
       const int cthr = (second ? c_base - s.c0 : c_base) + half * 4;
       chan_ok = cthr < ld_C;
       ld_bp = base + (chan_ok ? cthr : 0);
-      ld_cg = (c_base + half * 4) < Ctot ? c_base + half * 4 : 0;
     }
-    // GroupNorm parameters first (two pieces), the halo float4s after them: the LAST load is issued at position 5 at the
-    // latest, >= 500 matrix cycles before the barrier behind which store_stage consumes all of them
-#if SSDE_WINO_GNLDS
-    constexpr int kFirstRaw = 0;
-    if (false) {
-#else
-    constexpr int kFirstRaw = kGn ? 2 : 0;
-    if (kGn && k < 2) {
-#endif
-      if (k == 0) {
-        gam = *reinterpret_cast<const float4*>(s.gn_gamma + ld_cg);
-        bet = *reinterpret_cast<const float4*>(s.gn_beta + ld_cg);
-      }
-#pragma unroll
-      for (int it = 2 * k; it < 2 * k + 2; ++it) {
-        const int gi = (goff[it] >= 0 ? gimg[it] : 0) * s.gn_groups + ld_cg / cpg;
-        mu[it] = s.gn_mean[gi];
-        rs[it] = s.gn_rstd[gi];
-      }
-    } else if (k >= kFirstRaw && k < kFirstRaw + 4) {
-      const int it = k - kFirstRaw;
-      rv[it] = *reinterpret_cast<const float4*>(ld_bp + (size_t)(goff[it] >= 0 ? goff[it] : 0) * ld_C);
-    }
+    // the halo float4s in pieces 0-3, well ahead of the barrier behind which store_stage consumes them
+    if (k < 4) rv[k] = *reinterpret_cast<const float4*>(ld_bp + (size_t)(goff[k] >= 0 ? goff[k] : 0) * ld_C);
   };
   auto load_stage = [&](int st) {
 #pragma unroll
@@ -265,7 +222,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
   // prologue + raw LDS store (channel-pair major)
   auto store_stage = [&]() {
     const int half = sid & 1;
-#if SSDE_WINO_GNLDS
     if (kGn) {
       const int cg = (c_cur + half * 4) < Ctot ? c_cur + half * 4 : 0;
       gam = *reinterpret_cast<const float4*>(gb_tab + cg);
@@ -277,7 +233,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
         mu[it] = mr.x; rs[it] = mr.y;
       }
     }
-#endif
 #pragma unroll
     for (int it = 0; it < kMaxRaw; ++it) {
       if (goff[it] == -2) continue;
@@ -290,7 +245,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
     }
   };
   // V = B^T d B for this thread's (tile, channel pair), both channels at once.
-  // The 16 LDS reads and 16 LDS writes are issued in 8 groups of 4 with s_sleep in between (SSDE_WINO_TSLEEP): as one
+  // The 16 LDS reads and 16 LDS writes are issued in 8 groups of 4 with s_sleep in between: as one
   // burst at the start of the phase, the 4 x 32 LDS operations of the transforming waves queue in front of the matrix
   // waves' fragment reads, which are prefetched only one position (256 matrix cycles) ahead -- the matrix phase of
   // waves 4-7 took 3260 cycles instead of 2750 (tools/wino_trace.py).  Groups of 4 keep the LDS queue shorter than
@@ -308,11 +263,9 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
       r[1][x] = make_float2(d1.x + d2.x, d1.y + d2.y);
       r[2][x] = make_float2(d2.x - d1.x, d2.y - d1.y);
       r[3][x] = make_float2(d1.x - d3.x, d1.y - d3.y);
-#if SSDE_WINO_TSLEEP > 0
       __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_sleep(SSDE_WINO_TSLEEP);
+      __builtin_amdgcn_s_sleep(kTransformSleep);
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
 #pragma unroll
     for (int y = 0; y < 4; ++y) {
@@ -324,13 +277,11 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
       *reinterpret_cast<float2*>(Vn + (y * 4 + 1) * 512 + t_vcol) = v1;
       *reinterpret_cast<float2*>(Vn + (y * 4 + 2) * 512 + t_vcol) = v2;
       *reinterpret_cast<float2*>(Vn + (y * 4 + 3) * 512 + t_vcol) = v3;
-#if SSDE_WINO_TSLEEP > 0
       if (y < 3) {
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_sleep(SSDE_WINO_TSLEEP);
+        __builtin_amdgcn_s_sleep(kTransformSleep);
         __builtin_amdgcn_sched_barrier(0);
       }
-#endif
     }
   };
 
@@ -369,9 +320,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
   };
   auto mfma_stage = [&](const float* Vc, const float* Uc, auto&& piece) {
     __builtin_amdgcn_sched_barrier(0);
-#if SSDE_WINO_PRIO == 1
-    __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
     for (int ps = 0; ps < 8; ++ps) {
       const int cur = ps & 1;
@@ -402,32 +350,15 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-#if SSDE_WINO_PRIO == 1
-    __builtin_amdgcn_s_setprio(0);
-#endif
   };
-#if SSDE_WINO_PRIO == 2
-#define SSDE_STAGING_HI() __builtin_amdgcn_s_setprio(2)
-#define SSDE_STAGING_LO() __builtin_amdgcn_s_setprio(0)
-#else
-#define SSDE_STAGING_HI() do { } while (0)
-#define SSDE_STAGING_LO() do { } while (0)
-#endif
 
   // ---- pipeline prologue: stage 0 staged, stage 1 in flight ----
   const int last = nst - 1;
   SSDE_TR(1);
-#if SSDE_WINO_SCHED != 1
-  // the asynchronous issue work rides between the MFMAs of the matrix phases
-#if SSDE_WINO_GNLDS
   if (ph == 1) load_stage(0);
   else dma_weights(0, Ub);
   if (kGn) __syncthreads();                  // publishes the GroupNorm tables filled above
   if (ph == 1) store_stage();
-#else
-  if (ph == 1) { load_stage(0); store_stage(); }
-  else dma_weights(0, Ub);
-#endif
   SSDE_LDS_BARRIER();
   SSDE_TR(2);
   if (ph == 0) { transform(Vb); SSDE_WAIT_VMCNT(0); }
@@ -445,94 +376,27 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
       preload(Vc, Uc);
       mfma_stage(Vc, Uc, [&](int k) { dma_piece(sn, Un, k); });
     } else {
-      SSDE_STAGING_HI();
+      __builtin_amdgcn_s_setprio(2);
       if (st + 1 < nst) store_stage();
-      SSDE_STAGING_LO();
-#if SSDE_WINO_SCHED == 2
-      preload(Vc, Uc);
-#endif
+      __builtin_amdgcn_s_setprio(0);
     }
     if (st < 8) SSDE_TR(4 + st * 4);
     SSDE_LDS_BARRIER();
     if (st < 8) SSDE_TR(5 + st * 4);
     if (ph == 1) {
       const int sn = min(st + 2, last);
-#if SSDE_WINO_SCHED != 2
       preload(Vc, Uc);
-#endif
       mfma_stage(Vc, Uc, [&](int k) { load_piece(sn, k); });
     } else {
-      SSDE_STAGING_HI();
+      __builtin_amdgcn_s_setprio(2);
       if (st + 1 < nst) transform(Vn);
-      SSDE_STAGING_LO();
+      __builtin_amdgcn_s_setprio(0);
       SSDE_WAIT_VMCNT(0);
     }
     if (st < 8) SSDE_TR(6 + st * 4);
     SSDE_LDS_BARRIER();
     if (st < 8) SSDE_TR(7 + st * 4);
   }
-#else
-  // The matrix phases are PURE MFMA + fragment-read streams.  Every VMEM instruction (the 8 LDS-DMA pieces of the next
-  // weight stage, the halo float4 loads and GroupNorm parameters of the stage after next) is issued by waves 4-7 in
-  // phase 1, i.e. in the phase in which they do NOT own the matrix pipe: issued between MFMAs, an LDS-DMA piece held
-  // the issuing wave's next MFMA back by 60-185 cycles (MI355X_MICROARCH.md, "LDS-DMA piece issue cost"), ~1000
-  // cycles per 4096-cycle stage.  In-order VMEM return + the staging waves' vmcnt(0) at the end of their matrix phase
-  // (two phases after the issue) publishes the weights; the halo registers are consumed one stage later.
-  //   phase 1: waves 0-3 MFMA(k)                       waves 4-7 prologue + raw store (k+1); halo loads (k+2); weight DMA (k+1)
-  //   phase 2: waves 4-7 MFMA(k), then vmcnt(0)        waves 0-3 input transform raw -> V(k+1)
-  // Waves 4-7 read their first fragments of stage k before the barrier that opens phase 2 (V(k), U(k) are published).
-  if (ph == 1) {
-    dma_weights(0, Ub);
-    load_stage(0);
-  }
-#if SSDE_WINO_GNLDS
-  if (kGn) __syncthreads();                  // publishes the GroupNorm tables filled above
-#endif
-  if (ph == 1) {
-    store_stage();
-    load_stage(min(1, last));
-    SSDE_WAIT_VMCNT(0);
-  }
-  SSDE_LDS_BARRIER();
-  SSDE_TR(2);
-  if (ph == 0) transform(Vb);
-  SSDE_LDS_BARRIER();
-  SSDE_TR(3);
-
-  for (int st = 0; st < nst; ++st) {
-    const float* Vc = Vb + (st & 1) * kStageFloats;
-    const float* Uc = Ub + (st & 1) * kStageFloats;
-    float* Vn = Vb + ((st + 1) & 1) * kStageFloats;
-    float* Un = Ub + ((st + 1) & 1) * kStageFloats;
-    if (ph == 0) {
-      preload(Vc, Uc);
-      mfma_stage(Vc, Uc, [](int) {});
-    } else {
-      SSDE_STAGING_HI();
-      if (st + 1 < nst) {
-        store_stage();
-        if (st + 2 < nst) load_stage(st + 2);
-        dma_weights(st + 1, Un);
-      }
-      SSDE_STAGING_LO();
-      preload(Vc, Uc);
-    }
-    if (st < 8) SSDE_TR(4 + st * 4);
-    SSDE_LDS_BARRIER();
-    if (st < 8) SSDE_TR(5 + st * 4);
-    if (ph == 1) {
-      mfma_stage(Vc, Uc, [](int) {});
-      SSDE_WAIT_VMCNT(0);
-    } else if (st + 1 < nst) {
-      SSDE_STAGING_HI();
-      transform(Vn);
-      SSDE_STAGING_LO();
-    }
-    if (st < 8) SSDE_TR(6 + st * 4);
-    SSDE_LDS_BARRIER();
-    if (st < 8) SSDE_TR(7 + st * 4);
-  }
-#endif
   SSDE_TR(40);
   __syncthreads();
   SSDE_TR(41);
@@ -658,10 +522,8 @@ int ssde_conv_wino_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
   const int halo_px = imgs * (2 * tht + 2) * (2 * twt + 2);
   SSDE_REQUIRE(halo_px * 2 <= kMaxRaw * kStagers, "conv(winograd): halo of %d pixels exceeds the staging plan", halo_px);
   int lds = (4 * kStageFloats + 4 * halo_px * 2) * 4;
-#if SSDE_WINO_GNLDS
   if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) lds += (2 * imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
   SSDE_REQUIRE(lds <= 160 * 1024, "conv(winograd): %d bytes of LDS", lds);
-#endif
   if (lds_out) { *lds_out = lds; return SSDE_OK; }
   static std::atomic<bool> attr_set{false};   // once, before any stream capture
   if (!attr_set) {

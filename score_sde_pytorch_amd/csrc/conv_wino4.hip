@@ -41,9 +41,10 @@
 //   * One vector-memory instruction per position slot (as a burst in slots 0-1 they queued behind each other: 1500 cycles
 //     for two positions); addressing by scalar base + 32-bit lane offset (no vector address arithmetic per stage).
 //   Together +7 .. +10 % per layer (241-315 TF/s direct-equivalent with GroupNorm + SiLU, 240-333 without).
-//   Measured and NOT adopted: the transform as scalar v_fma_f32 instead of packed v_pk_* (neutral, -DSSDE_W4_SCALAR_BT=1);
-//   the two waves of a SIMD running their prologue at opposite ends of the stage (neutral: a VALU instruction of one wave
-//   waits out the 64-cycle MFMA the other has in the pipe, its head took 2100 cycles instead of 1500); the MFMAs of the
+//   Measured and NOT adopted (profiles/r3_wino4_ab.txt): the transform as scalar v_fma_f32 instead of packed v_pk_*
+//   (neutral: beside fp32 MFMAs, which share the VALU datapath, packing costs nothing); the two waves of a SIMD running
+//   their prologue at opposite ends of the stage (neutral: a VALU instruction of one wave waits out the 64-cycle MFMA the
+//   other has in the pipe, its head took 2100 cycles instead of 1500); the MFMAs of the
 //   last three positions issued after the barrier inside the next head, fragments carried in registers (2-3 % slower: the
 //   head grew by exactly the matrix cycles it gained -- LDS burst latency, VALU and fp32 MFMA time ADD on a SIMD).
 //   Where a stage's ~4400 cycles go (s_memtime, tools/wino4_trace.py): 2304 are MFMAs of the SIMD's two waves, ~950 VALU
@@ -86,45 +87,11 @@ extern "C" int ssde_debug_w4_trace(void* buf) {
 #ifndef SSDE_W4_PF
 #define SSDE_W4_PF 3
 #endif
-// 1: the short VALU / LDS bursts of the transforms and of the halo staging run at s_setprio 2 (as conv_wino.hip's staging)
-#ifndef SSDE_W4_PRIO
-#define SSDE_W4_PRIO 1
-#endif
-// 1: the two waves of a SIMD run their halo prologue at opposite ends of a stage (see the stage body); measured neutral
-// (profiles/r3_wino4_ab.txt: a VALU instruction of one wave waits out the running 64-cycle MFMA of the other, so the head of
-// the wave that overlaps took 2100 cycles instead of 1500), kept as a switch
-#ifndef SSDE_W4_STAGGER
-#define SSDE_W4_STAGGER 0
-#endif
-// 1: a stage head reads the GroupNorm tables before its fragment / transform reads
-#ifndef SSDE_W4_GNFIRST
-#define SSDE_W4_GNFIRST 1
-#endif
 // rows of the output tile a thread has in flight in the second round of the shared epilogue (residual loads issued before
 // the first use; the first round still holds half of the accumulators and keeps 4)
 #ifndef SSDE_W4_EPI_BATCH
 #define SSDE_W4_EPI_BATCH 8
 #endif
-// timing experiments (profiles/r4_wino4_upper_bounds.txt): variants that compute WRONG results on purpose, never the product
-#ifndef SSDE_W4_EXP_NOBARRIER
-#define SSDE_W4_EXP_NOBARRIER 0
-#endif
-#ifndef SSDE_W4_EXP_NOSTORE
-#define SSDE_W4_EXP_NOSTORE 0
-#endif
-// 1: the stage body without the GroupNorm / SiLU prologue and without both passes of the input transform (V is garbage): what the
-// main loop would cost if V arrived already transformed, from a separate HBM-bound pass (the classical two-kernel Winograd)
-#ifndef SSDE_W4_EXP_NOXFORM
-#define SSDE_W4_EXP_NOXFORM 0
-#endif
-#if SSDE_W4_PRIO
-#define SSDE_W4_HI() __builtin_amdgcn_s_setprio(2)
-#define SSDE_W4_LO() __builtin_amdgcn_s_setprio(0)
-#else
-#define SSDE_W4_HI() do { } while (0)
-#define SSDE_W4_LO() do { } while (0)
-#endif
-
 
 namespace {
 
@@ -142,9 +109,6 @@ constexpr int kPos = 36, kTiles = 32, kKc = 4;
 // bank conflicts (PMC), but the LDS is active only a third of the time
 #ifndef SSDE_W4_VPAD
 #define SSDE_W4_VPAD 16
-#endif
-#ifndef SSDE_W4_RAWPAD
-#define SSDE_W4_RAWPAD 0
 #endif
 constexpr int kVP = kTiles * kKc + SSDE_W4_VPAD;               // floats per position of V: 128 + 16, so that the 6 lines x 8 items of a
                                                     // wave's transform writes (b64) spread over all banks
@@ -190,28 +154,8 @@ __device__ __forceinline__ void bt6(const float2 (&d)[6], float2 (&o)[6]) {
   }
 }
 
-// -DSSDE_W4_SCALAR_BT=1 (A/B only, built with -fno-slp-vectorize): the same arithmetic as scalar v_fma_f32 / v_add_f32
-// instead of packed v_pk_* (MI355X_MICROARCH.md prices packed f32 VALU beside bf16 MFMAs as an anti-lever; beside fp32
-// MFMAs, which share the VALU datapath, it measured neutral: profiles/r3_wino4_ab.txt)
-#ifndef SSDE_W4_SCALAR_BT
-#define SSDE_W4_SCALAR_BT 0
-#endif
+// the same, on packed f32 pairs (v_pk_*)
 __device__ __forceinline__ void bt6(const ssde_f32x2 (&d)[6], ssde_f32x2 (&o)[6]) {
-#if SSDE_W4_SCALAR_BT
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    float d0 = d[0][e], d1 = d[1][e], d2 = d[2][e], d3 = d[3][e], d4 = d[4][e], d5 = d[5][e];
-    asm volatile("" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3), "+v"(d4), "+v"(d5));    // keeps the halves apart (no SLP re-packing)
-    const float t1 = d4 - 4.f * d2, t2 = d3 - 4.f * d1, t3 = d4 - d2, t4 = d3 - d1;
-    o[0][e] = 4.f * d0 - 5.f * d2 + d4;
-    o[1][e] = t1 + t2;
-    o[2][e] = t1 - t2;
-    o[3][e] = t3 + 2.f * t4;
-    o[4][e] = t3 - 2.f * t4;
-    o[5][e] = 4.f * d1 - 5.f * d3 + d5;
-  }
-  return;
-#endif
   const ssde_f32x2 t1 = d[4] - 4.f * d[2], t2 = d[3] - 4.f * d[1], t3 = d[4] - d[2], t4 = d[3] - d[1];
   o[0] = 4.f * d[0] - 5.f * d[2] + d[4];
   o[1] = t1 + t2;
@@ -262,10 +206,7 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   const int IMGS = kTiles >> (p.lTWt + p.lTHt);
   const int HWd = 4 * TWt + 2, HH = 4 * THt + 2;
   const int halo_px = IMGS * HH * HWd;
-  // floats between the two channel-pair planes of a raw buffer: with SSDE_W4_RAWPAD the planes are 32 banks apart (the 48
-  // lanes of a transform read touch 4 tiles x 6 columns of BOTH planes; columns shared by neighbouring tiles are the same
-  // address, but planes 8 banks apart collided)
-  const int raw_plane = SSDE_W4_RAWPAD ? ((2 * halo_px + 63) & ~63) + 32 : 2 * halo_px;
+  const int raw_plane = 2 * halo_px;           // floats between the two channel-pair planes of a raw buffer
   const int raw_stride = 2 * raw_plane;        // floats per raw buffer
   const int img0 = (mt / p.tiles_per_img) * IMGS;
   const int trem = mt % p.tiles_per_img;
@@ -478,10 +419,7 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   pass2(Vb);
   SSDE_WAIT_VMCNT_FOR(0, rv[0], rv[1]);        // unconditional: every path from a halo load to its use passes a counted wait
   if (nst > 1) store_raw(rawb + raw_stride, 1);
-  // group Y (waves 4-7, the second wave of every SIMD, SSDE_W4_STAGGER): activates and stores its halo at the END of a
-  // stage instead of at the head, see below
-  const bool grp_y = SSDE_W4_STAGGER && wave >= 4;
-  if (nst > 2 && !grp_y) {
+  if (nst > 2) {
 #pragma unroll
     for (int k = 0; k < kMaxRaw; ++k) load_piece(2, k);
   }
@@ -490,32 +428,27 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   SSDE_TR(2);
 
   // ---- one stage.  HAS1: a stage st + 1 exists (its weights are fetched and its input transformed here), HAS2: the halo of
-  // stage st + 2 is activated and stored, HASL: a halo is fetched (group X: that of stage st + 3, stored at the head of the
-  // next stage; group Y: that of stage st + 2, stored at the end of this one).  Compile-time flags: the main loop runs the
-  // all-true body, the last stages are peeled, and the body has no branch.
+  // stage st + 2 is activated and stored, HASL: the halo of stage st + 3 is fetched (stored at the head of the next stage).
+  // Compile-time flags: the main loop runs the all-true body, the last stages are peeled, and the body has no branch.
   //
-  //   head     own weight pieces 0, 1 landed | fragment reads of positions 0..2 | pass-1 reads | X: prologue of rv -> raw[cur]
+  //   head     own weight pieces 0, 1 landed | fragment reads of positions 0..2 | pass-1 reads | prologue of rv -> raw[cur]
   //   slot j   fragment reads of position j + 3 | 2 MFMAs of position j | ONE vector-memory instruction (slots 0..6:
   //            P0' H0' P1' H1' P2' P3' P4' -- as a burst in slots 0-1 the halo loads and the first pieces queued behind each
   //            other in the address path: 1500 cycles for two positions, tools/wino4_trace.py / profiles/r3_wino4_trace_a.txt)
   //            after slot 1: pass-1 arithmetic and writes; after 3: pass-2 reads; after 5: pass-2 arithmetic and writes
-  //   tail     Y: prologue of rv -> raw[cur] | LDS-only barrier
-  // X and Y are the two waves of a SIMD: while X runs the prologue (VALU: GroupNorm, SiLU -- two quarter-rate
-  // transcendentals per element) Y already issues MFMAs, and Y's prologue runs beside X's last positions.  With every wave
-  // doing the same thing at the same time each phase was bound by ITS resource while the matrix pipe idled.
+  //   tail     LDS-only barrier
+  // The short VALU / LDS bursts of the prologue and of the transforms run at s_setprio 2, as conv_wino.hip's staging.
   //
   // VMEM queue of a wave (in issue order; P = weight piece of this stage, ' = of the next, H = halo load):
-  //   on entry           [P0 H0 P1 H1 P2 P3 P4]  (Y: the H are done)   vmcnt(3): pieces 0, 1 (positions 0..3) and X's rv
+  //   on entry           [P0 H0 P1 H1 P2 P3 P4]                         vmcnt(3): pieces 0, 1 (positions 0..3) and rv
   //   slot 1 (pos 4, 5)  [P2 P3 P4 P0']                                 piece 2 <=> vmcnt(2 + HAS1)
   //   slot 3 (pos 6, 7)  [P3 P4 P0' H0' P1']                            piece 3 <=> vmcnt(1 + 2 HAS1 + HASL)
   //   slot 5 (pos 8)     [P4 P0' H0' P1' H1' P2']                       piece 4 <=> vmcnt(3 HAS1 + 2 HASL)
-  //   Y's tail           [P0' H0' P1' H1' P2' P3' P4']                  rv      <=> vmcnt(3 HAS1)
   // (fragment reads run SSDE_W4_PF = 3 positions ahead, so the read of position j + 3 is what a slot's count protects) ----
   static_assert(SSDE_W4_PF == 3 && kWaves == 8, "the vmcnt counts of the stage body assume reads 3 positions ahead");
-  auto stage = [&](auto H1, auto H2, auto HL, auto GY, const int st) __attribute__((always_inline)) {
-    constexpr bool has1 = decltype(H1)::value, has2 = decltype(H2)::value, hasl = decltype(HL)::value, gy = decltype(GY)::value;
+  auto stage = [&](auto H1, auto H2, auto HL, const int st) __attribute__((always_inline)) {
+    constexpr bool has1 = decltype(H1)::value, has2 = decltype(H2)::value, hasl = decltype(HL)::value;
     constexpr int n1 = has1 ? 1 : 0, nl = hasl ? 1 : 0;
-    const int st_l = gy ? st + 2 : st + 3;              // the stage whose halo this stage fetches
     const int cur = st & 1, nxt = cur ^ 1;
     const float* Vc = Vb + cur * kVFloats;
     const float* Uc = Ub + cur * kUFloats;
@@ -536,23 +469,22 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
     SSDE_OPAQUE_VGPR(ua);
     // ---- head ----
     GnRegs gnr;
-    if (has2 && !gy && SSDE_W4_GNFIRST && !SSDE_W4_EXP_NOXFORM) gnr = gn_fetch(st + 2);        // (tables: no dependence on the weight pieces)
-    if (has2 && !gy) SSDE_WAIT_VMCNT_FOR(3, rv[0], rv[1]); else SSDE_WAIT_VMCNT_FENCE(3);
+    if (has2) gnr = gn_fetch(st + 2);                   // (tables: no dependence on the weight pieces)
+    if (has2) SSDE_WAIT_VMCNT_FOR(3, rv[0], rv[1]); else SSDE_WAIT_VMCNT_FENCE(3);
 #pragma unroll
     for (int j = 0; j < SSDE_W4_PF; ++j) {
       af[j] = *(ssde_lds_cfloat2*)(va + kPS * j * kVP);
       bf[j] = *(ssde_lds_cfloat2*)(ua + j * 128);
     }
-    if (has1 && !SSDE_W4_EXP_NOXFORM) {
+    if (has1) {
       const float* rp = rawb + nxt * raw_stride + t_rawoff;
 #pragma unroll
       for (int a = 0; a < 6; ++a) { const float2 q = *reinterpret_cast<const float2*>(rp + a * HWd * 2); td[a].x = q.x; td[a].y = q.y; }
     }
-    if (has2 && !gy && !SSDE_W4_EXP_NOXFORM) {
-      SSDE_W4_HI();
-      if (SSDE_W4_GNFIRST) store_raw_with(rawb + cur * raw_stride, st + 2, gnr);
-      else store_raw(rawb + cur * raw_stride, st + 2);
-      SSDE_W4_LO();
+    if (has2) {
+      __builtin_amdgcn_s_setprio(2);
+      store_raw_with(rawb + cur * raw_stride, st + 2, gnr);
+      __builtin_amdgcn_s_setprio(0);
     }
     if (st < 8) SSDE_TR(8 + st * 10 + 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -574,15 +506,15 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
     __builtin_amdgcn_sched_barrier(0);
     SSDE_WAIT_VMCNT_FENCE(2 + n1);
     SSDE_W4_POS(1);
-    if (hasl) load_piece(st_l, 0);
+    if (hasl) load_piece(st + 3, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (st < 8) SSDE_TR(8 + st * 10 + 2);
-    if (has1 && !SSDE_W4_EXP_NOXFORM) {
-      SSDE_W4_HI();
+    if (has1) {
+      __builtin_amdgcn_s_setprio(2);
       bt6(td, to);
 #pragma unroll
       for (int a = 0; a < 6; ++a) *(ssde_lds_float2*)(tw + a * 6 * kVP) = to[a];
-      SSDE_W4_LO();
+      __builtin_amdgcn_s_setprio(0);
     }
     if (st < 8) SSDE_TR(8 + st * 10 + 3);
     __builtin_amdgcn_sched_barrier(0);
@@ -591,10 +523,10 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
     __builtin_amdgcn_sched_barrier(0);
     SSDE_WAIT_VMCNT_FENCE(1 + 2 * n1 + nl);
     SSDE_W4_POS(3);
-    if (hasl) load_piece(st_l, 1);
+    if (hasl) load_piece(st + 3, 1);
     __builtin_amdgcn_sched_barrier(0);
     if (st < 8) SSDE_TR(8 + st * 10 + 4);
-    if (has1 && !SSDE_W4_EXP_NOXFORM) {
+    if (has1) {
 #pragma unroll
       for (int b = 0; b < 6; ++b) td[b] = *(ssde_lds_float2*)(vp + b * kVP);
     }
@@ -606,12 +538,12 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
     SSDE_W4_POS(5);
     if (has1) SSDE_GLDS16_S_SAME_BASE(w_voff, wb, wl, 1024);
     __builtin_amdgcn_sched_barrier(0);
-    if (has1 && !SSDE_W4_EXP_NOXFORM) {
-      SSDE_W4_HI();
+    if (has1) {
+      __builtin_amdgcn_s_setprio(2);
       bt6(td, to);
 #pragma unroll
       for (int b = 0; b < 6; ++b) *(ssde_lds_float2*)(vp + b * kVP) = to[b];
-      SSDE_W4_LO();
+      __builtin_amdgcn_s_setprio(0);
     }
     if (st < 8) SSDE_TR(8 + st * 10 + 5);
     __builtin_amdgcn_sched_barrier(0);
@@ -626,20 +558,7 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
     emit_v(Vc, st, 2);
 #undef SSDE_W4_POS
     if (st < 8) SSDE_TR(8 + st * 10 + 6);
-    if (has2 && gy && !SSDE_W4_EXP_NOXFORM) {
-      SSDE_WAIT_VMCNT_FOR(3 * n1, rv[0], rv[1]);
-      SSDE_W4_HI();
-      store_raw(rawb + cur * raw_stride, st + 2);
-      SSDE_W4_LO();
-    }
-#if SSDE_W4_EXP_NOBARRIER
-    // TIMING EXPERIMENT ONLY (wrong results): no stage barrier -- the waves run free, an upper bound on what any scheme that
-    // lets waves of a SIMD drift apart (third V buffer + LDS ready/free counters) could gain in the loop
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-#else
     SSDE_LDS_BARRIER();
-#endif
     if (st < 8) SSDE_TR(8 + st * 10 + 8);
   };
   {
@@ -647,20 +566,14 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
     // (written so that the stage that consumes the halo in flight is the only successor of the stage that fetched it: the
     //  registers of an asm load are not protected by hipcc on a path it merely cannot rule out, tests/test_isa_guards.py)
     int st = 0;
-    if (!grp_y) {
-      if (nst >= 3) {
-        for (; st + 3 < nst; ++st) stage(T{}, T{}, T{}, F{}, st);
-        stage(T{}, T{}, F{}, F{}, st); ++st;
-        stage(T{}, F{}, F{}, F{}, st); ++st;
-      } else if (nst == 2) {
-        stage(T{}, F{}, F{}, F{}, st); ++st;
-      }
-      stage(F{}, F{}, F{}, F{}, st);
-    } else {
-      for (; st + 2 < nst; ++st) stage(T{}, T{}, T{}, T{}, st);
-      if (nst >= 2) { stage(T{}, F{}, F{}, T{}, st); ++st; }
-      stage(F{}, F{}, F{}, T{}, st);
+    if (nst >= 3) {
+      for (; st + 3 < nst; ++st) stage(T{}, T{}, T{}, st);
+      stage(T{}, T{}, F{}, st); ++st;
+      stage(T{}, F{}, F{}, st); ++st;
+    } else if (nst == 2) {
+      stage(T{}, F{}, F{}, st); ++st;
     }
+    stage(F{}, F{}, F{}, st);
   }
   SSDE_TR(3);
 
@@ -817,11 +730,6 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
       __syncthreads();
       if (rnd == 1 && tid == 0) { sy[0] = 0u; sy[1] = 0u; }              // ready for the next launch that is dealt these slots
     }
-#if SSDE_W4_EXP_NOSTORE
-    // TIMING EXPERIMENT ONLY (no output): the epilogue's coalesced store skipped -- an upper bound on what overlapping the
-    // store burst with the next tile's fill could gain
-    if (p.scale == 12345.f)
-#endif
     // round 1 has no accumulators left: all 8 rows of a thread (residual loads) in flight instead of 4
     if (rnd == 0) ssde_store_tile<256, 64, kEpiThreads, 4, 0>(park, kLdt, n0, e, pixfn, gn_entry, rpi_log2, gn_max);
     else ssde_store_tile<256, 64, kEpiThreads, SSDE_W4_EPI_BATCH, 0>(park, kLdt, n0, e, pixfn, gn_entry, rpi_log2, gn_max);
@@ -895,8 +803,7 @@ int ssde_conv_wino4_launch(const ssde_conv_args* a, void* stream, int* lds_out) 
   }
   const int halo_px = imgs * (4 * tht + 2) * (4 * twt + 2);
   SSDE_REQUIRE(halo_px <= kMaxRaw * kThreads, "conv(winograd 4x4): halo of %d pixels exceeds the staging plan", halo_px);
-  const int raw_plane = SSDE_W4_RAWPAD ? ((2 * halo_px + 63) & ~63) + 32 : 2 * halo_px;
-  int lds = (2 * kVFloats + 2 * kUFloats + 2 * 2 * raw_plane) * 4;
+  int lds = (2 * kVFloats + 2 * kUFloats + 2 * 2 * 2 * halo_px) * 4;
   if (gn) lds += (2 * imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
   const int lds_epi = kPos * 16 * kLdm * 4;
   if (lds < lds_epi) lds = lds_epi;

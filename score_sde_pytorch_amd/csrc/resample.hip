@@ -77,10 +77,6 @@ __global__ __launch_bounds__(256) void upfirdn_kernel(const FirParams p) {
 }
 
 
-#ifndef SSDE_FIR_STAGE_U
-#define SSDE_FIR_STAGE_U 4       // (1 = one load in flight per thread, the form of rounds 2-5: A/B variant only)
-#endif
-
 // ---- LDS-staged tiles for the 4x4 FIR -----------------------------------------------------------------------------
 constexpr int kFirCh = 32;        // channels per workgroup: 8 lanes x float4 = one 128-byte line per pixel
 struct FirTileParams {
@@ -120,7 +116,7 @@ __global__ __launch_bounds__(256) void upfirdn_tile_kernel(const FirTileParams p
   // kStageU loads of a thread are issued before the first of them is parked: with one load in flight per thread (a loop the
   // compiler cannot unroll: the tile size is a launch argument) the 4-12 round trips of a tile were paid one after the other
   // and the pass sat at 0.3-0.5 of the HBM peak on every shape but the largest (profiles/r6_fir_staging_unroll.txt)
-  constexpr int kStageU = SSDE_FIR_STAGE_U;
+  constexpr int kStageU = 4;
   for (int base = slot; base < npix; base += 32 * kStageU) {
     float4 v[kStageU];
 #pragma unroll

@@ -363,10 +363,8 @@ __device__ __forceinline__ void ssde_gn_merge16(const float* part0, const float*
 // is flushed when its last row has been stored, entries gn_entry, gn_entry + 1, ... (< gn_entry_max: the batch tail).
 template <int ROWS, int NCOLS, int NT, int BATCH = 4, int SWZ = 0, class PixFn>
 __device__ __forceinline__ void ssde_store_tile(float* tile, int ld, int n0, const SsdeEpi& e, PixFn pixfn, int gn_entry = -1,
-                                                int rpi_log2 = 30, int gn_entry_max = 0x7fffffff, int tid_in = -1) {
-  // tid_in: the caller's (opaque) copy of the thread id -- a persistent kernel passes one it re-derives per tile so that the row /
-  // pixel arithmetic below is not hoisted out of its tile loop and kept in registers across the matrix loop (conv_wino4r.hip)
-  const int tidx = tid_in >= 0 ? tid_in : (int)threadIdx.x;
+                                                int rpi_log2 = 30, int gn_entry_max = 0x7fffffff) {
+  const int tidx = threadIdx.x;
   constexpr int C4N = NCOLS / 4, TOTAL = ROWS * C4N, ITERS = TOTAL / NT, RSTEP = NT / C4N;
   static_assert(TOTAL % NT == 0 && NT % C4N == 0 && 64 % C4N == 0, "a thread owns one channel quad of ITERS rows");
   const int c = (tidx % C4N) * 4, row0 = tidx / C4N;

@@ -730,15 +730,9 @@ class Lowering:
         CIFAR sampler, images/s on one box): four cout tiles up 4.68-4.70, + input at most twice the output 4.71-4.73, everywhere
         4.75 -- so: wherever F(4x4,3x3) runs and the kernel's shape limits allow.  In a training program the pass's output is
         also the F(4x4,3x3) weight gradient's input (v_pre).
-        SSDE_WINO4_TWO: 0 = never, 1 = from four cout tiles up or input <= 2 x output, 3 = round 4's rule (four cout tiles)."""
-        mode = os.environ.get("SSDE_WINO4_TWO", "2")
-        if mode == "0" or 36 * self.n * (h // 4) * (w // 4) * c_in * 4 >= 2 ** 32 or c_in % 8 != 0:
-            return False
-        if mode == "3":
-            return c_out >= 256
-        if mode == "1":
-            return c_out >= 256 or c_in <= 2 * c_out or bool(getattr(self, "emit_wino_v", False))
-        return True
+        SSDE_WINO4_TWO=0 keeps every F(4x4,3x3) layer on the one fused kernel (the reference of the bit-identity tests)."""
+        return os.environ.get("SSDE_WINO4_TWO", "2") != "0" and 36 * self.n * (h // 4) * (w // 4) * c_in * 4 < 2 ** 32 \
+            and c_in % 8 == 0
 
     def _wgrad_takes_wino4(self, f):
         """Would ssde_conv_wgrad run the weight gradient of this forward conv on the F(4x4,3x3) path?  (shape-only query with
@@ -787,33 +781,23 @@ class Lowering:
         # (one workgroup per CU: F(4x4,3x3) workgroups own a whole CU's LDS and registers)
         if mode != "3" and legal4 and h >= 16 and w >= 16 and -(-(self.n * h * w) // 512) * n_tiles >= self.cus:
             return four()
-        # Fewer tiles than that (8x8 maps at batch 256: 128 tiles of 8 images x 64 couts): the kernel splits its reduction
-        # over 2 or 4 workgroups per tile (conv_wino4.hip, ssde_conv_wino4_splits -- the same rule).  Measured
-        # (profiles/r3_wino4_split_reduction_ab.txt): 17-40 % over the unsplit kernel, but only level with F(2x2,3x3) on
-        # 8x8 maps at batch 256 and 128 (0.123 / 0.184 ms against 0.110 / 0.190 ms; the PC iteration 58.1 against 57.0 ms),
-        # so the heuristic takes it only on request: SSDE_W4_SPLIT_MIN_WGS=<workgroups after the split, e.g. 192>
-        if mode != "3" and legal4 and "SSDE_W4_SPLIT_MIN_WGS" in os.environ:
-            wgs4 = -(-(-(-(self.n * h * w) // 512)) // 8) * 8 * n_tiles
-            splits = 1
-            if c_out % 4 == 0 and os.environ.get("SSDE_CONV_KSPLIT", "1") != "0":
-                splits = 4 if wgs4 <= self.cus // 4 and c_in >= 256 else 2 if wgs4 <= self.cus // 2 and c_in >= 128 else 1
-            if splits > 1 and wgs4 * splits >= int(os.environ["SSDE_W4_SPLIT_MIN_WGS"]):
-                return 4
+        # Fewer tiles than that (8x8 maps at batch 256: 128 tiles of 8 images x 64 couts): the fused kernel's split reduction
+        # (conv_wino4.hip) is 17-40 % faster than its unsplit form but only level with F(2x2,3x3) there
+        # (profiles/r3_wino4_split_reduction_ab.txt), so the lowering does not take it.
         # The register-fed matrix kernel splits its reduction too (conv_wino4r.hip, ssde_conv_wino4r_splits -- the same rule
         # here): its channel stage is ~2450 cycles against the fused kernel's ~4600, so where the shares fill exactly one round of
         # workgroups, transform pass + split matrix kernel beat F(2x2,3x3).  TWO shares -- the 8x8 maps at batch 256: 128 tiles ->
         # 256 workgroups: 256->256 0.077 against 0.109 ms, 512->256 0.112 against 0.193 (profiles/r5_wino4r_split_8x8.txt); with 128
         # input channels (16 stages per share) the hand-over costs what the split saves and F(2x2,3x3) stays.
-        # SSDE_W4R_SPLIT=0 keeps round 4's choice.
+        # SSDE_CONV_KSPLIT=0 (the library's SSDE_CONVF_NO_KSPLIT) switches every split off.
         if mode != "3" and legal4 and c_in % 16 == 0 and c_in >= 256 and c_out % 4 == 0 \
-                and os.environ.get("SSDE_W4R_SPLIT", "1") != "0" and os.environ.get("SSDE_CONV_KSPLIT", "1") != "0":
+                and os.environ.get("SSDE_CONV_KSPLIT", "1") != "0":
             wgs4 = -(-(-(-(self.n * h * w) // 512)) // 8) * 8 * n_tiles
             if self.cus // 2 < wgs4 * 2 <= self.cus and self._wino4_two_kernels(h, w, c_out, c_in):
                 return 6
             # (four shares filling one round -- the 8x8 maps at batch 128, the training step: 256->256 0.102 -> 0.063 ms, 512->256 0.184 -> 0.082,
-            #  step 0.0548 -> 0.0530 s, profiles/r5_wino4r_split_8x8_batch128.txt, r5_wino4r_split4_train_ab.txt; SSDE_W4R_SPLIT4=0 switches it off)
-            if os.environ.get("SSDE_W4R_SPLIT4", "1") == "1" and c_in % 32 == 0 and self.cus // 2 < wgs4 * 4 <= self.cus \
-                    and self._wino4_two_kernels(h, w, c_out, c_in):
+            #  step 0.0548 -> 0.0530 s, profiles/r5_wino4r_split_8x8_batch128.txt, r5_wino4r_split4_train_ab.txt)
+            if c_in % 32 == 0 and self.cus // 2 < wgs4 * 4 <= self.cus and self._wino4_two_kernels(h, w, c_out, c_in):
                 return 6
         # tools/heuristic_sweep.py (profiles/r2_heuristic_sweep.txt): F(4x4,3x3) wins from one of its workgroups per CU (256),
         # F(2x2,3x3) over the direct kernel from half a workgroup per CU (128; by 2-6 %; at 64 the direct kernel is 1.5x

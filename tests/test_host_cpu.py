@@ -167,10 +167,10 @@ def test_dry_lowering_of_baseline_configs(name, batch, gflop_per_img):
         eng.program.run()
 
 
-def test_two_kernel_winograd_is_the_form_of_every_f4x4_layer(monkeypatch):
+def test_every_f4x4_layer_runs_as_two_kernels(monkeypatch):
     """engine.Lowering._wino4_two_kernels: at the BASELINE sampler shape every F(4x4,3x3) layer is lowered as transform pass +
-    register-fed matrix kernel (SSDE_TILE_WINOGRAD4R) and owns a transformed-input buffer of 36/16 of its input; SSDE_WINO4_TWO=3
-    is round 4's rule (from four cout tiles up: the 128-cout layers on the fused kernel), SSDE_WINO4_TWO=0 switches the form off."""
+    register-fed matrix kernel (SSDE_TILE_WINOGRAD4R) and owns a transformed-input buffer of 36/16 of its input; SSDE_CONV_KSPLIT=0
+    keeps the 8x8 maps off it (no split reduction), SSDE_WINO4_TWO=0 switches the form off."""
     from score_sde_pytorch_amd import engine, _lib as L
     from score_sde_pytorch_amd.models import utils as mutils
     monkeypatch.setenv("SSDE_WINOGRAD", "1")               # the production heuristic (the suite's default forces F(2x2,3x3))
@@ -188,25 +188,21 @@ def test_two_kernel_winograd_is_the_form_of_every_f4x4_layer(monkeypatch):
     assert len(two) >= 40 and not [c for c in cs if c[0] == L.TILE_WINOGRAD4]
     assert all(c[2] >= 8 and c[3] % 8 == 0 for c in two)
     # the 8x8 maps (128 workgroup tiles at batch 256): two shares of the split matrix kernel fill the chip -- every layer with
-    # 256 input channels or more; the 128-channel one stays on F(2x2,3x3); SSDE_W4R_SPLIT=0 is round 4's choice
+    # 256 input channels or more; the 128-channel one stays on F(2x2,3x3); without the split none of them
     at8 = [c for c in cs if c[2] == 8 and c[0] in (L.TILE_WINOGRAD4R, L.TILE_WINOGRAD)]
     assert len(at8) >= 20 and all((c[0] == L.TILE_WINOGRAD4R) == (c[3] >= 256) for c in at8)
-    monkeypatch.setenv("SSDE_W4R_SPLIT", "0")
+    monkeypatch.setenv("SSDE_CONV_KSPLIT", "0")
     assert not [c for c in convs(engine.UNetEngine(model, 256, 32, 32, torch.device("cpu"))) if c[0] == L.TILE_WINOGRAD4R and c[2] < 16]
-    monkeypatch.delenv("SSDE_W4R_SPLIT")
+    monkeypatch.delenv("SSDE_CONV_KSPLIT")
     # batch 128 (the training step): four shares
     cs128 = convs(engine.UNetEngine(model, 128, 32, 32, torch.device("cpu")))
     assert len([c for c in cs128 if c[2] == 8 and c[0] == L.TILE_WINOGRAD4R]) >= 20
-    monkeypatch.setenv("SSDE_W4R_SPLIT4", "0")
+    monkeypatch.setenv("SSDE_CONV_KSPLIT", "0")
     assert not [c for c in convs(engine.UNetEngine(model, 128, 32, 32, torch.device("cpu"))) if c[2] == 8 and c[0] == L.TILE_WINOGRAD4R]
-    monkeypatch.delenv("SSDE_W4R_SPLIT4")
+    monkeypatch.delenv("SSDE_CONV_KSPLIT")
     for tile, c_out, h, c_in, v in two:
         assert v is not None and v.numel == 36 * 256 * (h // 4) ** 2 * c_in
     assert all(c[4] is None for c in cs if c[0] != L.TILE_WINOGRAD4R)          # inference: nobody else wants the transformed input
-    monkeypatch.setenv("SSDE_WINO4_TWO", "3")
-    cs = convs(engine.UNetEngine(model, 256, 32, 32, torch.device("cpu")))
-    two, one = [c for c in cs if c[0] == L.TILE_WINOGRAD4R], [c for c in cs if c[0] == L.TILE_WINOGRAD4]
-    assert len(two) >= 15 and len(one) >= 15 and all(c[1] >= 256 for c in two) and all(c[1] < 256 for c in one)
     monkeypatch.setenv("SSDE_WINO4_TWO", "0")
     assert not [c for c in convs(engine.UNetEngine(model, 256, 32, 32, torch.device("cpu"))) if c[0] == L.TILE_WINOGRAD4R]
 

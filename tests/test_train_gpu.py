@@ -185,10 +185,9 @@ def test_conv3x3_winograd_f4x4_in_two_kernels():
     T.check_conv_winograd4_two_kernels("cuda", big=True)
 
 
-def test_conv3x3_winograd_f4x4_matrix_kernel_persistent_workgroups(monkeypatch):
-    """the same cases on a pretend 8-CU device: launches of more than 8 tiles run as ONE workgroup per CU walking several tiles
-    (conv_wino4r_kernel<1, true>: the next tile's first loads are issued from the epilogue of the current one, empty padding tiles
-    are skipped) -- bit-identical to the one-kernel form when fed its by-product, like the one-tile-per-workgroup launch"""
+def test_conv3x3_winograd_f4x4_in_two_kernels_on_eight_cus(monkeypatch):
+    """the same cases on a pretend 8-CU device (SSDE_NUM_CUS=8): every launch is several rounds of workgroups and none splits its
+    reduction; the matrix kernel stays bit-identical to the one-kernel form when fed its by-product"""
     monkeypatch.setenv("SSDE_NUM_CUS", "8")
     T.check_conv_winograd4_two_kernels("cuda", big=True)
 
