@@ -14,7 +14,8 @@ replication (one independent sampler per GPU, no collectives) -> "sca
 Weights: deterministic random init of the full architecture (every tensor re-randomised, SURVEY F8);
 data: synthetic prior noise.  fp32 end to end (dtype "f32"), as the reference.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the JSON line.  With --full the line
+also carries (the --no-* options take legs out of a full run)
   roofline     -- the dominant kernel class (the 3x3 convolution launches of one U-Net evaluation, HIP events on the
                   launch stream).  `frac` = EXECUTED matrix FLOP/s over the 157.3 TFLOP/s fp32 MFMA peak: a launch on
                   the Winograd F(2x2,3x3) kernel executes 1/2.25 of its direct-form FLOPs, one on the F(4x4,3x3) kernel
@@ -28,6 +29,9 @@ The JSON line also carries
                   sample (rank 0, N=1 only): K PC iterations at the config batch, and a DSM training step;
   extra        -- compact results of the other BASELINE configs measured in the same run: `ffhq256` (configs[3]),
                   `subvp_ode` (configs[4]); `train` (configs[2]) is a top-level key;
+  matrix_*     -- the sampler and the training step in the other matrix mode;
+  telemetry    -- clock / power / temperature beside every timed leg.
+Every run carries
   rccl_ranks   -- world size confirmed by an actual 1-element all-reduce over RCCL (N > 1).
 """
 import argparse
@@ -57,6 +61,10 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--sde-steps", type=int, default=1000)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: roofline and per-class kernel times, the CPU baseline, the DSM training "
+                         "step with its exchange legs and replica check, the other matrix mode, the other BASELINE configs and telemetry "
+                         "(the --no-* options below take legs out of it).  Without it a run times the headline workload alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=256, help="batch of the CPU-oracle sampler sample (config batch)")
@@ -90,7 +98,7 @@ def parse(argv=None):
                          "16/GPU); subvp_ode = configs[4] (DDPM++ sub-VP, probability-flow ODE sampler with RK45; 1 step = 1 solve); "
                          "subvp_likelihood = configs[4]'s likelihood.py solve at rtol = atol = 1e-5")
     ap.add_argument("--likelihood-tol", type=float, default=1e-5,
-                    help="rtol = atol of the likelihood solve inside the default run (1e-5 = the config's own, likelihood.py:40; ~110 s)")
+                    help="rtol = atol of the likelihood solve inside a --full run (1e-5 = the config's own, likelihood.py:40; ~110 s)")
     ap.add_argument("--train-batch", type=int, default=128)
     ap.add_argument("--train-steps", type=int, default=100, help="timed training steps (SURVEY 8d: 100), a fresh batch each")
     ap.add_argument("--train-warmup", type=int, default=20, help="untimed training steps before them (SURVEY 8d: 20)")
@@ -100,13 +108,19 @@ def parse(argv=None):
                          "staged through the host; with --share-device it runs the N > 1 code paths on a single GPU)")
     ap.add_argument("--share-device", action="store_true",
                     help="rank r uses GPU r %% (visible GPUs): N ranks on fewer GPUs -- a functional run of the multi-rank branches "
-                         "(self-launch, rank census, bucketed gradient exchange, exposed-exchange leg, parameter broadcast), NOT a "
+                         "(self-launch, rank census; with --full the bucketed gradient exchange, exposed-exchange leg, parameter broadcast), NOT a "
                          "scaling measurement; needs --dist-backend gloo (RCCL refuses two ranks on one device)")
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.train_only or args.workload not in ("cifar10", "ffhq256")):
         ap.error("--dump-outputs writes the outputs of the PC sampler: --workload cifar10 or ffhq256, without --train-only")
+    if (args.dump_ops or args.dump_train_ops) and not args.full:
+        ap.error("--dump-ops and --dump-train-ops write the per-kernel times of the roofline legs: they need --full")
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps of the headline workload, --dump-outputs and the line
+        args.no_roofline = args.no_cpu_baseline = args.no_train = args.no_other_matrix = args.no_extras = True
+        args.no_exchange_probe = args.no_telemetry = True
     return args
 
 
@@ -177,7 +191,7 @@ def bench_train(args, cfg, dev, dist, world, rank, sync_all, leg="train"):
     eng = fs.eng
     exposed_ms = None
     replicas_equal = None
-    if dist is not None:
+    if dist is not None and args.full:
         # data parallel = same parameters everywhere after every step: compare a checksum and the extremes of the flat
         # parameter buffer across ranks (before the no-exchange leg below, which lets them diverge on purpose)
         flat = eng.flat.data
@@ -796,7 +810,7 @@ def bench_pc(args, cfg_name, B, N, dev, dist, world, rank, steps, warmup, detail
 
 
 def bench_ode_compact(args, dev, dist, world, rank):
-    """BASELINE configs[4] inside the default run: ONE solve of a batch (RK45 rtol = atol = 1e-5, eps 1e-3) after a few warm-up
+    """BASELINE configs[4] inside a --full run: ONE solve of a batch (RK45 rtol = atol = 1e-5, eps 1e-3) after a few warm-up
     evaluations of the right-hand side (engine lowering, graph of the integrator's stage kernels)."""
     import _util
     from score_sde_pytorch_amd import sde_lib, sampling
@@ -1209,7 +1223,7 @@ def main():
     if args.share_device and world > 1:
         out["scaling"] = "none: %d ranks share %d GPU(s) over %s -- a functional run of the multi-rank code paths, not a scaling point" \
             % (world, n_dev, args.dist_backend)
-    _phase("sampler + roofline done")
+    _phase("sampler done" if roof is None else "sampler + roofline done")
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, cfg, model, sd, R, args.sde_steps)
         _phase("cpu baseline done")
@@ -1255,7 +1269,7 @@ def main():
         out["matrix_" + other] = mx
         _phase("other matrix mode (%s) done" % other)
     if not args.no_extras:
-        # the other BASELINE configs, compact, so that the driver's default run witnesses them
+        # the other BASELINE configs, compact, so that a --full run witnesses them
         extra = {}
         with matrix_mode(args.matrix):                # (the other configs run in the headline's matrix mode)
             r3, e3, m3, _, _ = bench_pc(args, "ve/ffhq_256_ncsnpp_continuous", 16, 2000, dev, dist, world, rank, min(args.steps, 5), 2, False,

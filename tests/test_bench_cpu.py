@@ -1,4 +1,4 @@
-"""bench.py's host logic on the CPU: the schedule bookkeeping of the timed PC iterations and --dump-outputs."""
+"""bench.py's host logic on the CPU: the schedule bookkeeping of the timed PC iterations, --dump-outputs and what a plain run and a --full run measure."""
 import os
 import sys
 
@@ -49,6 +49,24 @@ def test_bench_rejects_steps_below_one_and_dumps_outside_the_sampler():
     with pytest.raises(SystemExit):
         bench.parse(["--dump-outputs", "out", "--workload", "subvp_ode"])
     assert bench.parse(["--dump-outputs", "out", "--steps", "4"]).dump_outputs == "out"
+
+
+LEGS = ("no_roofline", "no_cpu_baseline", "no_train", "no_other_matrix", "no_extras", "no_exchange_probe", "no_telemetry")
+
+
+def test_a_plain_bench_run_times_the_headline_alone_and_full_measures_the_rest():
+    plain = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and all(getattr(plain, k) for k in LEGS)
+    assert (plain.steps, plain.warmup, plain.prewarm_s, plain.batch, plain.sde_steps) == (5, 2, 3.0, 256, 1000)
+    full = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full"])
+    assert full.full and not any(getattr(full, k) for k in LEGS)
+    some = bench.parse(["--full", "--no-train", "--no-extras"])
+    assert some.no_train and some.no_extras and not (some.no_roofline or some.no_cpu_baseline or some.no_other_matrix)
+    # the per-kernel lists come from the roofline legs
+    for opt in ("--dump-ops", "--dump-train-ops"):
+        with pytest.raises(SystemExit):
+            bench.parse([opt, "ops.json"])
+        assert getattr(bench.parse([opt, "ops.json", "--full"]), opt[2:].replace("-", "_")) == "ops.json"
 
 
 def test_dump_outputs_writes_float32_arrays(tmp_path):

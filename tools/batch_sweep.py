@@ -17,7 +17,7 @@ if __name__ == "__main__":
         for mode, label in (("1", "heuristic"), ("0", "direct"), ("2", "F(2x2) where legal"), ("4", "F(4x4) where legal")):
             env = dict(os.environ, SSDE_WINOGRAD=mode)
             r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(b), "--steps", "10", "--warmup", "3",
-                                "--no-cpu-baseline", "--no-extras", "--no-train"], env=env, capture_output=True, text=True)
+                                "--full", "--no-cpu-baseline", "--no-extras", "--no-train"], env=env, capture_output=True, text=True)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if not line:
                 row.append("%s: failed (%s)" % (label, r.stderr.strip().splitlines()[-1] if r.stderr.strip() else "?"))
