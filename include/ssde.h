@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 10  /* (still 10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 11  /* 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
@@ -116,6 +116,12 @@ typedef struct ssde_conv_args {
   int32_t gn_in_slices0, gn_in_slices1;
   float gn_in_eps;
   int32_t _pad_gn_in;
+  /* ABI 11 -- SSDE_TILE_WINOGRAD4P only, REQUIRED there: the launch's workspace, the transformed input V[pos][(c0+c1)/4][t][4]
+   * (wino_v's layout, 36 * N*H*W/16 * (c0+c1) floats) followed by the products of every reduction share,
+   * [shares][36][N*H*W/16][roundup(c_out, 64)].  ssde_conv_ws_floats(args) returns what the library's choice of shares needs;
+   * a smaller workspace makes the launch take fewer shares.  Nobody reads it after the launch. */
+  float* wino_ws;
+  int64_t wino_ws_floats;
 } ssde_conv_args;
 
 enum { SSDE_CONVF_V_GIVEN = 1u,      /* SSDE_TILE_WINOGRAD4R: wino_v already holds B^T pro(main) B -- skip the transform pass */
@@ -130,7 +136,9 @@ enum { SSDE_CONVF_V_GIVEN = 1u,      /* SSDE_TILE_WINOGRAD4R: wino_v already hol
        SSDE_CONVF_NO_SMALL_COUT = 256u,/* 3x3 / stride 1 convolutions with at most four output channels (the image heads) on the general
                                           direct kernel instead of conv_small.hip (A/B runs, tests) */
        SSDE_CONVF_X6_WIDE = 512u,    /* bf16x6 GEMM: force the 128 x 256 tile wherever c_out % 256 == 0 (default: where its workgroups fill the device) */
-       SSDE_CONVF_X6_NO_WIDE = 1024u };/* bf16x6 GEMM: never take it */
+       SSDE_CONVF_X6_NO_WIDE = 1024u,/* bf16x6 GEMM: never take it */
+       SSDE_CONVF_KSPLIT2 = 2048u,   /* SSDE_TILE_WINOGRAD4P: two reduction shares where the channel count allows (else one) */
+       SSDE_CONVF_KSPLIT4 = 4096u }; /* SSDE_TILE_WINOGRAD4P: four shares (else two, else one); SSDE_CONVF_NO_KSPLIT: one */
 enum { SSDE_TILE_AUTO = 0, SSDE_TILE_256x64 = 1, SSDE_TILE_128x64 = 2, SSDE_TILE_64x64 = 3, SSDE_TILE_256x32 = 4,
        /* Winograd F(2x2,3x3) kernel (3x3, stride 1, pad 1, even output, no aux): w_main must then be packed as
         * [ceil(Cin/8)][ceil(Cout/64)][16 positions][4 channel pairs][64 couts, bit 4 ^= pair parity][2], G g G^T */
@@ -152,7 +160,14 @@ enum { SSDE_TILE_AUTO = 0, SSDE_TILE_256x64 = 1, SSDE_TILE_128x64 = 2, SSDE_TILE
         * (SSDE_PACK_WINO4R):
         * [ceil(Cin/4)][ceil(Cout/64)][8 waves (q, h)][4 pieces x [64 lanes][4] | [64 lanes][2]] where lane (lh, li) of wave (q, h)
         * holds, of cout 32 h + li and channels 2 lh, 2 lh + 1, the positions q + 4 (2 i), q + 4 (2 i + 1) in piece i and q + 32 last */
-       SSDE_TILE_WINOGRAD4R = 9 };
+       SSDE_TILE_WINOGRAD4R = 9,
+       /* F(4x4,3x3) unfused and batched over the 36 transform positions (conv_wino4p.hip, ABI 11), for maps with few tiles (the
+        * 4x4 maps: one tile per image): the transform pass into ssde_conv_args.wino_ws (REQUIRED; wino_v is not used), 36
+        * independent GEMMs [tiles x Cin] x [Cin x Cout] with the reduction split over 1, 2 or 4 shares into separate slabs, and
+        * an output pass that sums the slabs in a fixed order, applies A^T M A and the epilogue.  Cin % 32 == 0, c_out % 4 == 0,
+        * no aux; GroupNorm partials one slice per tile.  w_main packed (SSDE_PACK_WINO4P) as
+        * [36 positions][ceil(Cin/4)][roundup(Cout, 64)][4 channels], G g G^T */
+       SSDE_TILE_WINOGRAD4P = 10 };
 
 /* ---- GroupNorm statistics: mean / rstd per (sample, group) -----------------
  * replaces the reduction half of nn.GroupNorm(min(C/4,32), C, eps=1e-6)
@@ -462,7 +477,8 @@ typedef struct ssde_memset_args { void* dst; int64_t bytes; int32_t value; int32
  * every weight of the model from a device-resident descriptor table. */
 enum { SSDE_PACK_CONV3 = 1, SSDE_PACK_WINO3 = 2, SSDE_PACK_MATRIX = 3, SSDE_PACK_VECTOR = 4,
        SSDE_PACK_WINO4 = 5 /* conv -> the F(4x4,3x3) image of SSDE_TILE_WINOGRAD4 */,
-       SSDE_PACK_WINO4R = 6 /* conv -> the per-lane F(4x4,3x3) image of SSDE_TILE_WINOGRAD4R */ };
+       SSDE_PACK_WINO4R = 6 /* conv -> the per-lane F(4x4,3x3) image of SSDE_TILE_WINOGRAD4R */,
+       SSDE_PACK_WINO4P = 7 /* conv -> the position-major F(4x4,3x3) image of SSDE_TILE_WINOGRAD4P */ };
 typedef struct ssde_pack_desc {
   const float* src;        /* parameter: conv [cout][cin][3][3]; matrix [cout][cin]; vector [n] */
   const float* src2;       /* vector: optional second addend (Conv_1.bias + Conv_2.bias) */
@@ -518,6 +534,8 @@ int ssde_gn_finalize(const ssde_gn_finalize_args* a, void* stream);
 /* slices per image of the GroupNorm partials this launch would write (plan only, no device access); 0 = this
  * launch cannot produce them (a workgroup tile would span several images, or c_out % 4 != 0) */
 int ssde_conv_gn_slices(const ssde_conv_args* a);
+/* floats of ssde_conv_args.wino_ws this launch needs (plan only, no device access): 0 = its route takes no workspace, < 0 = invalid */
+int64_t ssde_conv_ws_floats(const ssde_conv_args* a);
 int ssde_upfirdn2d(const ssde_upfirdn_args* a, void* stream);
 int ssde_attention(const ssde_attn_args* a, void* stream);
 int ssde_embed(const ssde_embed_args* a, void* stream);

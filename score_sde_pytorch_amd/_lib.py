@@ -10,15 +10,16 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SSDE_LIB_PATH: developer switch for A/B timing of kernel variants built by _build.build_variant (tools/ab_bench.sh)
 LIB_PATH = os.environ.get("SSDE_LIB_PATH") or os.path.join(_HERE, "libssde_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_SILU = 0, 1, 2, 3
 TILE_AUTO, TILE_256x64, TILE_128x64, TILE_64x64, TILE_256x32, TILE_WINOGRAD, TILE_WINOGRAD4 = 0, 1, 2, 3, 4, 5, 6
 TILE_WINOGRAD4R = 9       # (7, 8: the bf16-split and the LDS-fed F(4x4,3x3) kernels of round 4, tools/experiments/)
-TILES_WINOGRAD4 = (TILE_WINOGRAD4, TILE_WINOGRAD4R)
+TILE_WINOGRAD4P = 10      # F(4x4,3x3) as position-batched GEMMs (conv_wino4p.hip): the 4x4 maps
+TILES_WINOGRAD4 = (TILE_WINOGRAD4, TILE_WINOGRAD4R, TILE_WINOGRAD4P)
 # routing switches of a launch (include/ssde.h: SSDE_CONVF_*, SSDE_WGRADF_*, SSDE_GNBWDF_*)
 CONVF_V_GIVEN, CONVF_BF16X6, CONVF_NO_KSPLIT, CONVF_BKC8, CONVF_GEMM_PIPE, CONVF_NO_GEMM_PIPE, CONVF_X6_BM64, CONVF_X6_PF2, \
-    CONVF_NO_SMALL_COUT, CONVF_X6_WIDE, CONVF_X6_NO_WIDE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024
+    CONVF_NO_SMALL_COUT, CONVF_X6_WIDE, CONVF_X6_NO_WIDE, CONVF_KSPLIT2, CONVF_KSPLIT4 = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
 WGRADF_DIRECT, WGRADF_F2, WGRADF_F4_FORCE, WGRADF_NO_STREAMK, WGRADF_NO_XCD_ORDER, WGRADF_1X1_CHUNKED, WGRADF_XVEC1 = 1, 2, 4, 8, 16, 32, 64
 GNBWDF_THREE_KERNELS, GNBWDF_DEFER_PARAMS = 1, 2
 (OP_CONV, OP_GN_STATS, OP_UPFIRDN, OP_ATTN, OP_EMBED, OP_TO_NHWC, OP_TO_NCHW, OP_BIAS_ACT, OP_SUMSQ,
@@ -27,7 +28,7 @@ GNBWDF_THREE_KERNELS, GNBWDF_DEFER_PARAMS = 1, 2
  OP_GN_FINALIZE, OP_PF_DRIFT, OP_HUTCH_DIV, OP_COLSUM_FINISH, OP_GN_BWD_FINISH) = range(1, 33)
 FINISH_JOBS = 16
 COLSUMF_DEFER = 1
-PACK_CONV3, PACK_WINO3, PACK_MATRIX, PACK_VECTOR, PACK_WINO4, PACK_WINO4R = 1, 2, 3, 4, 5, 6
+PACK_CONV3, PACK_WINO3, PACK_MATRIX, PACK_VECTOR, PACK_WINO4, PACK_WINO4R, PACK_WINO4P = 1, 2, 3, 4, 5, 6, 7
 
 _fp = C.c_void_p  # device pointers are passed as integers
 
@@ -48,7 +49,7 @@ class ConvArgs(C.Structure):
                 ("bias", _fp), ("chan_add", _fp), ("chan_add_ld", C.c_int32), ("resid_post", C.c_int32),
                 ("resid", _fp), ("out_scale", C.c_float), ("flags", C.c_uint32), ("dst", _fp), ("gn_part", _fp), ("wino_v", _fp),
                 ("gn_in_part0", _fp), ("gn_in_part1", _fp), ("gn_in_slices0", C.c_int32), ("gn_in_slices1", C.c_int32),
-                ("gn_in_eps", C.c_float), ("_pad_gn_in", C.c_int32)]
+                ("gn_in_eps", C.c_float), ("_pad_gn_in", C.c_int32), ("wino_ws", _fp), ("wino_ws_floats", C.c_int64)]
 
 
 class GnStatsArgs(C.Structure):
@@ -275,7 +276,7 @@ EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attent
            "ssde_abi_version", "ssde_sizeof_op", "ssde_last_error", "ssde_conv_lds_bytes",
            "ssde_conv_wgrad", "ssde_colsum", "ssde_gn_bwd_reduce", "ssde_prologue_bwd", "ssde_attention_bwd",
            "ssde_perturb", "ssde_dsm_loss", "ssde_sumsq_flat", "ssde_adam_clip_ema", "ssde_memset", "ssde_axpy",
-           "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
+           "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_conv_ws_floats", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
            # plan-level entry points (csrc/plan.hip; argument types: plan_export.bind)
            "ssde_plan_load", "ssde_plan_load_file", "ssde_plan_destroy", "ssde_plan_info", "ssde_plan_param",
            "ssde_plan_refresh_weights", "ssde_unet_forward", "ssde_pc_reset", "ssde_pc_run", "ssde_pc_state",
@@ -374,6 +375,8 @@ def bind(lib):
         getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
     lib.ssde_conv_lds_bytes.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_conv_gn_slices.argtypes = [C.POINTER(ConvArgs)]
+    lib.ssde_conv_ws_floats.argtypes = [C.POINTER(ConvArgs)]
+    lib.ssde_conv_ws_floats.restype = C.c_int64
     lib.ssde_wgrad_scratch_floats.argtypes = [C.POINTER(WgradArgs)]
     lib.ssde_wgrad_scratch_floats.restype = C.c_int64
     lib.ssde_wgrad_wants_winograd4.argtypes = [C.POINTER(WgradArgs)]

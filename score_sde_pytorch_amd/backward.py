@@ -402,9 +402,9 @@ class TrainEngine(E.UNetEngine):
         gsrc = _src(g, g_ld)
         if ksize == 3:
             wino = low.wino_ok(h_in, w_in, ctot, g_ld) if stride == 1 else 0
-            pack = {6: E.pack_wino4r_weight, 4: E.pack_wino4_weight, 2: E.pack_wino_weight}.get(wino, E.pack_conv_weight)
+            pack = {8: E.pack_wino4p_weight, 6: E.pack_wino4r_weight, 4: E.pack_wino4_weight, 2: E.pack_wino_weight}.get(wino, E.pack_conv_weight)
             wd = self.weights.derived(wpacked, lambda w: pack(w.permute(1, 0, 2, 3).flip(2, 3)),
-                                      {6: "dgrad_wino4r", 4: "dgrad_wino4", 2: "dgrad_wino"}.get(wino, "dgrad"))
+                                      {8: "dgrad_wino4p", 6: "dgrad_wino4r", 4: "dgrad_wino4", 2: "dgrad_wino"}.get(wino, "dgrad"))
             if stride == 1:
                 low.conv(dst, h_in, w_in, ctot, main=gsrc, w_main=wd, h_in=ho, w_in=wo, stride=1, pad=1, resid=resid,
                          resid_post=1, scale=scale, wino=wino)

@@ -936,11 +936,13 @@ __global__ __launch_bounds__(256) void pack_wino3_kernel(const ssde_pack_desc* _
 // [ceil(cin/4)][ceil(cout/64)][8 waves (q, h)][9 positions q + 4 j][32 couts of half h][4].  One thread = one (cout, cin):
 // it reads the 3x3 filter once and writes its 36 positions (consecutive lanes = the 4 channels of consecutive couts: 512 B
 // runs per position).  The products are formed in
-// fp64 and rounded once, like the host packing (engine.pack_wino4_weight).
-template <bool kPerLane>
+// fp64 and rounded once, like the host packing (engine.pack_wino4_weight).  kForm 0: that image (SSDE_PACK_WINO4), 1: the per-lane
+// image of conv_wino4r.hip (SSDE_PACK_WINO4R), 2: the position-major image of conv_wino4p.hip (SSDE_PACK_WINO4P).
+template <int kForm>
 __global__ __launch_bounds__(256) void pack_wino4_kernel(const ssde_pack_desc* __restrict__ table) {
   const ssde_pack_desc d = table[blockIdx.y];
   const int ntl = (d.cout_l + 63) / 64;
+  const size_t nq = (size_t)d.n / ((size_t)36 * ntl * 256);     // channel quads
   const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                           {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
   const size_t items = (size_t)d.n / 36;
@@ -965,8 +967,11 @@ __global__ __launch_bounds__(256) void pack_wino4_kernel(const ssde_pack_desc* _
       {
         const int pos = a * 6 + b, wv = (pos & 3) * 2 + (cs >> 5), j = pos >> 2;      // (conv_wino4.hip: wave (q, h) owns positions q + 4 j of cout half h)
         const float u = (float)(t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2]);
-        if (!kPerLane) {
+        if (kForm == 0) {
           d.dst[(((r * 8 + wv) * 9 + j) * 32 + (cs & 31)) * 4 + e] = u;
+        } else if (kForm == 2) {
+          // SSDE_PACK_WINO4P: [36 positions][channel quads][cout_pad][4]
+          d.dst[(((size_t)pos * nq + c4) * ((size_t)ntl * 64) + co) * 4 + e] = u;
         } else {
           // SSDE_PACK_WINO4R (conv_wino4r.hip): wave w owns positions 4 w .. 4 w + 3 with both cout halves -- lane (lh = e >> 1,
           // li = cout & 31) holds channels 2 lh, 2 lh + 1 of couts li and 32 + li as four floats per position -- and cout half
@@ -1008,8 +1013,9 @@ extern "C" int ssde_pack_weights(const ssde_pack_args* a, void* stream) {
   switch (a->kind) {
     case SSDE_PACK_CONV3: hipLaunchKernelGGL(pack_conv3_kernel, grid, dim3(256), 0, st, a->table); break;
     case SSDE_PACK_WINO3: hipLaunchKernelGGL(pack_wino3_kernel, grid, dim3(256), 0, st, a->table); break;
-    case SSDE_PACK_WINO4: hipLaunchKernelGGL(pack_wino4_kernel<false>, grid, dim3(256), 0, st, a->table); break;
-    case SSDE_PACK_WINO4R: hipLaunchKernelGGL(pack_wino4_kernel<true>, grid, dim3(256), 0, st, a->table); break;
+    case SSDE_PACK_WINO4: hipLaunchKernelGGL(pack_wino4_kernel<0>, grid, dim3(256), 0, st, a->table); break;
+    case SSDE_PACK_WINO4R: hipLaunchKernelGGL(pack_wino4_kernel<1>, grid, dim3(256), 0, st, a->table); break;
+    case SSDE_PACK_WINO4P: hipLaunchKernelGGL(pack_wino4_kernel<2>, grid, dim3(256), 0, st, a->table); break;
     case SSDE_PACK_MATRIX: hipLaunchKernelGGL(pack_matrix_kernel, grid, dim3(256), 0, st, a->table); break;
     case SSDE_PACK_VECTOR: hipLaunchKernelGGL(pack_vector_kernel, grid, dim3(256), 0, st, a->table); break;
     default: ssde_set_error("pack_weights: unknown kind %d", a->kind); return SSDE_EINVAL;

@@ -565,6 +565,7 @@ static ssde_wino_launcher wino_launcher(int tile) {
     case SSDE_TILE_WINOGRAD: return ssde_conv_wino_launch;
     case SSDE_TILE_WINOGRAD4: return ssde_conv_wino4_launch;
     case SSDE_TILE_WINOGRAD4R: return ssde_conv_wino4r_launch;
+    case SSDE_TILE_WINOGRAD4P: return ssde_conv_wino4p_launch;
     default: return nullptr;
   }
 }
@@ -630,6 +631,11 @@ extern "C" int ssde_conv_gn_slices(const ssde_conv_args* a) {
   ConvPlan pl;
   if (make_plan(&q, &pl)) return 0;
   return pl.gn_slices;
+}
+
+extern "C" int64_t ssde_conv_ws_floats(const ssde_conv_args* a) {
+  if (a && a->tile == SSDE_TILE_WINOGRAD4P) return ssde_conv_wino4p_ws_floats(a);
+  return 0;
 }
 
 extern "C" int ssde_conv_lds_bytes(const ssde_conv_args* a) {

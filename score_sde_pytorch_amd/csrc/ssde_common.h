@@ -19,6 +19,8 @@ int ssde_conv_wino4_launch(const ssde_conv_args* a, void* stream, int* lds_out);
 bool ssde_wino4_xform_merges_gn(const ssde_conv_args* a);                               // wino4_xform.hip: the pass merges the source's GroupNorm partials itself (gn_in_part0)
 int ssde_wino4_xform_vq_launch(const ssde_conv_args* a, void* stream);              // wino4_xform.hip: V = B^T pro(x) B into a->wino_v
 int ssde_conv_wino4r_launch(const ssde_conv_args* a, void* stream, int* lds_out);  // conv_wino4r.hip (two-kernel form, operands from registers)
+int ssde_conv_wino4p_launch(const ssde_conv_args* a, void* stream, int* lds_out);  // conv_wino4p.hip (position-batched GEMMs, the 4x4 maps)
+int64_t ssde_conv_wino4p_ws_floats(const ssde_conv_args* a);                       // conv_wino4p.hip: its workspace (ssde_conv_args.wino_ws)
 bool ssde_conv1x1_wants(const ssde_conv_args* a);                                    // conv1x1.hip
 int ssde_conv1x1_launch(const ssde_conv_args* a, void* stream, int* lds_out);
 unsigned* ssde_conv_sync_slots(int need);                                            // conv_mfma.hip

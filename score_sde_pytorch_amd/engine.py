@@ -31,6 +31,14 @@ INV_SQRT2 = float(1.0 / np.sqrt(2.0))
 # flops_class tags (echoed by ssde_program_run_timed; bench.py groups by them)
 FC_OTHER, FC_CONV3, FC_CONV1, FC_ATTN, FC_GN, FC_FIR = 0, 1, 2, 3, 4, 5
 
+# Lowering.wino_ok: the smallest batch whose 4x4-map 3x3 convolutions take the position-batched F(4x4,3x3) form (conv_wino4p.hip).
+# Measured against the direct kernel, GroupNorm + SiLU prologue (tools/w4p_bench.py), ms direct -> position-batched:
+#   batch 256:  256->256 0.064 -> 0.039   512->256 0.109 -> 0.055   768->256 0.153 -> 0.072
+#   batch 128:  256->256 0.039 -> 0.035   512->256 0.067 -> 0.042   768->256 0.093 -> 0.051
+#   batch 16:   256->256 0.036 -> 0.031   512->256 0.063 -> 0.040   768->256 0.088 -> 0.047
+# Smaller batches were not measured and stay on the direct kernel.
+W4P_MIN_BATCH = 16
+
 
 class Buf:
     """A symbolic activation buffer; storage is assigned by ProgramBuilder.finalize()."""
@@ -223,7 +231,8 @@ def _expand(kind, fields, fclass, fl):
     a.update(aux=_NOSRC, w_aux=None, resid=None, resid_post=0, out_scale=1.0, dst=fields["_split_tmp"], gn_part=None)
     b = dict(fields)
     b.update(main=_NOSRC, w_main=None, ksize=0, bias=None, chan_add=None, chan_add_ld=0, resid=fields["_split_tmp"],
-             resid_post=0, tile=L.TILE_AUTO, wino_v=None, gn_in_part0=None, gn_in_part1=None, gn_in_slices0=0, gn_in_slices1=0)
+             resid_post=0, tile=L.TILE_AUTO, wino_v=None, gn_in_part0=None, gn_in_part1=None, gn_in_slices0=0, gn_in_slices1=0,
+             wino_ws=None, wino_ws_floats=0)
     return [(a, fclass, fl - fl1), (b, FC_CONV1, fl1)]
 
 
@@ -353,6 +362,18 @@ def pack_wino4r_weight(w):
     return torch.cat([fp, hp], dim=3).contiguous()
 
 
+def pack_wino4p_weight(w):
+    """[Cout, Cin, 3, 3] -> the F(4x4,3x3) weights U = G g G^T (formed in fp64, stored in fp32) position-major for the 36 GEMMs
+    of conv_wino4p.hip (SSDE_TILE_WINOGRAD4P / SSDE_PACK_WINO4P): [36 positions][ceil(Cin/4)][roundup(Cout, 64)][4 channels]."""
+    cout, cin = w.shape[0], w.shape[1]
+    G = _WINO4_G.to(w.device)
+    u = torch.einsum("ak,ockl,bl->ocab", G, w.detach().to(torch.float64), G).to(torch.float32)     # [Cout, Cin, 6, 6]
+    c4, cpad = (cin + 3) // 4, (cout + 63) // 64 * 64
+    full = torch.zeros(cpad, c4 * 4, 36, dtype=torch.float32, device=w.device)
+    full[:cout, :cin] = u.reshape(cout, cin, 36)
+    return full.reshape(cpad, c4, 4, 36).permute(3, 1, 0, 2).contiguous()
+
+
 def pack_matrix(w):
     """[Cout, Cin] (nn.Linear / 1x1 conv orientation) -> [ceil(Cin/8)][roundup(Cout,64)][8]."""
     return pack_conv_weight(w.reshape(w.shape[0], w.shape[1], 1, 1))
@@ -403,7 +424,8 @@ class WeightStore:
         """[Cout, Cin, 3, 3] conv weight, optionally zero-padded to cin_pad / cout_pad channels; wino (see
         Lowering.wino_ok): 2 / True = packed for the Winograd F(2x2,3x3) kernel (G g G^T, conv_wino.hip), 4 = for the fused
         F(4x4,3x3) kernel (conv_wino4.hip), 6 = per lane for the
-        register-fed matrix kernel (conv_wino4r.hip), 0 = for the direct one."""
+        register-fed matrix kernel (conv_wino4r.hip), 8 = position-major for the position-batched GEMMs (conv_wino4p.hip),
+        0 = for the direct one."""
         def logical(w):
             w = w.to(torch.float32)
             if cin_pad and w.shape[1] < cin_pad:
@@ -414,8 +436,8 @@ class WeightStore:
         cout_l, cin_l = max(param.shape[0], cout_pad or 0), max(param.shape[1], cin_pad or 0)
         meta = dict(kind="conv3", sources=[param], logical=logical, dims=(cout_l, cin_l),
                     parts=[dict(param=param, row0=0, rows=param.shape[0], transpose=False)], cin_store=param.shape[1])
-        pack = pack_wino4r_weight if wino == 6 else pack_wino4_weight if wino == 4 else pack_wino_weight if wino else pack_conv_weight
-        kind = L.PACK_WINO4R if wino == 6 else L.PACK_WINO4 if wino == 4 else L.PACK_WINO3 if wino else L.PACK_CONV3
+        pack = {8: pack_wino4p_weight, 6: pack_wino4r_weight, 4: pack_wino4_weight}.get(wino, pack_wino_weight if wino else pack_conv_weight)
+        kind = {8: L.PACK_WINO4P, 6: L.PACK_WINO4R, 4: L.PACK_WINO4}.get(wino, L.PACK_WINO3 if wino else L.PACK_CONV3)
         recipe = [dict(kind=kind, src=param, cout=param.shape[0], cin=param.shape[1], cout_l=cout_l, cin_l=cin_l, flags=0, n="dst")]
         return self.add([param], lambda w: pack(logical(w)), meta, recipe)
 
@@ -466,14 +488,15 @@ class WeightStore:
 
     def derived(self, packed, fn, tag):
         """The input-gradient packing of an existing entry's logical weight: fn(logical) -> packed, with tag
-        'dgrad' (direct conv / matrix), 'dgrad_wino', 'dgrad_wino4' or 'dgrad_wino4r'."""
+        'dgrad' (direct conv / matrix), 'dgrad_wino', 'dgrad_wino4', 'dgrad_wino4r' or 'dgrad_wino4p'."""
         meta = self.meta[id(packed)]
         key = (id(packed), tag)
         if key not in self.meta:
             cout_l, cin_l = meta["dims"]
             if meta["kind"] == "conv3":
                 p_ = meta["sources"][0]
-                kind = {"dgrad_wino": L.PACK_WINO3, "dgrad_wino4": L.PACK_WINO4, "dgrad_wino4r": L.PACK_WINO4R}.get(tag, L.PACK_CONV3)
+                kind = {"dgrad_wino": L.PACK_WINO3, "dgrad_wino4": L.PACK_WINO4, "dgrad_wino4r": L.PACK_WINO4R,
+                        "dgrad_wino4p": L.PACK_WINO4P}.get(tag, L.PACK_CONV3)
                 recipe = [dict(kind=kind, src=p_, cout=p_.shape[0], cin=p_.shape[1],
                                cout_l=cin_l, cin_l=cout_l, flags=1, n="dst")]
             else:
@@ -602,7 +625,12 @@ class Lowering:
         """Slices per image of the GroupNorm partials the LAST launch of this conv spec would write (0: not available)."""
         if os.environ.get("SSDE_GN_FUSE", "1") == "0":
             return 0
-        sub = _expand(L.OP_CONV, fields, 0, 0.0)[-1][0]
+        return int(L.load().ssde_conv_gn_slices(C.byref(self._query_args(fields))))
+
+    def _query_args(self, fields, last=True):
+        """The ctypes arguments of the last (last=False: the first) launch of this conv spec, for the library's plan-only
+        queries."""
+        sub = _expand(L.OP_CONV, fields, 0, 0.0)[-1 if last else 0][0]
         a = L.ConvArgs()
         dummy = 0x1000                                            # the planner only tests pointers for presence
         for src_name in ("main", "aux"):
@@ -620,7 +648,7 @@ class Lowering:
             setattr(a, k, sub[k])
         a.dst = dummy
         a.flags = sub.get("flags", L.conv_route_flags())
-        return int(L.load().ssde_conv_gn_slices(C.byref(a)))
+        return a
 
     # -- GroupNorm statistics of a (possibly concatenated) NHWC source
     def gn_stats(self, t, c, hw, gn_module, t2=None, c2=0):
@@ -672,13 +700,13 @@ class Lowering:
     def conv(self, dst, h_out, w_out, c_out, main=None, w_main=None, h_in=0, w_in=0, stride=1, pad=1,
              aux=None, w_aux=None, bias=None, chan_add=None, chan_add_ld=0, resid=None, scale=1.0, tile=L.TILE_AUTO,
              resid_post=0, wino=False, stats=False):
-        """wino (2 / True, 4 or 6): w_main is Winograd-packed (see wino_ok); a fused 1x1 source then runs as a second launch.
+        """wino (2 / True, 4, 6 or 8): w_main is Winograd-packed (see wino_ok); a fused 1x1 source then runs as a second launch.
         stats=True: dst feeds a GroupNorm later -- when the launch plan allows it (ssde_conv_gn_slices) the epilogue
         also writes the tensor's partial statistics and gn_stats() turns into a finalize of a few thousand floats."""
         split_tmp = None
         if wino:
             assert main is not None and stride == 1 and pad == 1 and (h_in, w_in) == (h_out, w_out)
-            tile = L.TILE_WINOGRAD4R if wino == 6 else L.TILE_WINOGRAD4 if wino == 4 else L.TILE_WINOGRAD
+            tile = {8: L.TILE_WINOGRAD4P, 6: L.TILE_WINOGRAD4R, 4: L.TILE_WINOGRAD4}.get(wino, L.TILE_WINOGRAD)
             if aux is not None:
                 split_tmp = self.b.buf(self.n, h_out, w_out, c_out, name="wino_tmp")
         px = self.n * h_out * w_out
@@ -704,6 +732,12 @@ class Lowering:
             if tile == L.TILE_WINOGRAD4R or takes:
                 fields["wino_v"] = self.b.buf(v_floats, name="wino_v")
                 fields["_v_for_wgrad"] = bool(takes)
+        if wino == 8:
+            # the position-batched form's workspace: V, then the products of its reduction shares
+            need = int(L.load().ssde_conv_ws_floats(C.byref(self._query_args(fields, last=False))))
+            if need <= 0:
+                raise L.SsdeError("conv(winograd 4x4, position-batched): %s" % L.load().ssde_last_error().decode())
+            fields.update(wino_ws=self.b.buf(need, name="wino_ws"), wino_ws_floats=need)
         # GroupNorm statistics that are still partials (gn_stats): the transform pass of the two-kernel form merges those of
         # its main source itself; any other reader gets the finalize launch in front
         if aux is not None:
@@ -752,10 +786,11 @@ class Lowering:
         a.flags = L.wgrad_route_flags()
         return bool(L.load().ssde_wgrad_wants_winograd4(C.byref(a)))
 
-    def wino_ok(self, h, w, c_out, c_in):
+    def wino_ok(self, h, w, c_out, c_in, aux=False):
         """Which 3x3 / stride 1 kernel a layer gets: 0 = direct, 2 = Winograd F(2x2,3x3), 4 = F(4x4,3x3) in one fused kernel
         (conv_wino4.hip), 6 = F(4x4,3x3) as a transform pass + the register-fed matrix kernel (conv_wino4r.hip; _wino4_two_kernels
-        decides between 4 and 6).
+        decides between 4 and 6), 8 = F(4x4,3x3) as position-batched GEMMs on the 4x4 maps (conv_wino4p.hip).  aux: the layer
+        also has a fused 1x1 source.
         Winograd pays when the matrix pipe is the bound: enough channels to fill the 64-cout tile, and enough workgroups
         to cover the 256 CUs (F(2x2,3x3): 64 tiles x 64 couts per workgroup -- measured x1.2-1.5 over the direct kernel
         from 8x8 up at batch 256, x0.5 at 4x4 where only 64 workgroups exist).  F(4x4,3x3) does 1.78x less matrix work
@@ -770,6 +805,13 @@ class Lowering:
         mode = os.environ.get("SSDE_WINOGRAD", "1")
         if mode == "0":
             return 0
+        # 8 = the 4x4 maps, one F(4x4,3x3) tile per image: transform pass + 36 position-batched GEMMs + output pass
+        # (conv_wino4p.hip), whose parallelism comes from the transform positions rather than from the tiles.  Not where the
+        # layer also has a fused 1x1 source (aux: the Conv_2 skip of a residual block): the direct kernel runs it as more of the
+        # same reduction, the Winograd forms as a second launch, and at batch 256 that 1x1 GEMM alone (0.058 ms for 512 -> 256)
+        # costs more than the position-batched form saves (direct 0.079 ms against 0.044 + 0.058, tools/op_times.py)
+        if mode == "1" and h == 4 and w == 4 and not aux and c_in % 32 == 0 and c_out % 64 == 0 and self.n >= W4P_MIN_BATCH:
+            return 8
         legal2 = h % 2 == 0 and w % 2 == 0 and h >= 8 and w >= 8 and c_out >= 32 and c_in >= 8 and c_in % 8 == 0
         legal4 = h % 4 == 0 and w % 4 == 0 and h >= 8 and w >= 8 and c_out >= 32 and c_in >= 8 and c_in % 4 == 0
         four = lambda: 6 if self._wino4_two_kernels(h, w, c_out, c_in) else 4  # noqa: E731
@@ -1055,7 +1097,7 @@ class UNetEngine:
             skip_t, skip_c, skip_t2, skip_c2 = t, c, t2, c2
         h1 = b.buf(n, hh, ww, cout, name="res_h1")
         wino0 = low.wino_ok(hh, ww, cout, main0["c0"] + main0["c1"])
-        wino1 = low.wino_ok(hh, ww, cout, cout)
+        wino1 = low.wino_ok(hh, ww, cout, cout, aux=hasattr(m, "Conv_2"))
         low.conv(h1, hh, ww, cout, main=main0, w_main=self._w3(m.Conv_0, wino=wino0), h_in=hh, w_in=ww, bias=self._bias(m.Conv_0),
                  chan_add=chan_add, chan_add_ld=ld, wino=wino0, stats=True)
         gn1 = low.gn_stats(h1, cout, hh * ww, m.GroupNorm_1)

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import pack_conv_weight, pack_matrix, pack_wino_weight, pack_wino4_weight, pack_wino4r_weight
+from .engine import pack_conv_weight, pack_matrix, pack_wino_weight, pack_wino4_weight, pack_wino4r_weight, pack_wino4p_weight
 
 
 def _stream():
@@ -71,7 +71,7 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
             h_out, w_out = out_hw
         _fill_src(a.main, x, x2, pro, gn)
         packer = {L.TILE_WINOGRAD: pack_wino_weight, L.TILE_WINOGRAD4: pack_wino4_weight,
-                  L.TILE_WINOGRAD4R: pack_wino4r_weight}.get(tile, pack_conv_weight)
+                  L.TILE_WINOGRAD4R: pack_wino4r_weight, L.TILE_WINOGRAD4P: pack_wino4p_weight}.get(tile, pack_conv_weight)
         wp = packer(weight.to(x.device)); keep.append(wp)
         if tile == L.TILE_WINOGRAD4R:      # the two-kernel form needs the transformed-input buffer
             wv = torch.empty(36 * n * (h_in // 4) * (w_in // 4) * (x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)), device=x.device)
@@ -94,6 +94,11 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
         a.chan_add, a.chan_add_ld = _p(chan_add), chan_add.shape[-1]
     a.resid, a.out_scale, a.dst = _p(resid), scale, _p(dst)
     a.flags = L.conv_route_flags() if flags is None else flags
+    if tile == L.TILE_WINOGRAD4P:          # the position-batched form's workspace
+        need = int(L.load().ssde_conv_ws_floats(C.byref(a)))
+        L.check(min(need, 0), "ssde_conv_ws_floats")
+        ws = torch.empty(need, device=dev); keep.append(ws)
+        a.wino_ws, a.wino_ws_floats = _p(ws), need
     L.check(L.load().ssde_conv2d(C.byref(a), _stream()), "ssde_conv2d")
     return dst
 
