@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 11  /* 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 12  /* 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
@@ -82,7 +82,7 @@ typedef struct ssde_conv_args {
   int32_t h_out, w_out, c_out;
   int32_t ksize;         /* 0 or 3                                         */
   int32_t stride;        /* 1 or 2                                         */
-  int32_t pad;           /* zero padding of main (applied after prologue)  */
+  int32_t pad;           /* zero padding of main on every side (applied after prologue); see pad_end */
   int32_t tile;          /* SSDE_TILE_*; 0 = let the library choose        */
   const float* bias;     /* [c_out] or NULL                                */
   const float* chan_add; /* [N, chan_add_ld] per-(sample, channel) addend (Dense_0(act(temb))) or NULL */
@@ -115,7 +115,11 @@ typedef struct ssde_conv_args {
   const float* gn_in_part1;   /* main.c1 > 0 */
   int32_t gn_in_slices0, gn_in_slices1;
   float gn_in_eps;
-  int32_t _pad_gn_in;
+  /* ABI 12 -- zero rows / columns AFTER the last input row / column of main, on top of `pad` (0 or 1): the padded input is
+   * (pad + h_in + pad + pad_end) x (pad + w_in + pad + pad_end).  DDPM's Downsample pads one row and one column at the bottom /
+   * right only before its 3x3 / stride 2 / pad 0 convolution (models/layers.py:608-611).  Direct kernel only (conv_mfma.hip):
+   * naming a Winograd tile with pad_end != 0 is SSDE_EINVAL, and SSDE_TILE_AUTO never routes such a launch to conv_small.hip. */
+  int32_t pad_end;
   /* ABI 11 -- SSDE_TILE_WINOGRAD4P only, REQUIRED there: the launch's workspace, the transformed input V[pos][(c0+c1)/4][t][4]
    * (wino_v's layout, 36 * N*H*W/16 * (c0+c1) floats) followed by the products of every reduction share,
    * [shares][36][N*H*W/16][roundup(c_out, 64)].  ssde_conv_ws_floats(args) returns what the library's choice of shares needs;
@@ -341,6 +345,9 @@ typedef struct ssde_wgrad_args {
   const float* v_pre;      /* optional (ABI 6): the transformed input the FORWARD launch of this layer left behind
                             * (ssde_conv_args.wino_v, same src and prologue); taken only when ssde_wgrad_wants_winograd4()
                             * is true for these arguments -- the input-transform pass of the weight gradient is then skipped */
+  int32_t pad_end;         /* ABI 12: as ssde_conv_args.pad_end of the forward launch (0 or 1; ksize 3, direct kernel only: the
+                            * Winograd weight-gradient routes decline such a launch) */
+  int32_t _pad0;
 } ssde_wgrad_args;
 
 enum { SSDE_WGRADF_DIRECT = 1u,        /* never a Winograd weight-gradient kernel */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SSDE_LIB_PATH: developer switch for A/B timing of kernel variants built by _build.build_variant (tools/ab_bench.sh)
 LIB_PATH = os.environ.get("SSDE_LIB_PATH") or os.path.join(_HERE, "libssde_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_SILU = 0, 1, 2, 3
 TILE_AUTO, TILE_256x64, TILE_128x64, TILE_64x64, TILE_256x32, TILE_WINOGRAD, TILE_WINOGRAD4 = 0, 1, 2, 3, 4, 5, 6
@@ -49,7 +49,7 @@ class ConvArgs(C.Structure):
                 ("bias", _fp), ("chan_add", _fp), ("chan_add_ld", C.c_int32), ("resid_post", C.c_int32),
                 ("resid", _fp), ("out_scale", C.c_float), ("flags", C.c_uint32), ("dst", _fp), ("gn_part", _fp), ("wino_v", _fp),
                 ("gn_in_part0", _fp), ("gn_in_part1", _fp), ("gn_in_slices0", C.c_int32), ("gn_in_slices1", C.c_int32),
-                ("gn_in_eps", C.c_float), ("_pad_gn_in", C.c_int32), ("wino_ws", _fp), ("wino_ws_floats", C.c_int64)]
+                ("gn_in_eps", C.c_float), ("pad_end", C.c_int32), ("wino_ws", _fp), ("wino_ws_floats", C.c_int64)]
 
 
 class GnStatsArgs(C.Structure):
@@ -165,7 +165,8 @@ class WgradArgs(C.Structure):
                 ("n", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("h_out", C.c_int32), ("w_out", C.c_int32),
                 ("c_out", C.c_int32), ("ksize", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
                 ("cin_store", C.c_int32), ("transpose_out", C.c_int32), ("splits", C.c_int32), ("scale", C.c_float),
-                ("flags", C.c_uint32), ("dw", _fp), ("scratch", _fp), ("scratch_floats", C.c_int64), ("v_pre", _fp)]
+                ("flags", C.c_uint32), ("dw", _fp), ("scratch", _fp), ("scratch_floats", C.c_int64), ("v_pre", _fp),
+                ("pad_end", C.c_int32), ("_pad0", C.c_int32)]
 
 
 class ColsumArgs(C.Structure):

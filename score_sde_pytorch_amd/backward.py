@@ -146,7 +146,7 @@ def flat_params_of(model, device):
 
 
 class TrainEngine(E.UNetEngine):
-    """Forward (train mode) + backward program of NCSNpp at a fixed (batch, H, W)."""
+    """Forward (train mode) + backward program of NCSNpp / DDPM at a fixed (batch, H, W)."""
 
     def __init__(self, model, batch, height, width, device, vp_score=False, input_grad=False, dropout=True,
                  param_grads=True):
@@ -367,9 +367,9 @@ class TrainEngine(E.UNetEngine):
         b, low, n = self.b, self.low, f["n"]
         ho, wo = f["h_out"], f["w_out"]
         if ksize == 3:
-            h_in, w_in, stride, pad = f["h_in"], f["w_in"], f["stride"], f["pad"]
+            h_in, w_in, stride, pad, pad_end = f["h_in"], f["w_in"], f["stride"], f["pad"], f.get("pad_end", 0)
         else:
-            h_in, w_in, stride, pad = ho, wo, 1, 0
+            h_in, w_in, stride, pad, pad_end = ho, wo, 1, 0, 0
         meta = self.weights.meta[id(wpacked)]
         ctot = src["c0"] + src["c1"]
         parts = meta["parts"] if self.param_grads else []
@@ -380,7 +380,7 @@ class TrainEngine(E.UNetEngine):
         for part in parts:
             flops = 2.0 * n * ho * wo * ksize * ksize * meta["cin_store"] * part["rows"]
             fields = dict(src=src, g=g, g_ld=g_ld, g_off=part["row0"], n=n, h_in=h_in, w_in=w_in, h_out=ho, w_out=wo,
-                          c_out=part["rows"], ksize=ksize, stride=stride, pad=pad, cin_store=meta["cin_store"],
+                          c_out=part["rows"], ksize=ksize, stride=stride, pad=pad, pad_end=pad_end, cin_store=meta["cin_store"],
                           transpose_out=int(part["transpose"]), splits=0, scale=float(scale),
                           dw=part["view"] if part.get("view") is not None else self.flat.grad_view(part["param"]),
                           scratch=None, scratch_floats=0,
@@ -410,6 +410,7 @@ class TrainEngine(E.UNetEngine):
                          resid_post=1, scale=scale, wino=wino)
             else:
                 # transposed strided conv = zero-insertion (upfirdn, up=2, 1x1 kernel) + stride-1 conv with pad 2, cropped
+                # (an end-padded forward, pad_end: the gradient of the padded row / column falls outside the crop to h_in x w_in)
                 assert stride == 2 and pad == 0
                 gz, hz, wz = low.upfirdn(gsrc, g_ld, ho, wo, np.ones((1, 1), np.float32), up=2, pad=(0, 0), name="g_zero_ins")
                 low.conv(dst, h_in, w_in, ctot, main=_src(gz, g_ld), w_main=wd, h_in=hz, w_in=wz, stride=1, pad=2,
@@ -427,6 +428,7 @@ class TrainEngine(E.UNetEngine):
         for k in ("g_ld", "g_off", "n", "h_in", "w_in", "h_out", "w_out", "c_out", "ksize", "stride", "pad", "cin_store",
                   "transpose_out"):
             setattr(a, k, fields[k])
+        a.pad_end = fields.get("pad_end", 0)
         s = fields["src"]
         a.src.c0, a.src.c1, a.src.pro_mode, a.src.gn_groups = s["c0"], s["c1"], s["pro_mode"], s["gn_groups"]
         a.flags = fields.get("flags", L.wgrad_route_flags())

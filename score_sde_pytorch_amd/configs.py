@@ -95,6 +95,27 @@ _PRESETS = {
     }],
 }
 
+# The configs/vp/ddpm/* set: the DDPM U-Net (model.name='ddpm', models/ddpm.py) under the discrete or continuous VP SDE.
+_DDPM = {
+    "training": dict(sde="vpsde", continuous=False, reduce_mean=True),
+    "sampling": dict(predictor="ancestral_sampling", corrector="none"),
+    "data": dict(centered=True),
+    "model": dict(name="ddpm", scale_by_sigma=False, ema_rate=0.9999, num_res_blocks=2, resamp_with_conv=True, conditional=True),
+}
+_DDPM_256 = [_LSUN, _DDPM, {"model": dict(num_scales=1000, ch_mult=(1, 1, 2, 2, 4, 4)), "optim": dict(lr=2e-5)}]
+_PRESETS.update({
+    # configs/vp/ddpm/cifar10.py
+    "vp/ddpm/cifar10": [_DDPM],
+    # configs/vp/ddpm/cifar10_continuous.py
+    "vp/ddpm/cifar10_continuous": [_DDPM, {"training": dict(continuous=True), "sampling": dict(predictor="euler_maruyama")}],
+    # configs/vp/ddpm/cifar10_unconditional.py
+    "vp/ddpm/cifar10_unconditional": [_DDPM, {"model": dict(conditional=False)}],
+    # configs/vp/ddpm/church.py, bedroom.py, celebahq.py: one architecture, three data sets
+    "vp/ddpm/church": _DDPM_256 + [{"data": dict(category="church_outdoor")}],
+    "vp/ddpm/bedroom": _DDPM_256 + [{"data": dict(category="bedroom")}],
+    "vp/ddpm/celebahq": _DDPM_256 + [{"data": dict(dataset="CelebAHQ", image_size=256)}],
+})
+
 
 def get_config(name, **model_overrides):
     """Return a fresh ConfigDict for a named BASELINE experiment; keyword args override `config.model`."""

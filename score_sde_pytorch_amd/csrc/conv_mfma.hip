@@ -427,9 +427,15 @@ int make_plan(const ssde_conv_args* a, ConvPlan* pl) {
     if (int rc = src_check(a->main, "main")) return rc;
     SSDE_REQUIRE(a->w_main, "conv: w_main missing");
     SSDE_REQUIRE(a->stride == 1 || a->stride == 2, "conv: stride must be 1 or 2");
-    // the output may be a top-left crop of the full convolution result (used by strided input-gradients)
-    SSDE_REQUIRE((a->h_in + 2 * a->pad - 3) / a->stride + 1 >= a->h_out && (a->w_in + 2 * a->pad - 3) / a->stride + 1 >= a->w_out,
-                 "conv: output %dx%d larger than input %dx%d stride %d pad %d allows", a->h_out, a->w_out, a->h_in, a->w_in, a->stride, a->pad);
+    SSDE_REQUIRE(a->pad_end == 0 || a->pad_end == 1, "conv: pad_end must be 0 or 1 (got %d)", a->pad_end);
+    // the output may be a top-left crop of the full convolution result (used by strided input-gradients).  pad_end: zero rows /
+    // columns behind the last input row / column -- the staging plan of conv_phase reads every halo pixel at or beyond
+    // (Hin, Win) as zero already, so the kernel needs nothing but this bound: no halo pixel it touches lies further out than
+    // pad + pad_end behind the map
+    SSDE_REQUIRE((a->h_in + 2 * a->pad + a->pad_end - 3) / a->stride + 1 >= a->h_out &&
+                 (a->w_in + 2 * a->pad + a->pad_end - 3) / a->stride + 1 >= a->w_out,
+                 "conv: output %dx%d larger than input %dx%d stride %d pad %d pad_end %d allows", a->h_out, a->w_out, a->h_in, a->w_in,
+                 a->stride, a->pad, a->pad_end);
   }
   if (pl->has1) {
     if (int rc = src_check(a->aux, "aux")) return rc;
@@ -570,7 +576,16 @@ static ssde_wino_launcher wino_launcher(int tile) {
   }
 }
 
+// The Winograd kernels tile the output of a 3x3 / stride 1 / pad 1 convolution and know no end padding: a launch that names
+// one of their tiles with pad_end != 0 is refused here, before any of their launchers or plan queries sees it.
+static int wino_pad_end_ok(const ssde_conv_args* a) {
+  SSDE_REQUIRE(!a || a->pad_end == 0 || wino_launcher(a->tile) == nullptr,
+               "conv: pad_end %d with Winograd tile %d (end padding runs on the direct kernel only)", a->pad_end, a->tile);
+  return SSDE_OK;
+}
+
 extern "C" int ssde_conv2d(const ssde_conv_args* a, void* stream) {
+  if (int rc = wino_pad_end_ok(a)) return rc;
   if (a && a->gn_in_part0 && !ssde_wino4_xform_merges_gn(a)) {
     // the statistics of main are still partials and this route has no kernel that merges them for itself: the finalize launch
     // of ABI 3-9, issued here in front of the kernel
@@ -613,6 +628,7 @@ extern "C" int ssde_conv2d(const ssde_conv_args* a, void* stream) {
 
 extern "C" int ssde_conv_gn_slices(const ssde_conv_args* a) {
   if (!a || a->c_out % 4 != 0) return 0;
+  if (wino_pad_end_ok(a)) return 0;
   ssde_conv_args q = *a;
   q.gn_part = nullptr;
   if (ssde_wino_launcher fn = wino_launcher(q.tile)) {
@@ -634,11 +650,13 @@ extern "C" int ssde_conv_gn_slices(const ssde_conv_args* a) {
 }
 
 extern "C" int64_t ssde_conv_ws_floats(const ssde_conv_args* a) {
+  if (int rc = wino_pad_end_ok(a)) return rc;
   if (a && a->tile == SSDE_TILE_WINOGRAD4P) return ssde_conv_wino4p_ws_floats(a);
   return 0;
 }
 
 extern "C" int ssde_conv_lds_bytes(const ssde_conv_args* a) {
+  if (int rc = wino_pad_end_ok(a)) return rc;
   if (ssde_wino_launcher fn = a ? wino_launcher(a->tile) : nullptr) {
     int lds = 0;
     if (int rc = fn(a, nullptr, &lds)) return rc;

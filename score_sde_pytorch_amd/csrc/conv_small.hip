@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_small_cout_kernel(const Smal
 bool ssde_conv_small_wants(const ssde_conv_args* a) {
   if (!a || (a->flags & SSDE_CONVF_NO_SMALL_COUT) || a->tile != SSDE_TILE_AUTO) return false;
   const int ctot = a->main.c0 + a->main.c1;
-  return a->ksize == 3 && a->stride == 1 && a->pad == 1 && a->aux.p0 == nullptr && a->main.p0 && a->c_out >= 1 && a->c_out <= 4 &&
+  return a->ksize == 3 && a->stride == 1 && a->pad == 1 && a->pad_end == 0 && a->aux.p0 == nullptr && a->main.p0 && a->c_out >= 1 && a->c_out <= 4 &&
          a->h_in == a->h_out && a->w_in == a->w_out && ctot >= 8 && ctot % 8 == 0 && a->main.c0 % 4 == 0 && a->gn_part == nullptr;
 }
 

@@ -438,9 +438,15 @@ int make_plan(const ssde_wgrad_args* a, WgPlan* pl) {
   SSDE_REQUIRE(a->g_ld % 4 == 0 && a->g_off % 4 == 0 && a->g_off + a->c_out <= a->g_ld + 3, "wgrad: bad g columns");
   SSDE_REQUIRE(a->n > 0 && a->h_out > 0 && a->w_out > 0 && a->c_out > 0, "wgrad: bad shape");
   SSDE_REQUIRE(!a->transpose_out || a->ksize == 1, "wgrad: transpose_out needs ksize 1");
-  if (a->ksize == 1) SSDE_REQUIRE(a->h_in == a->h_out && a->w_in == a->w_out && a->stride == 1 && a->pad == 0, "wgrad: 1x1 geometry");
-  else SSDE_REQUIRE((a->h_in + 2 * a->pad - 3) / a->stride + 1 >= a->h_out && (a->w_in + 2 * a->pad - 3) / a->stride + 1 >= a->w_out,
-                    "wgrad: output larger than the convolution produces");
+  if (a->ksize == 1) SSDE_REQUIRE(a->h_in == a->h_out && a->w_in == a->w_out && a->stride == 1 && a->pad == 0 && a->pad_end == 0, "wgrad: 1x1 geometry");
+  else {
+    // pad_end (ABI 12): zero rows / columns behind the last input row / column; the halo staging of wgrad_kernel reads every
+    // pixel at or beyond (Hin, Win) as zero already, so this bound is all the end padding needs
+    SSDE_REQUIRE(a->pad_end == 0 || a->pad_end == 1, "wgrad: pad_end must be 0 or 1 (got %d)", a->pad_end);
+    SSDE_REQUIRE((a->h_in + 2 * a->pad + a->pad_end - 3) / a->stride + 1 >= a->h_out &&
+                 (a->w_in + 2 * a->pad + a->pad_end - 3) / a->stride + 1 >= a->w_out,
+                 "wgrad: output larger than the convolution produces");
+  }
   if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU)
     SSDE_REQUIRE(s.gn_groups > 0 && Ctot % s.gn_groups == 0 && (Ctot / s.gn_groups) % 4 == 0, "wgrad: GroupNorm channels-per-group %% 4");
   WgParams& p = pl->p;

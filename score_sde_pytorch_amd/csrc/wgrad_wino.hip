@@ -353,7 +353,7 @@ bool winograd_enabled(const ssde_wgrad_args* a) { return !(a->flags & SSDE_WGRAD
 
 // ssde_conv_wgrad / ssde_wgrad_scratch_floats (wgrad.hip) route eligible launches here.
 bool ssde_wgrad_wino_wants(const ssde_wgrad_args* a) {
-  if (!winograd_enabled(a) || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->transpose_out) return false;
+  if (!winograd_enabled(a) || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->pad_end != 0 || a->transpose_out) return false;
   if (a->h_in != a->h_out || a->w_in != a->w_out || a->h_out % 4 != 0 || a->w_out % 8 != 0) return false;
   const ssde_src& s = a->src;
   const int Ctot = s.c0 + s.c1;

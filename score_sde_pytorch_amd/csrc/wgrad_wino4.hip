@@ -527,7 +527,7 @@ int64_t scratch_floats(const W4Params& p) {
 // ssde_conv_wgrad / ssde_wgrad_scratch_floats (wgrad.hip) route eligible launches here, before wgrad_wino.hip
 bool ssde_wgrad_wino4_wants(const ssde_wgrad_args* a) {
   const int m = mode(a);
-  if ((m != 4 && m != 44) || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->transpose_out) return false;
+  if ((m != 4 && m != 44) || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->pad_end != 0 || a->transpose_out) return false;
   if (a->h_in != a->h_out || a->w_in != a->w_out || a->h_out % 4 != 0 || a->w_out % 4 != 0 || a->h_out < 8 || a->w_out < 8) return false;
   const ssde_src& s = a->src;
   const int Ctot = s.c0 + s.c1;

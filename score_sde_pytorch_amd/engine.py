@@ -1,4 +1,4 @@
-"""Lowers an NCSNpp module to a static program of HIP kernels (libssde_hip.so) and runs it.
+"""Lowers an NCSNpp or DDPM module to a static program of HIP kernels (libssde_hip.so) and runs it.
 
 The reference walks ~60 nn.Modules per forward and issues ~900 eager kernels
 (models/ncsnpp.py:232-381).  Here the walk happens ONCE per
@@ -646,6 +646,7 @@ class Lowering:
         a.w_aux = dummy if sub["w_aux"] is not None else None
         for k in ("n", "h_in", "w_in", "h_out", "w_out", "c_out", "ksize", "stride", "pad", "tile"):
             setattr(a, k, sub[k])
+        a.pad_end = sub.get("pad_end", 0)
         a.dst = dummy
         a.flags = sub.get("flags", L.conv_route_flags())
         return a
@@ -699,13 +700,15 @@ class Lowering:
 
     def conv(self, dst, h_out, w_out, c_out, main=None, w_main=None, h_in=0, w_in=0, stride=1, pad=1,
              aux=None, w_aux=None, bias=None, chan_add=None, chan_add_ld=0, resid=None, scale=1.0, tile=L.TILE_AUTO,
-             resid_post=0, wino=False, stats=False):
+             resid_post=0, wino=False, stats=False, pad_end=0):
         """wino (2 / True, 4, 6 or 8): w_main is Winograd-packed (see wino_ok); a fused 1x1 source then runs as a second launch.
+        pad_end: zero rows / columns after the last input row / column on top of pad (the one-sided F.pad(x, (0, 1, 0, 1)) of
+        DDPM's Downsample, models/layers.py:608-611); direct kernel only.
         stats=True: dst feeds a GroupNorm later -- when the launch plan allows it (ssde_conv_gn_slices) the epilogue
         also writes the tensor's partial statistics and gn_stats() turns into a finalize of a few thousand floats."""
         split_tmp = None
         if wino:
-            assert main is not None and stride == 1 and pad == 1 and (h_in, w_in) == (h_out, w_out)
+            assert main is not None and stride == 1 and pad == 1 and pad_end == 0 and (h_in, w_in) == (h_out, w_out)
             tile = {8: L.TILE_WINOGRAD4P, 6: L.TILE_WINOGRAD4R, 4: L.TILE_WINOGRAD4}.get(wino, L.TILE_WINOGRAD)
             if aux is not None:
                 split_tmp = self.b.buf(self.n, h_out, w_out, c_out, name="wino_tmp")
@@ -718,7 +721,7 @@ class Lowering:
         fields = dict(
             main=main if main is not None else _NOSRC, aux=aux if aux is not None else _NOSRC,
             w_main=w_main, w_aux=w_aux, n=self.n, h_in=h_in, w_in=w_in, h_out=h_out, w_out=w_out, c_out=c_out,
-            ksize=3 if main is not None else 0, stride=stride, pad=pad, tile=tile, bias=bias, chan_add=chan_add,
+            ksize=3 if main is not None else 0, stride=stride, pad=pad, pad_end=pad_end, tile=tile, bias=bias, chan_add=chan_add,
             chan_add_ld=chan_add_ld, resid_post=resid_post, resid=resid, out_scale=float(scale), dst=dst, gn_part=None,
             wino_v=None, _split_tmp=split_tmp)
         if wino in (4, 6):
@@ -782,6 +785,7 @@ class Lowering:
         a.g_ld, a.g_off = f["c_out"], meta["parts"][0]["row0"]
         a.n, a.h_in, a.w_in, a.h_out, a.w_out = f["n"], f["h_in"], f["w_in"], f["h_out"], f["w_out"]
         a.c_out, a.ksize, a.stride, a.pad = meta["parts"][0]["rows"], 3, f["stride"], f["pad"]
+        a.pad_end = f.get("pad_end", 0)
         a.cin_store, a.transpose_out = meta["cin_store"], 0
         a.flags = L.wgrad_route_flags()
         return bool(L.load().ssde_wgrad_wants_winograd4(C.byref(a)))
@@ -862,7 +866,7 @@ class Lowering:
 
 # --------------------------------------------------------------------------- the U-Net engine
 class UNetEngine:
-    """Static program for NCSNpp.forward at a fixed (batch, H, W)."""
+    """Static program for NCSNpp.forward / DDPM.forward at a fixed (batch, H, W)."""
 
     def __init__(self, model, batch, height, width, device, vp_score=False, train=False, input_grad=False,
                  finalize=True):
@@ -899,6 +903,7 @@ class UNetEngine:
             self.drop_seed = torch.zeros(1, dtype=torch.int32, device=device)
             self.b.tensor(self.drop_seed)
         self._n_res = 0
+        self._emb = self._tproj = None
         self._lower()
         if finalize:
             self.program = self.b.finalize()
@@ -911,12 +916,28 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ lowering
     def _lower(self):
+        """The conditioning chain and the input boundary are shared; the body between them and the output boundary is the
+        model family's own (`model.family`: NCSN++ / DDPM++ or DDPM)."""
+        idx = self._lower_cond()
+        body = {"ncsnpp": self._lower_ncsnpp, "ddpm": self._lower_ddpm}[getattr(self.model, "family", "ncsnpp")]
+        o, hh, ww = body(idx)
+        mode = 2 if self.vp_score else (1 if self.cfg.model.scale_by_sigma else 0)
+        vec = self.std if mode == 2 else (self.sig if mode == 1 else None)
+        self.b.add(L.OP_TO_NCHW, dict(src=o, dst=self.out, n=self.n, c=self.channels, h=hh, w=ww, c_src=4, mode=mode, v=vec))
+
+    def _lower_cond(self):
+        """Time embedding, the two Linear layers and every Dense_0 projection (ncsnpp.py:236-257, ddpm.py:113-122); returns the
+        index of the first module behind them.  An unconditional model (ddpm.py:121-122: temb = None) emits nothing."""
         model, b, low, n = self.model, self.b, self.low, self.n
         mods = list(model.all_modules)
         nf = model.nf
         idx = 0
-        skip_scale = INV_SQRT2 if model.skip_rescale else 1.0
-        fir, fk = model.fir, model.fir_kernel
+        if not model.conditional and getattr(model, "family", "ncsnpp") == "ddpm":
+            self._cond_specs = 0
+            # no op reads the noise level, so the storage planner never meets `cond`: it keeps a block of its own for the callers
+            # that write it whatever the model (load_inputs, the samplers' label fill, the loss head)
+            self.cond.tensor = torch.zeros((n + 1023) // 1024 * 1024, dtype=torch.float32, device=self.device)
+            return idx
 
         # ---- time embedding (ncsnpp.py:236-257)
         if model.embedding_type == "fourier":
@@ -958,20 +979,42 @@ class UNetEngine:
             self._tproj = b.buf(n, off, name="tproj", persistent=True)
             low.conv(self._tproj, 1, 1, off, aux=_src(temb, 4 * nf, pro=L.PRO_SILU), w_aux=wd, bias=bd)
         self._cond_specs = len(b.specs)            # the leading specs that read nothing but the noise level
+        return idx
 
-        # ---- input boundary: NCHW -> NHWC (C padded to 4), 2x-1 for un-centred data (ncsnpp.py:259-261)
+    def _lower_input(self, conv_in):
+        """Input boundary: NCHW -> NHWC (C padded to 4), 2x-1 for un-centred data, and the first 3x3 convolution
+        (ncsnpp.py:259-267, ddpm.py:124-132)."""
+        b, n, nf = self.b, self.n, self.model.nf
         H, W = self.h, self.w
         cpad = 4
         x0 = b.buf(n, H, W, cpad, name="x_nhwc")
         self._x0 = x0
         a, sh = (1.0, 0.0) if self.cfg.data.centered else (2.0, -1.0)
         b.add(L.OP_TO_NHWC, dict(src=self.x_in, dst=x0, n=n, c=self.channels, h=H, w=W, c_pad=cpad, a=a, b=sh))
-        pyr, pyr_c = (x0, cpad) if model.progressive_input != "none" else (None, 0)
-
-        conv_in = mods[idx]; idx += 1
         h = b.buf(n, H, W, nf, name="h0")
-        low.conv(h, H, W, nf, main=_src(x0, cpad), w_main=self._w3(conv_in, cin_pad=cpad), h_in=H, w_in=W,
-                 bias=self._bias(conv_in), stats=True)
+        self.low.conv(h, H, W, nf, main=_src(x0, cpad), w_main=self._w3(conv_in, cin_pad=cpad), h_in=H, w_in=W,
+                      bias=self._bias(conv_in), stats=True)
+        return h
+
+    def _lower_head(self, gn_m, conv_m, h, cur_c, hh, ww):
+        """act(GroupNorm(h)) -> 3x3 convolution onto the image channels, padded to 4 (ncsnpp.py:368-375, ddpm.py:168-170)."""
+        gn = self.low.gn_stats(h, cur_c, hh * ww, gn_m)
+        o = self.b.buf(self.n, hh, ww, 4, name="head")
+        self.low.conv(o, hh, ww, 4, main=_src(h, cur_c, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
+                      h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=4))
+        return o
+
+    def _lower_ncsnpp(self, idx):
+        model, b, low, n = self.model, self.b, self.low, self.n
+        mods = list(model.all_modules)
+        nf = model.nf
+        skip_scale = INV_SQRT2 if model.skip_rescale else 1.0
+        fir, fk = model.fir, model.fir_kernel
+        H, W = self.h, self.w
+        cpad = 4
+        h = self._lower_input(mods[idx]); idx += 1
+        x0 = self._x0
+        pyr, pyr_c = (x0, cpad) if model.progressive_input != "none" else (None, 0)
         hs = [(h, nf, H, W)]
         cur_c = nf
 
@@ -1051,14 +1094,78 @@ class UNetEngine:
             o = pyramid
         else:
             gn_m, conv_m = mods[idx], mods[idx + 1]; idx += 2
-            gn = low.gn_stats(h, cur_c, hh * ww, gn_m)
-            o = b.buf(n, hh, ww, 4, name="head")
-            low.conv(o, hh, ww, 4, main=_src(h, cur_c, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
-                     h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=4))
+            o = self._lower_head(gn_m, conv_m, h, cur_c, hh, ww)
         assert idx == len(mods), (idx, len(mods))
-        mode = 2 if self.vp_score else (1 if self.cfg.model.scale_by_sigma else 0)
-        vec = self.std if mode == 2 else (self.sig if mode == 1 else None)
-        b.add(L.OP_TO_NCHW, dict(src=o, dst=self.out, n=n, c=self.channels, h=hh, w=ww, c_src=4, mode=mode, v=vec))
+        return o, hh, ww
+
+    def _lower_ddpm(self, idx):
+        """The DDPM U-Net (models/ddpm.py:131-170): ResnetBlockDDPM / AttnBlock through the shared _res / _attn, Downsample as ONE
+        end-padded stride-2 launch, Upsample as the nearest box resampler followed by a plain 3x3 convolution."""
+        model, b, low, n = self.model, self.b, self.low, self.n
+        mods = list(model.all_modules)
+        nf = model.nf
+        H, W = self.h, self.w
+        h = self._lower_input(mods[idx]); idx += 1
+        hs = [(h, nf, H, W)]
+        cur_c, hh, ww = nf, H, W
+
+        def is_attn(res):
+            return res in model.attn_resolutions
+
+        # ---- encoder (ddpm.py:134-145)
+        for lvl in range(model.num_resolutions):
+            for _ in range(model.num_res_blocks):
+                t, c, hh, ww = hs[-1]
+                h, cur_c = self._res(mods[idx], t, c, hh, ww); idx += 1
+                if is_attn(ww):
+                    h = self._attn(mods[idx], h, cur_c, hh, ww); idx += 1
+                hs.append((h, cur_c, hh, ww))
+            if lvl != model.num_resolutions - 1:
+                down = mods[idx]; idx += 1
+                t, c, hh, ww = hs[-1]
+                if down.with_conv:
+                    # F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 / no padding (layers.py:608-611): the zero row and column are the
+                    # launch's pad_end, never a tensor
+                    ho, wo = hh // 2, ww // 2
+                    h = b.buf(n, ho, wo, c, name="down")
+                    low.conv(h, ho, wo, c, main=_src(t, c), w_main=self._w3(down.Conv_0), h_in=hh, w_in=ww, stride=2, pad=0,
+                             pad_end=1, bias=self._bias(down.Conv_0), stats=True)
+                else:
+                    # F.avg_pool2d(x, 2, 2) (layers.py:613): the 2x2 box
+                    h, ho, wo = low.upfirdn(_src(t, c), c, hh, ww, fir_taps([1, 1]), down=2, pad=(0, 0), name="down")
+                hs.append((h, c, ho, wo))
+
+        # ---- bottleneck (ddpm.py:147-153)
+        t, c, hh, ww = hs[-1]
+        h, cur_c = self._res(mods[idx], t, c, hh, ww); idx += 1
+        h = self._attn(mods[idx], h, cur_c, hh, ww); idx += 1
+        h, cur_c = self._res(mods[idx], h, cur_c, hh, ww); idx += 1
+
+        # ---- decoder (ddpm.py:156-165)
+        for lvl in reversed(range(model.num_resolutions)):
+            for _ in range(model.num_res_blocks + 1):
+                st, sc, sh_, sw_ = hs.pop()
+                assert (sh_, sw_) == (hh, ww)
+                h, cur_c = self._res(mods[idx], h, cur_c, hh, ww, t2=st, c2=sc); idx += 1
+            if is_attn(ww):
+                h = self._attn(mods[idx], h, cur_c, hh, ww); idx += 1
+            if lvl != 0:
+                up = mods[idx]; idx += 1
+                # F.interpolate(nearest, x2) (layers.py:593): the box resampler with gain 4
+                h, hh, ww = low.upfirdn(_src(h, cur_c), cur_c, hh, ww, fir_taps([1, 1], gain=4.0), up=2, pad=(1, 0), name="up")
+                if up.with_conv:
+                    hn = b.buf(n, hh, ww, cur_c, name="up_conv")
+                    wino = low.wino_ok(hh, ww, cur_c, cur_c)
+                    low.conv(hn, hh, ww, cur_c, main=_src(h, cur_c), w_main=self._w3(up.Conv_0, wino=wino), h_in=hh, w_in=ww,
+                             bias=self._bias(up.Conv_0), wino=wino, stats=True)
+                    h = hn
+        assert not hs
+
+        # ---- head (ddpm.py:168-170)
+        gn_m, conv_m = mods[idx], mods[idx + 1]; idx += 2
+        o = self._lower_head(gn_m, conv_m, h, cur_c, hh, ww)
+        assert idx == len(mods), (idx, len(mods))
+        return o, hh, ww
 
     # -- packed parameter helpers
     def _w3(self, m, cin_pad=None, cout_pad=None, wino=False):
@@ -1070,7 +1177,20 @@ class UNetEngine:
     def _bias(self, m, pad_to=None):
         return self.weights.vector([m.bias], pad_to=pad_to)
 
-    # -- ResnetBlockBigGANpp (layerspp.py:242-274)
+    # -- ResnetBlockBigGANpp (layerspp.py:242-274) and ResnetBlockDDPM (layers.py:645-662).  What differs between them is read off
+    #    the module: the group count from its GroupNorm modules, the 1/sqrt(2) rescale (skip_rescale), the resampling (up / down,
+    #    BigGAN only) and the kind of shortcut (Conv_2: a 1x1 convolution, [out, in]; NIN_0: [in, out])
+    def _shortcut(self, m):
+        """(packed 1x1 weight, bias parameter) of the block's projection shortcut, or (None, None) for the identity."""
+        conv, nin = getattr(m, "Conv_2", None), getattr(m, "NIN_0", None)
+        if conv is not None:
+            if tuple(conv.weight.shape[2:]) != (1, 1):
+                raise NotImplementedError("ResnetBlockDDPM(conv_shortcut=True): the 3x3 shortcut is not lowered (DDPM never sets it)")
+            return self._w1(conv), conv.bias
+        if nin is not None:
+            return self.weights.matrix([(nin.W, True)]), nin.b
+        return None, None
+
     def _res(self, m, t, c, hh, ww, t2=None, c2=0):
         b, low, n = self.b, self.low, self.n
         cin, cout = c + c2, m.out_ch
@@ -1078,7 +1198,7 @@ class UNetEngine:
         scale = INV_SQRT2 if m.skip_rescale else 1.0
         gn0 = low.gn_stats(t, c, hh * ww, m.GroupNorm_0, t2, c2)
         chan_add, ld = None, 0
-        if hasattr(m, "Dense_0"):
+        if hasattr(m, "Dense_0") and self._tproj is not None:
             chan_add, ld = (self._tproj, self._tproj_off[id(m.Dense_0)]), self._tproj_ld
         if m.up or m.down:
             assert t2 is None
@@ -1097,7 +1217,8 @@ class UNetEngine:
             skip_t, skip_c, skip_t2, skip_c2 = t, c, t2, c2
         h1 = b.buf(n, hh, ww, cout, name="res_h1")
         wino0 = low.wino_ok(hh, ww, cout, main0["c0"] + main0["c1"])
-        wino1 = low.wino_ok(hh, ww, cout, cout, aux=hasattr(m, "Conv_2"))
+        w_short, b_short = self._shortcut(m)
+        wino1 = low.wino_ok(hh, ww, cout, cout, aux=w_short is not None)
         low.conv(h1, hh, ww, cout, main=main0, w_main=self._w3(m.Conv_0, wino=wino0), h_in=hh, w_in=ww, bias=self._bias(m.Conv_0),
                  chan_add=chan_add, chan_add_ld=ld, wino=wino0, stats=True)
         gn1 = low.gn_stats(h1, cout, hh * ww, m.GroupNorm_1)
@@ -1105,10 +1226,10 @@ class UNetEngine:
         self._n_res += 1
         drop = (float(m.dropout), self.drop_seed, 0x9E3779B1 * self._n_res) if self.drop_seed is not None else None
         main1 = _src(h1, cout, pro=L.PRO_GN_SILU, gn=gn1, drop=drop)
-        if hasattr(m, "Conv_2"):
-            bsum = self.weights.vector([m.Conv_1.bias, m.Conv_2.bias], mode="sum")
+        if w_short is not None:
+            bsum = self.weights.vector([m.Conv_1.bias, b_short], mode="sum")
             low.conv(out, hh, ww, cout, main=main1, w_main=self._w3(m.Conv_1, wino=wino1), h_in=hh, w_in=ww,
-                     aux=_src(skip_t, skip_c, skip_t2, skip_c2), w_aux=self._w1(m.Conv_2), bias=bsum, scale=scale, wino=wino1,
+                     aux=_src(skip_t, skip_c, skip_t2, skip_c2), w_aux=w_short, bias=bsum, scale=scale, wino=wino1,
                      stats=True)
         else:
             assert skip_t2 is None
@@ -1116,7 +1237,7 @@ class UNetEngine:
                      bias=self._bias(m.Conv_1), resid=skip_t, scale=scale, wino=wino1, stats=True)
         return out, cout
 
-    # -- AttnBlockpp (layerspp.py:75-91)
+    # -- AttnBlockpp (layerspp.py:75-91) and AttnBlock (layers.py:568-581: the same without the rescale)
     def _attn(self, m, t, c, hh, ww):
         b, low, n = self.b, self.low, self.n
         gn = low.gn_stats(t, c, hh * ww, m.GroupNorm_0)

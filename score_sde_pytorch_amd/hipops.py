@@ -56,8 +56,9 @@ def groupnorm_stats(x, groups, eps=1e-6, x2=None, slices=1):
 
 def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_NONE, gn=None,
            aux=None, aux2=None, aux_weight=None, aux_pro=L.PRO_NONE, aux_gn=None,
-           chan_add=None, resid=None, scale=1.0, tile=L.TILE_AUTO, out_hw=None, flags=None):
+           chan_add=None, resid=None, scale=1.0, tile=L.TILE_AUTO, out_hw=None, flags=None, pad_end=0):
     """k x k (k=3) conv of NHWC `x` (weight OIHW) plus optional 1x1 conv of `aux` (weight [Cout, Cin]).
+    pad_end: zero rows / columns behind the last row / column of x on top of pad (F.pad(x, (0, 1, 0, 1)) for pad_end=1).
     flags: SSDE_CONVF_* routing switches (None: the A/B variables of the environment, _lib.conv_route_flags)."""
     _need_cuda(x, aux, resid)
     a = L.ConvArgs()
@@ -65,8 +66,8 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
     if x is not None:
         n, h_in, w_in = x.shape[0], x.shape[1], x.shape[2]
         c_out = weight.shape[0]
-        h_out = (h_in + 2 * pad - 3) // stride + 1
-        w_out = (w_in + 2 * pad - 3) // stride + 1
+        h_out = (h_in + 2 * pad + pad_end - 3) // stride + 1
+        w_out = (w_in + 2 * pad + pad_end - 3) // stride + 1
         if out_hw is not None:      # top-left crop of the full result (transposed strided convolutions)
             h_out, w_out = out_hw
         _fill_src(a.main, x, x2, pro, gn)
@@ -78,6 +79,7 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
             keep.append(wv)
             a.wino_v = _p(wv)
         a.w_main, a.ksize, a.stride, a.pad, a.h_in, a.w_in = _p(wp), 3, stride, pad, h_in, w_in
+        a.pad_end = pad_end
     else:
         n, h_out, w_out = aux.shape[0], aux.shape[1], aux.shape[2]
         c_out = aux_weight.shape[0]
@@ -199,7 +201,7 @@ def set_dropout(s, p, seed_t, salt):
 
 
 def conv_wgrad(x, g, ksize, dw, stride=1, pad=1, x2=None, pro=L.PRO_NONE, gn=None, g_off=0, c_out=None, cin_store=None,
-               transpose_out=False, scale=1.0, splits=0, dropout=None, flags=None):
+               transpose_out=False, scale=1.0, splits=0, dropout=None, flags=None, pad_end=0):
     """dw += scale * sum_pixels g[:, g_off:g_off+c_out]^T pro(x)[shifted]; x, g NHWC; dw in the reference layout.
     flags: SSDE_WGRADF_* (None: the A/B variables of the environment, _lib.wgrad_route_flags)."""
     _need_cuda(x, g, dw)
@@ -212,7 +214,7 @@ def conv_wgrad(x, g, ksize, dw, stride=1, pad=1, x2=None, pro=L.PRO_NONE, gn=Non
     a.n, a.h_in, a.w_in, a.h_out, a.w_out = x.shape[0], x.shape[1], x.shape[2], g.shape[1], g.shape[2]
     a.c_out = c_out if c_out is not None else g.shape[-1] - g_off
     ctot = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
-    a.ksize, a.stride, a.pad = ksize, stride, pad
+    a.ksize, a.stride, a.pad, a.pad_end = ksize, stride, pad, pad_end
     a.cin_store = cin_store if cin_store is not None else ctot
     a.transpose_out, a.splits, a.scale, a.dw = int(transpose_out), splits, scale, _p(dw)
     a.splits = 0

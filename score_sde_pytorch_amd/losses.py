@@ -529,10 +529,10 @@ def _on_device(t):
 
 
 def _fused_candidate(state, loss_fn, optimize_fn, train):
-    from .models.ncsnpp import NCSNpp
+    from .models.ncsnpp import HipUNet
     from .models.ema import ExponentialMovingAverage
     model = state['model']
-    if not isinstance(model, NCSNpp) or getattr(loss_fn, "ssde_spec", None) is None:
+    if not isinstance(model, HipUNet) or getattr(loss_fn, "ssde_spec", None) is None:
         return False
     if not _on_device(next(model.parameters())):
         return False

@@ -161,8 +161,45 @@ class Combine(nn.Module):
 
 
 # --------------------------------------------------------------------------- the network
+class HipUNet(nn.Module):
+    """What every score network of this package shares: the parameters live in `all_modules` under the reference's names, and
+    `forward` is a program of HIP kernels lowered once per (device, batch, H, W) by engine.UNetEngine -- `family` names the
+    lowering.  Samplers, losses and the ODE code accept any subclass."""
+    family = "ncsnpp"
+
+    def flat_param_groups(self):
+        """Parameters the HIP programs use as one concatenated operand (backward.FlatParams stores them back to back)."""
+        if not self.conditional:
+            return []
+        dense = [m.Dense_0 for m in self.all_modules if getattr(m, "kind", "") == "res" and hasattr(m, "Dense_0")]
+        return [[d.weight for d in dense], [d.bias for d in dense]] if dense else []
+
+    # ------------------------------------------------------------------ forward
+    def _engine_for(self, x):
+        from .. import engine as _engine
+        key = (x.device.index, x.shape[0], x.shape[2], x.shape[3])
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = _engine.UNetEngine(self, batch=x.shape[0], height=x.shape[2], width=x.shape[3], device=x.device)
+            self._engines[key] = eng
+        return eng
+
+    def forward(self, x, time_cond):
+        name = type(self).__name__
+        if not x.is_cuda:
+            raise RuntimeError("score_sde_pytorch_amd.%s runs on MI355X through libssde_hip.so only; "
+                               "got a %s tensor (there is no CPU fallback)" % (name, x.device.type))
+        if x.dtype != torch.float32 or x.dim() != 4:
+            raise TypeError("%s.forward expects a float32 [B, C, H, W] tensor" % name)
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if needs_grad:
+            from .. import autograd as _autograd
+            return _autograd.unet_apply(self, x, time_cond)
+        return self._engine_for(x).forward(x, time_cond)
+
+
 @utils.register_model(name="ncsnpp")
-class NCSNpp(nn.Module):
+class NCSNpp(HipUNet):
     """NCSN++ (fir=True, progressive input/output) and DDPM++ (fir=False) score network."""
 
     def __init__(self, config):
@@ -276,30 +313,3 @@ class NCSNpp(nn.Module):
 
         self.all_modules = nn.ModuleList(mods)
         self._engines = {}
-
-    def flat_param_groups(self):
-        """Parameters the HIP programs use as one concatenated operand (backward.FlatParams stores them back to back)."""
-        dense = [m.Dense_0 for m in self.all_modules if getattr(m, "kind", "") == "res" and hasattr(m, "Dense_0")]
-        return [[d.weight for d in dense], [d.bias for d in dense]] if dense else []
-
-    # ------------------------------------------------------------------ forward
-    def _engine_for(self, x):
-        from .. import engine as _engine
-        key = (x.device.index, x.shape[0], x.shape[2], x.shape[3])
-        eng = self._engines.get(key)
-        if eng is None:
-            eng = _engine.UNetEngine(self, batch=x.shape[0], height=x.shape[2], width=x.shape[3], device=x.device)
-            self._engines[key] = eng
-        return eng
-
-    def forward(self, x, time_cond):
-        if not x.is_cuda:
-            raise RuntimeError("score_sde_pytorch_amd.NCSNpp runs on MI355X through libssde_hip.so only; "
-                               "got a %s tensor (there is no CPU fallback)" % x.device.type)
-        if x.dtype != torch.float32 or x.dim() != 4:
-            raise TypeError("NCSNpp.forward expects a float32 [B, C, H, W] tensor")
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if needs_grad:
-            from .. import autograd as _autograd
-            return _autograd.unet_apply(self, x, time_cond)
-        return self._engine_for(x).forward(x, time_cond)

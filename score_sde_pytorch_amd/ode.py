@@ -296,8 +296,8 @@ class _FusedRhs:
     @staticmethod
     def applies(model, sde, x):
         from . import sde_lib
-        from .models.ncsnpp import NCSNpp
-        if not isinstance(model, NCSNpp) or not x.is_cuda or type(sde) not in (sde_lib.VESDE, sde_lib.VPSDE, sde_lib.subVPSDE):
+        from .models.ncsnpp import HipUNet
+        if not isinstance(model, HipUNet) or not x.is_cuda or type(sde) not in (sde_lib.VESDE, sde_lib.VPSDE, sde_lib.subVPSDE):
             return False
         return not (type(sde) is not sde_lib.VESDE and model.config.model.scale_by_sigma)
 

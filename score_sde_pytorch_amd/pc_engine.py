@@ -36,8 +36,8 @@ from . import sde_lib
 def plan_fused(sde, predictor, corrector, model, continuous, x, probability_flow=False):
     """Return a lowering plan when (sde, predictor, corrector, model) are all stock, else None."""
     from . import sampling as S
-    from .models.ncsnpp import NCSNpp
-    if not isinstance(model, NCSNpp) or not x.is_cuda:
+    from .models.ncsnpp import HipUNet
+    if not isinstance(model, HipUNet) or not x.is_cuda:
         return None
     if type(sde) not in (sde_lib.VESDE, sde_lib.VPSDE, sde_lib.subVPSDE):
         return None

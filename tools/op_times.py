@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-launch HIP-event times of ONE U-Net evaluation of the CIFAR-10 NCSN++ sampler at batch 256 (GPU only): every op of the
+"""Per-launch HIP-event times of ONE U-Net evaluation (default: the CIFAR-10 NCSN++ sampler at batch 256; any preset of either model family) (GPU only): every op of the
 lowered program with its kind, shape and ms, the list sorted by time, and the sums per (kind, shape).  What to look at next."""
 import collections
 import os
@@ -43,11 +43,11 @@ def describe(op):
 if __name__ == "__main__":
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     dev = torch.device("cuda")
-    name = sys.argv[2] if len(sys.argv) > 2 else "ve/cifar10_ncsnpp_continuous"      # e.g. 16 ve/ffhq_256_ncsnpp_continuous
+    name = sys.argv[2] if len(sys.argv) > 2 else "ve/cifar10_ncsnpp_continuous"      # e.g. 16 ve/ffhq_256_ncsnpp_continuous, 256 vp/ddpm/cifar10
     cfg = _util.cfgs.get_config(name)
     R = cfg.data.image_size
     torch.manual_seed(0)
-    model = mutils.get_model("ncsnpp")(cfg)
+    model = mutils.get_model(cfg.model.name)(cfg)
     _util.load_seeded(model, seed=1)
     model = model.to(dev).eval()
     eng = E.UNetEngine(model, B, R, R, dev)
