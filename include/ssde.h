@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 12  /* 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 13  /* 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
@@ -182,8 +182,44 @@ typedef struct ssde_gn_stats_args {
   int32_t n, hw, groups; float eps;
   float* mean; float* rstd;      /* [N, G] */
   float* scratch;                /* >= N*slices*G*2 floats when slices > 1 */
-  int32_t slices; int32_t _pad0;
+  int32_t slices;
+  uint32_t flags;                /* SSDE_GNSTATF_* (ABI 13; the former pad slot, 0 = the library's own choice) */
 } ssde_gn_stats_args;
+/* Channels-per-group that are a multiple of 4 run on the quad kernel (a 16-byte lane lies inside one group); any other width
+ * >= 4 -- nn.GroupNorm(min(C // 4, 32), C) on 192 = 128 + 64 channels gives 32 groups of 6, layerspp.py:219,231 -- on the
+ * any-width kernel, where a lane's four channels may belong to two groups and a group may straddle p0 / p1.  Both sum relative
+ * to the group's first element, in the same fixed order. */
+enum { SSDE_GNSTATF_ANY_WIDTH = 1u };  /* take the any-width kernel also for a multiple of 4 (tests: the same bits as the quad kernel) */
+
+/* ---- GroupNorm as a launch of its own (ABI 13) -----------------------------------------------------------------
+ * dst = drop(act(gamma * (x - mean) * rstd + beta)) for src.pro_mode SSDE_PRO_GN / SSDE_PRO_GN_SILU: the prologue the
+ * consumers otherwise apply while they stage the source, materialised as ONE contiguous NHWC tensor of c0 + c1 channels.
+ * For the group widths the fused prologues refuse ((c0 + c1) / gn_groups % 4 != 0); any width >= 1 is accepted.
+ * HBM-bound: one read of the (possibly concatenated) source, one write, 16-byte lanes; the group of a channel comes from
+ * a per-workgroup table.  Dropout: element e = pixel * (c0 + c1) + channel of the virtual concat tensor, as in ssde_src.
+ * SSDE_PRO_NONE is accepted too: the plain copy of a concatenation whose boundary c0 the matrix kernels refuse (c0 % 32 != 0:
+ * 16 + 16 channels at the top level of the nf = 16 networks); its adjoint is two ssde_prologue_bwd slices of the gradient. */
+typedef struct ssde_gn_apply_args {
+  ssde_src src;                  /* p0 / p1, statistics, affine, dropout identity; c0 % 4 == 0, c1 % 4 == 0 */
+  int32_t n, hw;
+  float* dst;                    /* [N, hw, c0 + c1] */
+} ssde_gn_apply_args;
+
+/* Its adjoint: with u = xhat * gamma + beta, du = dy * mask * silu'(u), dxh = du * gamma,
+ *   dgamma = sum du * xhat, dbeta = sum du, dx = rstd * (dxh - mean_g(dxh) - xhat * mean_g(dxh * xhat)).
+ * Three launches (channel sums per (image, pixel slice); their fixed-order merge into sums / dgamma / dbeta; apply): no float
+ * atomics, bit-reproducible.  SiLU' and the dropout mask are recomputed. */
+typedef struct ssde_gn_apply_bwd_args {
+  ssde_src src;                  /* as in the forward */
+  const float* dy;               /* [N * hw, c0 + c1] gradient of dst */
+  int32_t n, hw;
+  float* sums;                   /* [N, G, 2] scratch: mean_g(dxh), mean_g(dxh * xhat) */
+  float* dgamma; float* dbeta;   /* [c0 + c1] written (not accumulated), or both NULL */
+  float* scratch;                /* >= N * slices * (c0 + c1) * 2 floats */
+  int32_t slices; int32_t _pad0; /* pixel slices per image of the first launch (>= 1) */
+  float* g0; float* g1;          /* gradients of p0 [N * hw, c0] and p1 [N * hw, c1] (NULL: that source needs no gradient) */
+  int32_t acc0, acc1;            /* 1: g += ..., 0: g = ... */
+} ssde_gn_apply_bwd_args;
 
 /* GroupNorm statistics from the PRODUCERS' partials instead of a pass over the tensor: merges, in a fixed order,
  * the (mean, M2, count) triples the convolution epilogues wrote (ssde_conv_args.gn_part) over the slices and the
@@ -538,6 +574,8 @@ typedef struct ssde_hutch_div_args {
 int ssde_conv2d(const ssde_conv_args* a, void* stream);
 int ssde_groupnorm_stats(const ssde_gn_stats_args* a, void* stream);
 int ssde_gn_finalize(const ssde_gn_finalize_args* a, void* stream);
+int ssde_gn_apply(const ssde_gn_apply_args* a, void* stream);
+int ssde_gn_apply_bwd(const ssde_gn_apply_bwd_args* a, void* stream);
 /* slices per image of the GroupNorm partials this launch would write (plan only, no device access); 0 = this
  * launch cannot produce them (a workgroup tile would span several images, or c_out % 4 != 0) */
 int ssde_conv_gn_slices(const ssde_conv_args* a);
@@ -593,7 +631,8 @@ enum {
   SSDE_OP_WGRAD = 15, SSDE_OP_COLSUM = 16, SSDE_OP_GN_BWD_REDUCE = 17, SSDE_OP_PROLOGUE_BWD = 18,
   SSDE_OP_ATTN_BWD = 19, SSDE_OP_PERTURB = 20, SSDE_OP_DSM_LOSS = 21, SSDE_OP_SUMSQ_FLAT = 22,
   SSDE_OP_ADAM = 23, SSDE_OP_MEMSET = 24, SSDE_OP_AXPY = 25, SSDE_OP_PACK = 26, SSDE_OP_PROJECT = 27,
-  SSDE_OP_GN_FINALIZE = 28, SSDE_OP_PF_DRIFT = 29, SSDE_OP_HUTCH_DIV = 30, SSDE_OP_COLSUM_FINISH = 31, SSDE_OP_GN_BWD_FINISH = 32
+  SSDE_OP_GN_FINALIZE = 28, SSDE_OP_PF_DRIFT = 29, SSDE_OP_HUTCH_DIV = 30, SSDE_OP_COLSUM_FINISH = 31, SSDE_OP_GN_BWD_FINISH = 32,
+  SSDE_OP_GN_APPLY = 33, SSDE_OP_GN_APPLY_BWD = 34
 };
 typedef struct ssde_op {
   int32_t kind; int32_t flops_class;   /* flops_class: free tag echoed by timing */
@@ -609,6 +648,7 @@ typedef struct ssde_op {
     ssde_pack_args pack; ssde_project_args project; ssde_gn_finalize_args gn_fin;
     ssde_pf_drift_args pf_drift; ssde_hutch_div_args hutch_div;
     ssde_colsum_finish_args colsum_fin; ssde_gn_bwd_finish_args gn_bwd_fin;
+    ssde_gn_apply_args gn_apply; ssde_gn_apply_bwd_args gn_apply_bwd;
   } u;
 } ssde_op;
 

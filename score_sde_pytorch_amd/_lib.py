@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SSDE_LIB_PATH: developer switch for A/B timing of kernel variants built by _build.build_variant (tools/ab_bench.sh)
 LIB_PATH = os.environ.get("SSDE_LIB_PATH") or os.path.join(_HERE, "libssde_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_SILU = 0, 1, 2, 3
 TILE_AUTO, TILE_256x64, TILE_128x64, TILE_64x64, TILE_256x32, TILE_WINOGRAD, TILE_WINOGRAD4 = 0, 1, 2, 3, 4, 5, 6
@@ -25,7 +25,8 @@ GNBWDF_THREE_KERNELS, GNBWDF_DEFER_PARAMS = 1, 2
 (OP_CONV, OP_GN_STATS, OP_UPFIRDN, OP_ATTN, OP_EMBED, OP_TO_NHWC, OP_TO_NCHW, OP_BIAS_ACT, OP_SUMSQ,
  OP_RANDN, OP_LANGEVIN, OP_PREDICTOR, OP_FILL, OP_STEP_INC, OP_WGRAD, OP_COLSUM, OP_GN_BWD_REDUCE, OP_PROLOGUE_BWD,
  OP_ATTN_BWD, OP_PERTURB, OP_DSM_LOSS, OP_SUMSQ_FLAT, OP_ADAM, OP_MEMSET, OP_AXPY, OP_PACK, OP_PROJECT,
- OP_GN_FINALIZE, OP_PF_DRIFT, OP_HUTCH_DIV, OP_COLSUM_FINISH, OP_GN_BWD_FINISH) = range(1, 33)
+ OP_GN_FINALIZE, OP_PF_DRIFT, OP_HUTCH_DIV, OP_COLSUM_FINISH, OP_GN_BWD_FINISH, OP_GN_APPLY, OP_GN_APPLY_BWD) = range(1, 35)
+GNSTATF_ANY_WIDTH = 1
 FINISH_JOBS = 16
 COLSUMF_DEFER = 1
 PACK_CONV3, PACK_WINO3, PACK_MATRIX, PACK_VECTOR, PACK_WINO4, PACK_WINO4R, PACK_WINO4P = 1, 2, 3, 4, 5, 6, 7
@@ -55,7 +56,17 @@ class ConvArgs(C.Structure):
 class GnStatsArgs(C.Structure):
     _fields_ = [("p0", _fp), ("p1", _fp), ("c0", C.c_int32), ("c1", C.c_int32),
                 ("n", C.c_int32), ("hw", C.c_int32), ("groups", C.c_int32), ("eps", C.c_float),
-                ("mean", _fp), ("rstd", _fp), ("scratch", _fp), ("slices", C.c_int32), ("_pad0", C.c_int32)]
+                ("mean", _fp), ("rstd", _fp), ("scratch", _fp), ("slices", C.c_int32), ("flags", C.c_uint32)]
+
+
+class GnApplyArgs(C.Structure):
+    _fields_ = [("src", Src), ("n", C.c_int32), ("hw", C.c_int32), ("dst", _fp)]
+
+
+class GnApplyBwdArgs(C.Structure):
+    _fields_ = [("src", Src), ("dy", _fp), ("n", C.c_int32), ("hw", C.c_int32), ("sums", _fp), ("dgamma", _fp), ("dbeta", _fp),
+                ("scratch", _fp), ("slices", C.c_int32), ("_pad0", C.c_int32), ("g0", _fp), ("g1", _fp),
+                ("acc0", C.c_int32), ("acc1", C.c_int32)]
 
 
 class RkCombineArgs(C.Structure):
@@ -254,7 +265,8 @@ class _OpUnion(C.Union):
                 ("attn_bwd", AttnBwdArgs), ("perturb", PerturbArgs), ("dsm_loss", DsmLossArgs),
                 ("sumsq_flat", SumsqFlatArgs), ("adam", AdamArgs), ("memset", MemsetArgs), ("axpy", AxpyArgs),
                 ("pack", PackArgs), ("project", ProjectArgs), ("gn_fin", GnFinalizeArgs),
-                ("pf_drift", PfDriftArgs), ("hutch_div", HutchDivArgs), ("colsum_fin", ColsumFinishArgs), ("gn_bwd_fin", GnBwdFinishArgs)]
+                ("pf_drift", PfDriftArgs), ("hutch_div", HutchDivArgs), ("colsum_fin", ColsumFinishArgs), ("gn_bwd_fin", GnBwdFinishArgs),
+                ("gn_apply", GnApplyArgs), ("gn_apply_bwd", GnApplyBwdArgs)]
 
 
 class Op(C.Structure):
@@ -268,7 +280,7 @@ _UNION_FIELD = {OP_CONV: "conv", OP_GN_STATS: "gn", OP_UPFIRDN: "fir", OP_ATTN: 
                 OP_PROLOGUE_BWD: "pro_bwd", OP_ATTN_BWD: "attn_bwd", OP_PERTURB: "perturb", OP_DSM_LOSS: "dsm_loss",
                 OP_SUMSQ_FLAT: "sumsq_flat", OP_ADAM: "adam", OP_MEMSET: "memset", OP_AXPY: "axpy", OP_PACK: "pack", OP_PROJECT: "project",
                 OP_GN_FINALIZE: "gn_fin", OP_PF_DRIFT: "pf_drift", OP_HUTCH_DIV: "hutch_div", OP_COLSUM_FINISH: "colsum_fin",
-                OP_GN_BWD_FINISH: "gn_bwd_fin"}
+                OP_GN_BWD_FINISH: "gn_bwd_fin", OP_GN_APPLY: "gn_apply", OP_GN_APPLY_BWD: "gn_apply_bwd"}
 
 EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attention", "ssde_embed", "ssde_to_nhwc",
            "ssde_to_nchw", "ssde_fused_bias_act", "ssde_sumsq", "ssde_randn", "ssde_langevin_update",
@@ -278,6 +290,7 @@ EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attent
            "ssde_conv_wgrad", "ssde_colsum", "ssde_gn_bwd_reduce", "ssde_prologue_bwd", "ssde_attention_bwd",
            "ssde_perturb", "ssde_dsm_loss", "ssde_sumsq_flat", "ssde_adam_clip_ema", "ssde_memset", "ssde_axpy",
            "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_conv_ws_floats", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
+           "ssde_gn_apply", "ssde_gn_apply_bwd",
            # plan-level entry points (csrc/plan.hip; argument types: plan_export.bind)
            "ssde_plan_load", "ssde_plan_load_file", "ssde_plan_destroy", "ssde_plan_info", "ssde_plan_param",
            "ssde_plan_refresh_weights", "ssde_unet_forward", "ssde_pc_reset", "ssde_pc_run", "ssde_pc_state",
@@ -372,7 +385,8 @@ def bind(lib):
                       ("ssde_axpy", AxpyArgs), ("ssde_pack_weights", PackArgs), ("ssde_project_update", ProjectArgs),
                       ("ssde_gn_finalize", GnFinalizeArgs), ("ssde_rk_combine", RkCombineArgs), ("ssde_hutch_div", HutchDivArgs), ("ssde_sample_update", SampleUpdateArgs),
                       ("ssde_rk_error_norm", RkErrorArgs), ("ssde_pf_drift", PfDriftArgs),
-                      ("ssde_colsum_finish", ColsumFinishArgs), ("ssde_gn_bwd_finish", GnBwdFinishArgs)]:
+                      ("ssde_colsum_finish", ColsumFinishArgs), ("ssde_gn_bwd_finish", GnBwdFinishArgs),
+                      ("ssde_gn_apply", GnApplyArgs), ("ssde_gn_apply_bwd", GnApplyBwdArgs)]:
         getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
     lib.ssde_conv_lds_bytes.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_conv_gn_slices.argtypes = [C.POINTER(ConvArgs)]

@@ -204,7 +204,7 @@ class TrainEngine(E.UNetEngine):
         if self.param_grads:
             b.add(L.OP_MEMSET, dict(dst=self.flat.grad, bytes=self.flat.numel * 4, value=0), FC_BWD)
         handlers = {L.OP_CONV: self._bwd_conv, L.OP_UPFIRDN: self._bwd_fir, L.OP_ATTN: self._bwd_attn,
-                    L.OP_TO_NCHW: self._bwd_to_nchw, L.OP_TO_NHWC: self._bwd_to_nhwc}
+                    L.OP_TO_NCHW: self._bwd_to_nchw, L.OP_TO_NHWC: self._bwd_to_nhwc, L.OP_GN_APPLY: self._bwd_gn_apply}
         for kind, f, _, _ in reversed(fwd):
             h = handlers.get(kind)
             if h is not None:
@@ -298,6 +298,37 @@ class TrainEngine(E.UNetEngine):
             b.add(L.OP_PROLOGUE_BWD, dict(src=src, dp=dP, dp_ld=ctot, dp_off=0, n=n, hw=hw, sums=None, scale=1.0,
                                           acc0=int(e0[1]) if e0 else 0, acc1=int(e1[1]) if e1 else 0,
                                           g0=e0[0] if e0 else None, g1=e1[0] if e1 else None), FC_BWD)
+        if e0:
+            e0[1] = True
+        if e1:
+            e1[1] = True
+
+    def _bwd_gn_apply(self, f):
+        """The adjoint of a materialised GroupNorm (engine.Lowering.src): its consumers accumulated d loss / d dst like the
+        gradient of any plain tensor; one OP_GN_APPLY_BWD turns it into dgamma / dbeta and the gradients of the (possibly
+        concatenated) sources.  Fixed-order reductions, written results: nothing is deferred."""
+        e = self._G.get(id(f["dst"]))
+        if e is None:
+            return
+        b, src, n, hw = self.b, f["src"], f["n"], f["hw"]
+        ctot = src["c0"] + src["c1"]
+        if src["pro_mode"] == L.PRO_NONE:                # a materialised concatenation: its gradient, sliced
+            self._accum(src["p0"], e[0], ctot, 0, src["c0"], n, hw, 1.0)
+            if src["p1"] is not None:
+                self._accum(src["p1"], e[0], ctot, src["c0"], src["c1"], n, hw, 1.0)
+            return
+        e0 = self._gentry(src["p0"]) if self._needs(src["p0"]) else None
+        e1 = self._gentry(src["p1"]) if self._needs(src["p1"]) else None
+        if e0 is None and e1 is None and not self.param_grads:
+            return
+        slices = max(1, min(int(math.ceil(256 / n)), hw // 64)) if hw >= 128 else 1
+        b.add(L.OP_GN_APPLY_BWD, dict(
+            src=src, dy=e[0], n=n, hw=hw, sums=b.buf(n, src["gn_groups"], 2, name="gn_apply_bwd_sums"),
+            dgamma=self.flat.grad_view(self._param_of(src["gn_gamma"])) if self.param_grads else None,
+            dbeta=self.flat.grad_view(self._param_of(src["gn_beta"])) if self.param_grads else None,
+            scratch=b.buf(n * slices * ctot * 2, name="gn_apply_bwd_scratch"), slices=slices,
+            g0=e0[0] if e0 else None, g1=e1[0] if e1 else None,
+            acc0=int(e0[1]) if e0 else 0, acc1=int(e1[1]) if e1 else 0), FC_BWD)
         if e0:
             e0[1] = True
         if e1:

@@ -95,6 +95,23 @@ _PRESETS = {
     }],
 }
 
+# The two 1024-px NCSN++ configs (configs/ve/ffhq_ncsnpp_continuous.py, configs/ve/celebahq_ncsnpp_continuous.py): nf = 16 under
+# ch_mult (1, 2, 4, 8, 16, 32, 32, 32), one block per level.  Their decoder meets 192 = 128 + 64 channels in 32 groups of 6
+# (engine.Lowering.src).
+_NCSNPP_1024 = [_LSUN, {
+    "training": dict(batch_size=8),
+    "sampling": dict(snr=0.15),
+    "eval": dict(batch_size=1024, begin_ckpt=1, end_ckpt=96),
+    "data": dict(image_size=1024),
+    "model": dict(sigma_max=1348, ema_rate=0.9999, nf=16, ch_mult=(1, 2, 4, 8, 16, 32, 32, 32), num_res_blocks=1,
+                  progressive="output_skip", progressive_input="input_skip"),
+    "optim": dict(amsgrad=False),
+}]
+_PRESETS.update({
+    "ve/ffhq_ncsnpp_continuous": _NCSNPP_1024 + [{"training": dict(reduce_mean=True), "data": dict(dataset="FFHQ")}],
+    "ve/celebahq_ncsnpp_continuous": _NCSNPP_1024 + [{"data": dict(dataset="CelebAHQ")}],
+})
+
 # The configs/vp/ddpm/* set: the DDPM U-Net (model.name='ddpm', models/ddpm.py) under the discrete or continuous VP SDE.
 _DDPM = {
     "training": dict(sde="vpsde", continuous=False, reduce_mean=True),

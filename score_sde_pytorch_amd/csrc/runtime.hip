@@ -96,6 +96,8 @@ static int run_one(const ssde_op& op, void* stream) {
     case SSDE_OP_HUTCH_DIV: return ssde_hutch_div(&op.u.hutch_div, stream);
     case SSDE_OP_COLSUM_FINISH: return ssde_colsum_finish(&op.u.colsum_fin, stream);
     case SSDE_OP_GN_BWD_FINISH: return ssde_gn_bwd_finish(&op.u.gn_bwd_fin, stream);
+    case SSDE_OP_GN_APPLY: return ssde_gn_apply(&op.u.gn_apply, stream);
+    case SSDE_OP_GN_APPLY_BWD: return ssde_gn_apply_bwd(&op.u.gn_apply_bwd, stream);
   }
   ssde_set_error("program: unknown op kind %d", op.kind);
   return SSDE_EINVAL;

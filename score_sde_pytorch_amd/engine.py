@@ -15,6 +15,10 @@ Fusions encoded in the program (per ResnetBlockBigGANpp, models/layerspp.py:242-
   Conv_1 (+Conv_2) -> conv kernel; the 1x1 skip conv is an extra K-range of the same
                       GEMM; epilogue adds the identity skip and scales by 1/sqrt(2)
   torch.cat        -> never materialised: a source is a pair of tensors
+
+A GroupNorm whose channels-per-group is no multiple of 4 (nn.GroupNorm(min(C // 4, 32), C) on 192 = 128 + 64 channels: 32 groups
+of 6 -- the 1024-px configs, layerspp.py:219,231) is NOT fused: no consumer's prologue accepts a channel quad that spans two
+groups.  It runs as launches of its own (statistics pass + ssde_gn_apply) and its consumers read a plain tensor (Lowering.src).
 """
 import ctypes as C
 import math
@@ -105,7 +109,8 @@ _STRUCT = {L.OP_CONV: L.ConvArgs, L.OP_GN_STATS: L.GnStatsArgs, L.OP_UPFIRDN: L.
            L.OP_GN_BWD_REDUCE: L.GnBwdReduceArgs, L.OP_PROLOGUE_BWD: L.PrologueBwdArgs, L.OP_ATTN_BWD: L.AttnBwdArgs,
            L.OP_PERTURB: L.PerturbArgs, L.OP_DSM_LOSS: L.DsmLossArgs, L.OP_SUMSQ_FLAT: L.SumsqFlatArgs,
            L.OP_ADAM: L.AdamArgs, L.OP_MEMSET: L.MemsetArgs, L.OP_AXPY: L.AxpyArgs, L.OP_GN_FINALIZE: L.GnFinalizeArgs,
-           L.OP_COLSUM_FINISH: L.ColsumFinishArgs, L.OP_GN_BWD_FINISH: L.GnBwdFinishArgs}
+           L.OP_COLSUM_FINISH: L.ColsumFinishArgs, L.OP_GN_BWD_FINISH: L.GnBwdFinishArgs,
+           L.OP_GN_APPLY: L.GnApplyArgs, L.OP_GN_APPLY_BWD: L.GnApplyBwdArgs}
 
 
 _ROUTE = {L.OP_CONV: L.conv_route_flags, L.OP_WGRAD: L.wgrad_route_flags, L.OP_GN_BWD_REDUCE: L.gn_bwd_route_flags,
@@ -682,7 +687,22 @@ class Lowering:
         gamma = self.w.vector([gn_module.weight])
         beta = self.w.vector([gn_module.bias])
         assert ctot == gn_module.num_channels
-        return dict(groups=groups, mean=mean, rstd=rstd, gamma=gamma, beta=beta)
+        return dict(groups=groups, mean=mean, rstd=rstd, gamma=gamma, beta=beta, narrow=(ctot // groups) % 4 != 0)
+
+    def src(self, t, c, hw, t2=None, c2=0, pro=L.PRO_NONE, gn=None, drop=None):
+        """The source descriptor of a consumer that reads pro(cat(t, t2)).  A GroupNorm of a width the fused prologues refuse
+        (gn_stats: narrow) is materialised here -- one OP_GN_APPLY launch writes drop(act(GroupNorm(x))) as one contiguous
+        tensor of c + c2 channels -- and the consumer (whichever 3x3 route, the resampler, the 1x1 GEMM, conv_small) gets a
+        plain source; so do its weight gradient and its input gradient (backward.TrainEngine._bwd_gn_apply is the adjoint).
+        The same launch materialises a concatenation whose boundary the matrix kernels refuse (c % 32 != 0: 16 + 16 channels at
+        the top level of the nf = 16 networks), with or without a GroupNorm."""
+        if not (gn is not None and gn.get("narrow")) and not (t2 is not None and c % 32 != 0):
+            return _src(t, c, t2, c2, pro=pro, gn=gn, drop=drop)
+        self._materialize_stats(gn)
+        ctot = c + c2
+        dst = self.b.buf(self.n, hw, ctot, name="gn_applied")
+        self.b.add(L.OP_GN_APPLY, dict(src=_src(t, c, t2, c2, pro=pro, gn=gn, drop=drop), n=self.n, hw=hw, dst=dst), FC_GN)
+        return _src(dst, ctot)
 
     def _materialize_stats(self, gn, fields=None):
         """The statistics of `gn` are about to be read: if they are still the producers' partials, either hand the merge to the
@@ -1000,7 +1020,7 @@ class UNetEngine:
         """act(GroupNorm(h)) -> 3x3 convolution onto the image channels, padded to 4 (ncsnpp.py:368-375, ddpm.py:168-170)."""
         gn = self.low.gn_stats(h, cur_c, hh * ww, gn_m)
         o = self.b.buf(self.n, hh, ww, 4, name="head")
-        self.low.conv(o, hh, ww, 4, main=_src(h, cur_c, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
+        self.low.conv(o, hh, ww, 4, main=self.low.src(h, cur_c, hh * ww, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
                       h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=4))
         return o
 
@@ -1081,7 +1101,7 @@ class UNetEngine:
                     up_pyr, _, _ = low.upfirdn(_src(pyramid, 4), 4, hh // 2, ww // 2, taps, up=2, pad=pd, name="pyr_up")
                 gn = low.gn_stats(h, cur_c, hh * ww, gn_m)
                 pn = b.buf(n, hh, ww, 4, name="pyramid")
-                low.conv(pn, hh, ww, 4, main=_src(h, cur_c, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
+                low.conv(pn, hh, ww, 4, main=low.src(h, cur_c, hh * ww, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
                          h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=4), resid=up_pyr)
                 pyramid = pn
             if lvl != 0:
@@ -1208,12 +1228,12 @@ class UNetEngine:
             else:
                 taps = fir_taps(m.fir_kernel) if m.fir else fir_taps([1, 1])
                 kw = dict(down=2, pad=(1, 1) if m.fir else (0, 0))
-            hr, ho, wo = low.upfirdn(_src(t, c, pro=L.PRO_GN_SILU, gn=gn0), c, hh, ww, taps, name="res_h_rs", **kw)
+            hr, ho, wo = low.upfirdn(low.src(t, c, hh * ww, pro=L.PRO_GN_SILU, gn=gn0), c, hh, ww, taps, name="res_h_rs", **kw)
             xr, _, _ = low.upfirdn(_src(t, c), c, hh, ww, taps, name="res_x_rs", **kw)
             main0, skip_t, skip_c, skip_t2, skip_c2 = _src(hr, c), xr, c, None, 0
             hh, ww = ho, wo
         else:
-            main0 = _src(t, c, t2, c2, pro=L.PRO_GN_SILU, gn=gn0)
+            main0 = low.src(t, c, hh * ww, t2, c2, pro=L.PRO_GN_SILU, gn=gn0)
             skip_t, skip_c, skip_t2, skip_c2 = t, c, t2, c2
         h1 = b.buf(n, hh, ww, cout, name="res_h1")
         wino0 = low.wino_ok(hh, ww, cout, main0["c0"] + main0["c1"])
@@ -1225,11 +1245,11 @@ class UNetEngine:
         out = b.buf(n, hh, ww, cout, name="res_out")
         self._n_res += 1
         drop = (float(m.dropout), self.drop_seed, 0x9E3779B1 * self._n_res) if self.drop_seed is not None else None
-        main1 = _src(h1, cout, pro=L.PRO_GN_SILU, gn=gn1, drop=drop)
+        main1 = low.src(h1, cout, hh * ww, pro=L.PRO_GN_SILU, gn=gn1, drop=drop)
         if w_short is not None:
             bsum = self.weights.vector([m.Conv_1.bias, b_short], mode="sum")
             low.conv(out, hh, ww, cout, main=main1, w_main=self._w3(m.Conv_1, wino=wino1), h_in=hh, w_in=ww,
-                     aux=_src(skip_t, skip_c, skip_t2, skip_c2), w_aux=w_short, bias=bsum, scale=scale, wino=wino1,
+                     aux=low.src(skip_t, skip_c, hh * ww, skip_t2, skip_c2), w_aux=w_short, bias=bsum, scale=scale, wino=wino1,
                      stats=True)
         else:
             assert skip_t2 is None
@@ -1244,7 +1264,7 @@ class UNetEngine:
         wqkv = self.weights.matrix([(m.NIN_0.W, True), (m.NIN_1.W, True), (m.NIN_2.W, True)])
         bqkv = self.weights.vector([m.NIN_0.b, m.NIN_1.b, m.NIN_2.b])
         qkv = b.buf(n, hh, ww, 3 * c, name="qkv")
-        low.conv(qkv, hh, ww, 3 * c, aux=_src(t, c, pro=L.PRO_GN, gn=gn), w_aux=wqkv, bias=bqkv)
+        low.conv(qkv, hh, ww, 3 * c, aux=low.src(t, c, hh * ww, pro=L.PRO_GN, gn=gn), w_aux=wqkv, bias=bqkv)
         ao = b.buf(n, hh, ww, c, name="attn_o")
         L_ = hh * ww
         b.add(L.OP_ATTN, dict(qkv=qkv, dst=ao, n=n, l=L_, c=c, scale=float(int(c) ** (-0.5))), FC_ATTN,

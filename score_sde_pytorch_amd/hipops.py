@@ -36,8 +36,9 @@ def _fill_src(s, t, t2=None, pro=L.PRO_NONE, gn=None):
         s.gn_groups, s.gn_mean, s.gn_rstd, s.gn_gamma, s.gn_beta = groups, _p(mean), _p(rstd), _p(gamma), _p(beta)
 
 
-def groupnorm_stats(x, groups, eps=1e-6, x2=None, slices=1):
-    """(mean, rstd) [N, G] of the channel-concat of NHWC tensors x (and x2)."""
+def groupnorm_stats(x, groups, eps=1e-6, x2=None, slices=1, any_width=False):
+    """(mean, rstd) [N, G] of the channel-concat of NHWC tensors x (and x2).  Any channels-per-group >= 4; any_width takes the
+    any-width kernel also for a multiple of 4 (SSDE_GNSTATF_ANY_WIDTH: same bits as the quad kernel)."""
     _need_cuda(x, x2)
     n = x.shape[0]
     hw = int(np.prod(x.shape[1:-1]))
@@ -50,8 +51,52 @@ def groupnorm_stats(x, groups, eps=1e-6, x2=None, slices=1):
     a.mean, a.rstd = _p(mean), _p(rstd)
     scratch = torch.empty(n * slices * groups * 2, device=x.device) if slices > 1 else None
     a.scratch, a.slices = _p(scratch), slices
+    a.flags = L.GNSTATF_ANY_WIDTH if any_width else 0
     L.check(L.load().ssde_groupnorm_stats(C.byref(a), _stream()), "ssde_groupnorm_stats")
     return mean, rstd
+
+
+def _fill_drop(s, drop):
+    """drop = (p, seed word tensor (int32 [1]), salt): the dropout identity of ssde_src"""
+    if drop is not None:
+        p, seed_t, salt = drop
+        s.drop_thresh, s.drop_scale = min(int(round(p * 2.0 ** 32)), 2 ** 32 - 1), 1.0 / (1.0 - p)
+        s.drop_seed, s.drop_salt = _p(seed_t), salt & 0xFFFFFFFF
+
+
+def groupnorm_apply(x, gn, x2=None, silu=True, drop=None):
+    """drop(act(GroupNorm(cat(x, x2)))) as one contiguous NHWC tensor (ssde_gn_apply): the launch that stands in for the
+    consumers' fused prologue where channels-per-group is no multiple of 4.  gn = (mean, rstd, gamma, beta, groups)."""
+    _need_cuda(x, x2)
+    n, hw = x.shape[0], int(np.prod(x.shape[1:-1]))
+    c = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
+    out = torch.empty(tuple(x.shape[:-1]) + (c,), device=x.device)
+    a = L.GnApplyArgs()
+    _fill_src(a.src, x, x2, L.PRO_GN_SILU if silu else L.PRO_GN, gn)
+    _fill_drop(a.src, drop)
+    a.n, a.hw, a.dst = n, hw, _p(out)
+    L.check(L.load().ssde_gn_apply(C.byref(a), _stream()), "ssde_gn_apply")
+    return out
+
+
+def groupnorm_apply_bwd(dy, x, gn, x2=None, silu=True, drop=None, slices=1, g0=None, g1=None):
+    """Adjoint of groupnorm_apply (ssde_gn_apply_bwd): returns (dx, dx2, dgamma, dbeta); g0 / g1 given = accumulate into them."""
+    _need_cuda(dy, x, x2)
+    n, hw = x.shape[0], int(np.prod(x.shape[1:-1]))
+    c = dy.shape[-1]
+    a = L.GnApplyBwdArgs()
+    _fill_src(a.src, x, x2, L.PRO_GN_SILU if silu else L.PRO_GN, gn)
+    _fill_drop(a.src, drop)
+    sums = torch.empty(n, gn[4], 2, device=x.device)
+    scratch = torch.empty(n * slices * c * 2, device=x.device)
+    dgamma, dbeta = torch.empty(c, device=x.device), torch.empty(c, device=x.device)
+    a.acc0, a.acc1 = int(g0 is not None), int(g1 is not None)
+    g0 = torch.empty_like(x) if g0 is None else g0
+    g1 = (torch.empty_like(x2) if g1 is None else g1) if x2 is not None else None
+    a.dy, a.n, a.hw, a.sums, a.dgamma, a.dbeta, a.scratch, a.slices = _p(dy), n, hw, _p(sums), _p(dgamma), _p(dbeta), _p(scratch), slices
+    a.g0, a.g1 = _p(g0), _p(g1)
+    L.check(L.load().ssde_gn_apply_bwd(C.byref(a), _stream()), "ssde_gn_apply_bwd")
+    return g0, g1, dgamma, dbeta
 
 
 def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_NONE, gn=None,

@@ -36,7 +36,11 @@ def describe(op):
         return "gn_finalize c %d+%d slices %d,%d" % (a.c0, a.c1, a.slices0, a.slices1)
     if k == L.OP_GN_STATS:
         a = op.u.gn
-        return "gn_stats c %d+%d hw %d" % (a.c0, a.c1, a.hw)
+        return "gn_stats c %d+%d hw %d (%.1f MB read)" % (a.c0, a.c1, a.hw, 4e-6 * a.n * a.hw * (a.c0 + a.c1))
+    if k == L.OP_GN_APPLY:
+        a = op.u.gn_apply
+        return "gn_apply%s c %d+%d hw %d (%.1f MB read + as much written)" % (" (copy)" if a.src.pro_mode == L.PRO_NONE else "", a.src.c0, a.src.c1,
+                                                                            a.hw, 4e-6 * a.n * a.hw * (a.src.c0 + a.src.c1))
     return KIND.get(k, str(k))
 
 
