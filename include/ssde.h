@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 13  /* 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 13  /* (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
@@ -251,16 +251,26 @@ typedef struct ssde_upfirdn_args {
 
 /* ---- single-head self-attention core ----------------------------------------
  * replaces layerspp.py:82-86: w = softmax(q.k * C^-1/2) over keys; h = w.v
- * qkv: [N, L, 3C] (q | k | v per token, output of the fused NIN_0..2 GEMM). */
+ * qkv: [N, L, 3C] (q | k | v per token, output of the fused NIN_0..2 GEMM).  C % 32 == 0.
+ * L <= 256 tokens: one 64 x L score tile per workgroup (attn_kernel / attn_x6_kernel).  256 < L <= SSDE_ATTN_L_MAX (added under ABI 13):
+ * the streaming kernel (attn_stream_kernel: key blocks of 256, online softmax, the output held in registers), C <= 512.
+ * Beyond either bound the launch is SSDE_EINVAL with a message; ssde_attention_route answers the same question without a
+ * device, so a lowering can refuse a shape before its first launch. */
+#define SSDE_ATTN_L_MAX 16384    /* 128 x 128 tokens */
 typedef struct ssde_attn_args {
   const float* qkv; float* dst;  /* dst [N, L, C] */
   int32_t n, l, c; float scale;
-  uint32_t flags;                /* SSDE_ATTNF_* (ABI 10; 0 = the fp32-MFMA kernel) */
+  uint32_t flags;                /* SSDE_ATTNF_* (ABI 10; 0 = the fp32-MFMA kernels) */
   int32_t _pad0;
 } ssde_attn_args;
-enum { SSDE_ATTNF_BF16X6 = 1u }; /* both contractions (Q K^T and P V) on the BF16 matrix pipe as exact-fp32 products of a 3-way bf16
+enum { SSDE_ATTNF_BF16X6 = 1u,   /* both contractions (Q K^T and P V) on the BF16 matrix pipe as exact-fp32 products of a 3-way bf16
                                   * split, fp32 accumulation and an fp32 softmax (attention.hip: attn_x6_kernel) -- the forward at
-                                  * L = 256 tokens and C <= 256 channels; other shapes and the backward stay on the fp32 kernels */
+                                  * L = 256 tokens and C <= 256 channels, C % 64 == 0; every other shape (L > 256 included: the flag is
+                                  * accepted there and the fp32 streaming kernel runs) and the backward stay on the fp32 kernels */
+       SSDE_ATTNF_STREAM = 2u }; /* (added under ABI 13) take the streaming forward kernel at any L (tests and same-box A/B runs; it wins over
+                                  * SSDE_ATTNF_BF16X6).  The backward has no flag field: it streams exactly when L > 256 */
+/* what ssde_attention_route returns (>= 0), the kernel a forward launch with these arguments takes */
+enum { SSDE_ATTN_ROUTE_F32 = 0, SSDE_ATTN_ROUTE_X6 = 1, SSDE_ATTN_ROUTE_STREAM = 2 };
 
 /* ---- time / noise-level embeddings -------------------------------------------
  * kind 0: GaussianFourierProjection(log(cond)) (layerspp.py:39-41, ncsnpp.py:239)
@@ -478,7 +488,7 @@ typedef struct ssde_attn_bwd_args {
   const float* o;          /* [N, L, C]  forward output */
   const float* d_o;        /* [N, L, C]  gradient of the output */
   float* dqkv;             /* [N, L, 3C] written */
-  float* stats;            /* [N, L, 4] scratch: row max, row sum, D = sum_c dO*O */
+  float* stats;            /* [N, L, 4] scratch: row max, row sum, D = sum_c dO*O (l > 256: written by a pass of its own) */
   int32_t n, l, c; float scale;
 } ssde_attn_bwd_args;
 
@@ -583,6 +593,7 @@ int ssde_conv_gn_slices(const ssde_conv_args* a);
 int64_t ssde_conv_ws_floats(const ssde_conv_args* a);
 int ssde_upfirdn2d(const ssde_upfirdn_args* a, void* stream);
 int ssde_attention(const ssde_attn_args* a, void* stream);
+int ssde_attention_route(const ssde_attn_args* a);   /* plan query (added under ABI 13): SSDE_ATTN_ROUTE_* or < 0 with ssde_last_error set; pointers are not read */
 int ssde_embed(const ssde_embed_args* a, void* stream);
 int ssde_to_nhwc(const ssde_to_nhwc_args* a, void* stream);
 int ssde_to_nchw(const ssde_to_nchw_args* a, void* stream);

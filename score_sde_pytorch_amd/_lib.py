@@ -282,7 +282,7 @@ _UNION_FIELD = {OP_CONV: "conv", OP_GN_STATS: "gn", OP_UPFIRDN: "fir", OP_ATTN: 
                 OP_GN_FINALIZE: "gn_fin", OP_PF_DRIFT: "pf_drift", OP_HUTCH_DIV: "hutch_div", OP_COLSUM_FINISH: "colsum_fin",
                 OP_GN_BWD_FINISH: "gn_bwd_fin", OP_GN_APPLY: "gn_apply", OP_GN_APPLY_BWD: "gn_apply_bwd"}
 
-EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attention", "ssde_embed", "ssde_to_nhwc",
+EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attention", "ssde_attention_route", "ssde_embed", "ssde_to_nhwc",
            "ssde_to_nchw", "ssde_fused_bias_act", "ssde_sumsq", "ssde_randn", "ssde_langevin_update",
            "ssde_predictor_update", "ssde_fill_from_table", "ssde_step_inc", "ssde_program_run",
            "ssde_program_run_timed", "ssde_graph_capture", "ssde_graph_launch", "ssde_graph_destroy",
@@ -330,13 +330,17 @@ def conv_route_flags(env=None):
     return f
 
 
-ATTNF_BF16X6 = 1
+ATTNF_BF16X6, ATTNF_STREAM = 1, 2
+ATTN_ROUTE_F32, ATTN_ROUTE_X6, ATTN_ROUTE_STREAM = 0, 1, 2
+ATTN_L_MAX = 16384
 
 
 def attn_route_flags(env=None):
-    """SSDE_MATRIX=bf16x6 also moves the attention forward onto the BF16 matrix pipe (SSDE_ATTN_X6=0 keeps the fp32 kernel: A/B runs)"""
+    """SSDE_MATRIX=bf16x6 also moves the attention forward onto the BF16 matrix pipe (SSDE_ATTN_X6=0 keeps the fp32 kernel: A/B runs);
+    SSDE_ATTN_STREAM=1 forces the streaming forward kernel at any token count (above 256 tokens the library takes it by itself)"""
     e = os.environ if env is None else env
-    return ATTNF_BF16X6 if e.get("SSDE_MATRIX", "").startswith("b") and e.get("SSDE_ATTN_X6", "1") != "0" else 0
+    x6 = ATTNF_BF16X6 if e.get("SSDE_MATRIX", "").startswith("b") and e.get("SSDE_ATTN_X6", "1") != "0" else 0
+    return x6 | (ATTNF_STREAM if e.get("SSDE_ATTN_STREAM", "0") == "1" else 0)
 
 
 def wgrad_route_flags(env=None):
@@ -389,6 +393,7 @@ def bind(lib):
                       ("ssde_gn_apply", GnApplyArgs), ("ssde_gn_apply_bwd", GnApplyBwdArgs)]:
         getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
     lib.ssde_conv_lds_bytes.argtypes = [C.POINTER(ConvArgs)]
+    lib.ssde_attention_route.argtypes = [C.POINTER(AttnArgs)]
     lib.ssde_conv_gn_slices.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_conv_ws_floats.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_conv_ws_floats.restype = C.c_int64

@@ -1,8 +1,10 @@
 // Single-head spatial self-attention core of AttnBlockpp (models/layerspp.py:82-86):
 //   w = softmax_j( sum_c q[i,c] k[j,c] * C^-1/2 ),  h[i,c] = sum_j w[i,j] v[j,c]
-// with L = H*W <= 256 tokens (attention only ever runs at 16x16 and at the 4x4
-// bottleneck) and d = C channels, and its backward (what autograd derives
-// for those three lines).  fp32 operands on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32).
+// with L = H*W tokens and d = C channels, and its backward (what autograd derives for those
+// three lines).  fp32 operands on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32).
+// L <= 256 (the 16x16 attention and the 4x4 bottleneck of every shipped config) runs
+// on the single-tile kernels described first; 256 < L <= SSDE_ATTN_L_MAX (attn_resolutions of 32
+// and more, larger bottlenecks, non-square maps) on the streaming kernels further down.
 //
 // Forward, one workgroup = 64 query rows of one image:
 //   1. S = Q K^T  (4 waves x 64 keys each), Q/K channel chunks staged in LDS
@@ -717,6 +719,380 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
   gemm_pv(Ps, Lp, base, L, C3, C, Vs, dqkv + ((size_t)n * L + k0) * C3 + C, C3, valid, scale);
 }
 
+// ---- more than 256 tokens: streaming kernels (ABI 13, added without a layout change) ---------------------------------------------------------------------------
+// The kernels above hold a whole 64 x L score tile in LDS, which is what stops them at L = 256.  The kernels below keep the
+// same tile, the same two GEMM phases and the same fragment handling, but the tile is a WINDOW of at most 256 keys (forward, dQ)
+// or 256 queries (dK / dV) that walks the other axis in a fixed order, and the output stays in the accumulator registers across
+// the windows (4 waves x 64 channels: 64 accumulator VGPRs per 256 channels).  Nothing of size L^2 reaches HBM, there are no
+// atomics, and two runs agree to the bit.
+//   forward   attn_stream_kernel<NCP>: per key block S = Q K_blk^T -> tile; online softmax (running row max m and row sum l,
+//             P_blk = exp(S - m_new) left unnormalised); O *= exp(m_old - m_new); O += P_blk V_blk; at the end O /= l, once.
+//             NCP = channel passes of 256 (1: C <= 256, 2: C <= 512) = accumulator sets held by a wave.
+//   backward  attn_stream_stats_kernel: m, l by the same online pass (no P V) and D = sum_c dO O, into stats[N, L, 4];
+//             attn_stream_bwd_q_kernel<NCP>: per key block P = exp(S - m) / l, dP = dO V_blk^T, dS = P o (dP - D), dQ += dS K_blk;
+//             attn_stream_bwd_kv_kernel: per query block P^T, dV += P^T dO_blk, dS^T, dK += dS^T Q_blk for one 256-channel pass of
+//             the outputs (blockIdx.z: at C = 512 the two passes of a key block each recompute S^T and dP^T rather than hold
+//             256 accumulator registers of dK and dV beside the 64 of the running product).
+// Rows / keys past L: gemm_nt and pv_pass clamp their addresses and zero what they fetched, the softmax reads the valid columns
+// only and zeroes the tile up to the next multiple of 32, and no row >= L is stored.
+constexpr int kKB = 256;                                    // keys (dK / dV: queries) per window
+constexpr int kStreamCMax = 512;                            // two 256-channel passes held in registers (the widest attention of a shipped config)
+constexpr int kStreamVch = 16;                              // V tokens per chunk of the streaming forward (one workgroup per CU: 290 registers)
+constexpr int kStreamLdsFloats = kQB * kLDP + kStreamVch * kLDP + kQB;   // forward / statistics: tile | V chunk | one float per row (83 KB)
+constexpr int kStreamBwdLdsFloats = kBwdLdsFloats;          // backward: tile | staging | 3 x 256 row constants
+
+// acc += Ps[64 x Lp] * Bm[rows x (cp .. cp + Cw)]: gemm_pv's main loop for one 256-channel pass, without its zeroing and its store
+template <int VCH>
+__device__ __forceinline__ void pv_pass(const float* Ps, int Lp, const float* __restrict__ Bm, int b_valid, size_t ldb, int cp, int Cw,
+                                        float* Vs, f32x16 (&acc)[2][2]) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 31, lh = lane >> 5;
+  const int cb = wave * 64;
+  constexpr int NIT = VCH / 4;
+  const int f4n = Cw >> 2;
+  int vrow[NIT], vf[NIT];
+  {
+    int row = tid / f4n, ff = tid - row * f4n;
+    const int dr = 256 / f4n, df = 256 - dr * f4n;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      vrow[it] = row; vf[it] = ff;
+      row += dr; ff += df;
+      if (ff >= f4n) { ff -= f4n; ++row; }
+    }
+  }
+  float4 rv[NIT];
+  auto load_chunk = [&](int k0) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int tok = k0 + vrow[it];
+      const float4 v = *reinterpret_cast<const float4*>(Bm + (size_t)max(min(tok, b_valid - 1), 0) * ldb + cp + vf[it] * 4);
+      rv[it] = (vrow[it] < VCH && tok < b_valid) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  load_chunk(0);
+  for (int k0 = 0; k0 < Lp; k0 += VCH) {
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+      if (vrow[it] < VCH) *reinterpret_cast<float4*>(Vs + vrow[it] * kLDP + vf[it] * 4) = rv[it];
+    __syncthreads();
+    if (k0 + VCH < Lp) load_chunk(k0 + VCH);
+    if (cb < Cw) {
+#pragma unroll
+      for (int kk = 0; kk < VCH / 8; ++kk) {
+        float4 af[2];
+        float bf[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const float4*>(Ps + (a * 32 + li) * kLDP + k0 + kk * 8 + lh * 4);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bf[b][j] = Vs[(kk * 8 + lh * 4 + j) * kLDP + cb + b * 32 + li];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].x, bf[b][0], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].y, bf[b][1], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].z, bf[b][2], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].w, bf[b][3], acc[a][b], 0, 0, 0);
+          }
+      }
+    }
+  }
+}
+
+// acc[a][b][r] *= Rs[row of (a, r)]   (Rs: one float per row of the 64-row block, in LDS)
+__device__ __forceinline__ void scale_rows(f32x16 (&acc)[2][2], const float* Rs) {
+  const int lh = (threadIdx.x & 63) >> 5;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float s = Rs[a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[a][b][r] *= s;
+    }
+}
+
+// out[row][cp + wave's 64 channels] = acc * mul for rows < out_valid, channels < C
+__device__ __forceinline__ void store_acc(const f32x16 (&acc)[2][2], float* __restrict__ out, size_t ldo, int out_valid, int cp, int C,
+                                          float mul) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int li = lane & 31, lh = lane >> 5;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int col = cp + wave * 64 + b * 32 + li;
+      if (col >= C) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (row < out_valid) out[(size_t)row * ldo + col] = acc[a][b][r] * mul;
+      }
+    }
+}
+
+// One window of the online softmax over the first Lb columns of the tile (4 lanes per row, the arithmetic of softmax_rows):
+// m_new = max(m, row max), alpha = exp(m - m_new), l = l * alpha + sum_j exp(s_j - m_new).  kWriteP: the tile becomes
+// exp(s - m_new) with columns Lb .. roundup(Lb, 32) - 1 zeroed.  Returns alpha (the same value in the 4 lanes of a row).
+template <bool kWriteP>
+__device__ __forceinline__ float online_softmax(float* Ps, int Lb, float& m_run, float& l_run) {
+  const int tid = threadIdx.x;
+  const int row = tid >> 2, sub = tid & 3;
+  float* prow = Ps + row * kLDP;
+  float m = -INFINITY;
+  for (int j = sub; j < Lb; j += 4) m = fmaxf(m, prow[j]);
+  m = fmaxf(m, __shfl_xor(m, 1, 64));
+  m = fmaxf(m, __shfl_xor(m, 2, 64));
+  m = fmaxf(m, m_run);
+  const float alpha = __expf(m_run - m);                    // first window: exp(-inf) = 0 against l = 0 and O = 0
+  float sum = 0.f;
+  for (int j = sub; j < Lb; j += 4) {
+    const float e = __expf(prow[j] - m);
+    if (kWriteP) prow[j] = e;
+    sum += e;
+  }
+  sum += __shfl_xor(sum, 1, 64);
+  sum += __shfl_xor(sum, 2, 64);
+  if (kWriteP) {
+    const int Lp = (Lb + 31) & ~31;
+    for (int j = Lb + sub; j < Lp; j += 4) prow[j] = 0.f;
+  }
+  l_run = l_run * alpha + sum;
+  m_run = m;
+  return alpha;
+}
+
+template <int NCP>
+__global__ __launch_bounds__(256) void attn_stream_kernel(const float* __restrict__ qkv, float* __restrict__ dst,
+                                                          int N, int L, int C, float scale) {
+  SSDE_LDS(smem);
+  float* Qs = smem;                       // [64][36]    (inside the tile: dead once S sits in the accumulators)
+  float* Ks = smem + kQB * kLDC;          // [256][36]
+  float* Ps = smem;                       // [64][260]
+  float* Vs = smem + kQB * kLDP;          // [kStreamVch][260]
+  float* Rs = Vs + kStreamVch * kLDP;     // [64] per-row factor
+  const int n = blockIdx.y, q0 = blockIdx.x * kQB, tid = threadIdx.x;
+  const int C3 = 3 * C;
+  const float* base = qkv + (size_t)n * L * C3;
+  const int valid = L - q0;
+
+  f32x16 o[NCP][2][2];
+#pragma unroll
+  for (int p = 0; p < NCP; ++p) zero_acc(o[p]);
+  float m_run = -INFINITY, l_run = 0.f;   // of row tid >> 2 (held by its 4 lanes)
+  for (int kb0 = 0; kb0 < L; kb0 += kKB) {
+    const int Lb = min(kKB, L - kb0);
+    const int Lk = (Lb + 63) & ~63, Lp = (Lb + 31) & ~31;
+    f32x16 acc[2][2];
+    gemm_nt(base + (size_t)q0 * C3, valid, C3, base + (size_t)kb0 * C3 + C, Lb, C3, C, Lk, Qs, Ks, acc);
+    __syncthreads();
+    acc_to_tile(acc, Ps, Lk, scale);
+    __syncthreads();
+    const float alpha = online_softmax<true>(Ps, Lb, m_run, l_run);
+    if ((tid & 3) == 0) Rs[tid >> 2] = alpha;
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < NCP; ++p) {
+      if (p * 256 < C) {
+        scale_rows(o[p], Rs);
+        pv_pass<kStreamVch>(Ps, Lp, base + (size_t)kb0 * C3 + 2 * C, Lb, C3, p * 256, min(256, C - p * 256), Vs, o[p]);
+      }
+    }
+    // (the next window's gemm_nt opens with a barrier before it writes the staging inside the tile; Rs is next written
+    // behind three more)
+  }
+  __syncthreads();
+  if ((tid & 3) == 0) Rs[tid >> 2] = 1.0f / l_run;
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < NCP; ++p) {
+    if (p * 256 < C) {
+      scale_rows(o[p], Rs);
+      store_acc(o[p], dst + ((size_t)n * L + q0) * C, C, valid, p * 256, C, 1.0f);
+    }
+  }
+}
+
+// ---- streaming backward 1: row max, row sum and D per query row ----
+__global__ __launch_bounds__(256) void attn_stream_stats_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
+                                                                const float* __restrict__ d_o, float* __restrict__ stats,
+                                                                int N, int L, int C, float scale) {
+  SSDE_LDS(smem);
+  float* Qs = smem;
+  float* Ks = smem + kQB * kLDC;
+  float* Ps = smem;
+  const int n = blockIdx.y, q0 = blockIdx.x * kQB, tid = threadIdx.x;
+  const int C3 = 3 * C;
+  const float* base = qkv + (size_t)n * L * C3;
+  const int valid = L - q0;
+  float m_run = -INFINITY, l_run = 0.f;
+  for (int kb0 = 0; kb0 < L; kb0 += kKB) {
+    const int Lb = min(kKB, L - kb0);
+    const int Lk = (Lb + 63) & ~63;
+    f32x16 acc[2][2];
+    gemm_nt(base + (size_t)q0 * C3, valid, C3, base + (size_t)kb0 * C3 + C, Lb, C3, C, Lk, Qs, Ks, acc);
+    __syncthreads();
+    acc_to_tile(acc, Ps, Lk, scale);
+    __syncthreads();
+    online_softmax<false>(Ps, Lb, m_run, l_run);
+  }
+  const int row = tid >> 2, sub = tid & 3;
+  float d = 0.f;
+  if (row < valid) {
+    const float* po = o + ((size_t)n * L + q0 + row) * C;
+    const float* pd = d_o + ((size_t)n * L + q0 + row) * C;
+    for (int c = sub * 4; c < C; c += 16) {
+      const float4 a = *reinterpret_cast<const float4*>(po + c);
+      const float4 b = *reinterpret_cast<const float4*>(pd + c);
+      d += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+    }
+  }
+  d += __shfl_xor(d, 1, 64);
+  d += __shfl_xor(d, 2, 64);
+  if (sub == 0 && row < valid) {
+    float* st = stats + ((size_t)n * L + q0 + row) * 4;
+    st[0] = m_run; st[1] = l_run; st[2] = d; st[3] = 0.f;
+  }
+}
+
+// tile[row][col] = exp(scale * acc - m) / l over the wave's 64 columns; zero for rows >= rows_valid and columns >= cols_valid.
+// kRowStats: m, l belong to the tile's ROWS (dQ: St[row], St[kKB + row]), else to its COLUMNS (dK / dV)
+template <bool kRowStats>
+__device__ __forceinline__ void acc_to_probs(const f32x16 (&acc)[2][2], float* Ps, const float* St, int Lk, int rows_valid, int cols_valid,
+                                             float scale) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int li = lane & 31, lh = lane >> 5, kb = wave * 64;
+  if (kb < Lk) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int col = kb + b * 32 + li;
+          const int s = kRowStats ? row : col;
+          float pv = 0.f;
+          if (row < rows_valid && col < cols_valid) pv = __expf(acc[a][b][r] * scale - St[s]) / St[kKB + s];
+          Ps[row * kLDP + col] = pv;
+        }
+  }
+}
+
+// tile[row][col] *= acc - D over the wave's 64 columns (columns < Lp)
+template <bool kRowStats>
+__device__ __forceinline__ void probs_to_ds(const f32x16 (&acc)[2][2], float* Ps, const float* St, int Lk, int Lp) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int li = lane & 31, lh = lane >> 5, kb = wave * 64;
+  if (kb < Lk) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int col = kb + b * 32 + li;
+          if (col < Lp) Ps[row * kLDP + col] *= (acc[a][b][r] - St[2 * kKB + (kRowStats ? row : col)]);
+        }
+  }
+}
+
+// ---- streaming backward 2: dQ for 64 query rows ----
+template <int NCP>
+__global__ __launch_bounds__(256) void attn_stream_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
+                                                                float* __restrict__ dqkv, const float* __restrict__ stats,
+                                                                int N, int L, int C, float scale) {
+  SSDE_LDS(smem);
+  float* Ps = smem;                       // [64 queries][260 keys]
+  float* Qs = smem + kTileFloats;         // staging
+  float* Ks = Qs + kQB * kLDC;
+  float* Vs = Qs;
+  float* St = smem + kTileFloats + kStageFloats;   // [3][256]: m, l, D of the block's 64 rows (the first 64 of each)
+  const int n = blockIdx.y, q0 = blockIdx.x * kQB, tid = threadIdx.x;
+  const int C3 = 3 * C;
+  const float* base = qkv + (size_t)n * L * C3;
+  const int valid = L - q0;
+  if (tid < kQB) {
+    float m = 0.f, l = 1.f, d = 0.f;
+    if (tid < valid) { const float* st = stats + ((size_t)n * L + q0 + tid) * 4; m = st[0]; l = st[1]; d = st[2]; }
+    St[tid] = m; St[kKB + tid] = l; St[2 * kKB + tid] = d;
+  }
+  f32x16 dq[NCP][2][2];
+#pragma unroll
+  for (int p = 0; p < NCP; ++p) zero_acc(dq[p]);
+  for (int kb0 = 0; kb0 < L; kb0 += kKB) {
+    const int Lb = min(kKB, L - kb0);
+    const int Lk = (Lb + 63) & ~63, Lp = (Lb + 31) & ~31;
+    f32x16 acc[2][2];
+    gemm_nt(base + (size_t)q0 * C3, valid, C3, base + (size_t)kb0 * C3 + C, Lb, C3, C, Lk, Qs, Ks, acc);
+    __syncthreads();                      // (also: the previous window's dS has been read, St is written)
+    acc_to_probs<true>(acc, Ps, St, Lk, valid, Lb, scale);
+    // dP = dO V_blk^T
+    gemm_nt(d_o + ((size_t)n * L + q0) * C, valid, C, base + (size_t)kb0 * C3 + 2 * C, Lb, C3, C, Lk, Qs, Ks, acc);
+    __syncthreads();
+    probs_to_ds<true>(acc, Ps, St, Lk, Lp);
+    // dQ += dS K_blk   (scale applied once, at the store)
+#pragma unroll
+    for (int p = 0; p < NCP; ++p)
+      if (p * 256 < C) pv_pass<32>(Ps, Lp, base + (size_t)kb0 * C3 + C, Lb, C3, p * 256, min(256, C - p * 256), Vs, dq[p]);
+  }
+#pragma unroll
+  for (int p = 0; p < NCP; ++p)
+    if (p * 256 < C) store_acc(dq[p], dqkv + ((size_t)n * L + q0) * C3, C3, valid, p * 256, C, scale);
+}
+
+// ---- streaming backward 3: dK, dV for 64 key rows and one 256-channel pass of the outputs ----
+__global__ __launch_bounds__(256) void attn_stream_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
+                                                                 float* __restrict__ dqkv, const float* __restrict__ stats,
+                                                                 int N, int L, int C, float scale) {
+  SSDE_LDS(smem);
+  float* Ps = smem;                       // [64 keys][260 queries]
+  float* Qs = smem + kTileFloats;
+  float* Ks = Qs + kQB * kLDC;
+  float* Vs = Qs;
+  float* St = smem + kTileFloats + kStageFloats;   // [3][256]: m, l, D of the window's queries
+  const int n = blockIdx.y, k0 = blockIdx.x * kQB, tid = threadIdx.x;
+  const int cp = blockIdx.z * 256, Cw = min(256, C - cp);
+  const int C3 = 3 * C;
+  const float* base = qkv + (size_t)n * L * C3;
+  const float* dob = d_o + (size_t)n * L * C;
+  const int valid = L - k0;
+  f32x16 dv[2][2], dk[2][2];
+  zero_acc(dv);
+  zero_acc(dk);
+  for (int qb0 = 0; qb0 < L; qb0 += kKB) {
+    const int Lb = min(kKB, L - qb0);
+    const int Lk = (Lb + 63) & ~63, Lp = (Lb + 31) & ~31;
+    __syncthreads();                      // the previous window's readers of St and of the tile are done
+    {
+      float m = 0.f, l = 1.f, d = 0.f;
+      if (tid < Lb) { const float* st = stats + ((size_t)n * L + qb0 + tid) * 4; m = st[0]; l = st[1]; d = st[2]; }
+      St[tid] = m; St[kKB + tid] = l; St[2 * kKB + tid] = d;
+    }
+    f32x16 acc[2][2];
+    // S^T = K_tile Q_blk^T
+    gemm_nt(base + (size_t)k0 * C3 + C, valid, C3, base + (size_t)qb0 * C3, Lb, C3, C, Lk, Qs, Ks, acc);
+    __syncthreads();
+    acc_to_probs<false>(acc, Ps, St, Lk, valid, Lb, scale);
+    // dV += P^T dO_blk
+    pv_pass<32>(Ps, Lp, dob + (size_t)qb0 * C, Lb, C, cp, Cw, Vs, dv);
+    // dP^T = V_tile dO_blk^T
+    gemm_nt(base + (size_t)k0 * C3 + 2 * C, valid, C3, dob + (size_t)qb0 * C, Lb, C, C, Lk, Qs, Ks, acc);
+    __syncthreads();
+    probs_to_ds<false>(acc, Ps, St, Lk, Lp);
+    // dK += dS^T Q_blk
+    pv_pass<32>(Ps, Lp, base + (size_t)qb0 * C3, Lb, C3, cp, Cw, Vs, dk);
+  }
+  float* out = dqkv + ((size_t)n * L + k0) * C3;
+  store_acc(dv, out + 2 * C, C3, valid, cp, C, 1.0f);
+  store_acc(dk, out + C, C3, valid, cp, C, scale);
+}
+
 template <typename K>
 int set_lds_once(K kfn, int bytes, std::atomic<bool>* done) {   // idempotent: a lost race only sets the attribute twice
   if (!*done) {
@@ -728,11 +1104,42 @@ int set_lds_once(K kfn, int bytes, std::atomic<bool>* done) {   // idempotent: a
 
 }  // namespace
 
+// The route of a forward launch (the plan query ssde_attention_route): no device access
+static int attn_route(const ssde_attn_args* a) {
+  SSDE_REQUIRE(a, "attention: null args");
+  SSDE_REQUIRE(a->n > 0 && a->l > 0 && a->l <= SSDE_ATTN_L_MAX, "attention: token count %d outside 1..%d", a->l, SSDE_ATTN_L_MAX);
+  SSDE_REQUIRE(a->c > 0 && a->c % 32 == 0, "attention: channels must be a multiple of 32 (got %d)", a->c);
+  if (a->l > kLMax || (a->flags & SSDE_ATTNF_STREAM)) {
+    SSDE_REQUIRE(a->c <= kStreamCMax, "attention: the streaming kernels (more than %d tokens, or SSDE_ATTNF_STREAM) take at most %d channels (got %d)",
+                 kLMax, kStreamCMax, a->c);
+    return SSDE_ATTN_ROUTE_STREAM;
+  }
+  if ((a->flags & SSDE_ATTNF_BF16X6) && a->l == x6::kL && a->c <= 256 && a->c % 64 == 0) return SSDE_ATTN_ROUTE_X6;
+  return SSDE_ATTN_ROUTE_F32;
+}
+
+extern "C" int ssde_attention_route(const ssde_attn_args* a) { return attn_route(a); }
+
 extern "C" int ssde_attention(const ssde_attn_args* a, void* stream) {
   SSDE_REQUIRE(a && a->qkv && a->dst, "attention: null args");
-  SSDE_REQUIRE(a->n > 0 && a->l > 0 && a->l <= kLMax, "attention: token count %d outside 1..%d", a->l, kLMax);
-  SSDE_REQUIRE(a->c > 0 && a->c % 32 == 0, "attention: channels must be a multiple of 32 (got %d)", a->c);
-  if ((a->flags & SSDE_ATTNF_BF16X6) && a->l == x6::kL && a->c <= 256 && a->c % 64 == 0) {
+  const int route = attn_route(a);
+  if (route < 0) return route;
+  if (route == SSDE_ATTN_ROUTE_STREAM) {
+    const int lds = kStreamLdsFloats * 4;
+    static std::atomic<bool> stream_set[2];   // set once, outside any stream capture
+    const dim3 grid(ssde_cdiv(a->l, kQB), a->n);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (a->c <= 256) {
+      if (int rc = set_lds_once(attn_stream_kernel<1>, lds, &stream_set[0])) return rc;
+      hipLaunchKernelGGL(attn_stream_kernel<1>, grid, dim3(256), lds, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
+    } else {
+      if (int rc = set_lds_once(attn_stream_kernel<2>, lds, &stream_set[1])) return rc;
+      hipLaunchKernelGGL(attn_stream_kernel<2>, grid, dim3(256), lds, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
+    }
+    SSDE_LAUNCH_CHECK();
+    return SSDE_OK;
+  }
+  if (route == SSDE_ATTN_ROUTE_X6) {
     static std::atomic<bool> x6_set[4];
     const dim3 grid(ssde_cdiv(a->n, 8) * 8 * 4);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -762,14 +1169,35 @@ extern "C" int ssde_attention(const ssde_attn_args* a, void* stream) {
 
 extern "C" int ssde_attention_bwd(const ssde_attn_bwd_args* a, void* stream) {
   SSDE_REQUIRE(a && a->qkv && a->o && a->d_o && a->dqkv && a->stats, "attention_bwd: null args");
-  SSDE_REQUIRE(a->n > 0 && a->l > 0 && a->l <= kLMax, "attention_bwd: token count %d outside 1..%d", a->l, kLMax);
+  SSDE_REQUIRE(a->n > 0 && a->l > 0 && a->l <= SSDE_ATTN_L_MAX, "attention_bwd: token count %d outside 1..%d", a->l, SSDE_ATTN_L_MAX);
   SSDE_REQUIRE(a->c > 0 && a->c % 32 == 0, "attention_bwd: channels must be a multiple of 32 (got %d)", a->c);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(ssde_cdiv(a->l, kQB), a->n);
+  if (a->l > kLMax) {   // (no flag field: the backward routes by the token count alone)
+    SSDE_REQUIRE(a->c <= kStreamCMax, "attention_bwd: the streaming kernels (more than %d tokens) take at most %d channels (got %d)", kLMax,
+                 kStreamCMax, a->c);
+    const int lds_s = kStreamLdsFloats * 4, lds_b = kStreamBwdLdsFloats * 4;
+    static std::atomic<bool> set_s{false}, set_sq[2], set_skv{false};
+    if (int rc = set_lds_once(attn_stream_stats_kernel, lds_s, &set_s)) return rc;
+    if (int rc = set_lds_once(attn_stream_bwd_q_kernel<1>, lds_b, &set_sq[0])) return rc;
+    if (int rc = set_lds_once(attn_stream_bwd_q_kernel<2>, lds_b, &set_sq[1])) return rc;
+    if (int rc = set_lds_once(attn_stream_bwd_kv_kernel, lds_b, &set_skv)) return rc;
+    hipLaunchKernelGGL(attn_stream_stats_kernel, grid, dim3(256), lds_s, st, a->qkv, a->o, a->d_o, a->stats, a->n, a->l, a->c, a->scale);
+    SSDE_LAUNCH_CHECK();
+    if (a->c <= 256)
+      hipLaunchKernelGGL(attn_stream_bwd_q_kernel<1>, grid, dim3(256), lds_b, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
+    else
+      hipLaunchKernelGGL(attn_stream_bwd_q_kernel<2>, grid, dim3(256), lds_b, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
+    SSDE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_stream_bwd_kv_kernel, dim3(grid.x, grid.y, ssde_cdiv(a->c, 256)), dim3(256), lds_b, st, a->qkv, a->d_o, a->dqkv,
+                       a->stats, a->n, a->l, a->c, a->scale);
+    SSDE_LAUNCH_CHECK();
+    return SSDE_OK;
+  }
   const int lds = kBwdLdsFloats * 4;
   static std::atomic<bool> set_q{false}, set_kv{false};
   if (int rc = set_lds_once(attn_bwd_q_kernel, lds, &set_q)) return rc;
   if (int rc = set_lds_once(attn_bwd_kv_kernel, lds, &set_kv)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(ssde_cdiv(a->l, kQB), a->n);
   hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(256), lds, st, a->qkv, a->o, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
   SSDE_LAUNCH_CHECK();
   hipLaunchKernelGGL(attn_bwd_kv_kernel, grid, dim3(256), lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);

@@ -1297,7 +1297,8 @@ class UNetEngine:
         return sum(self.program.flops)
 
     def validate_plans(self):
-        """Host-side check of every conv launch plan (tile choice, halo fit, LDS size); returns LDS bytes per conv."""
+        """Host-side check of every conv launch plan (tile choice, halo fit, LDS size) and of every attention launch (token
+        count, channels: ssde_attention_route); returns LDS bytes per conv."""
         lib = L.load()
         out = []
         for i in range(self.program.n):
@@ -1307,4 +1308,7 @@ class UNetEngine:
                 if r < 0:
                     raise L.SsdeError("op %d: %s" % (i, lib.ssde_last_error().decode()))
                 out.append(r)
+            elif op.kind == L.OP_ATTN:
+                if lib.ssde_attention_route(C.byref(op.u.attn)) < 0:
+                    raise L.SsdeError("op %d: %s" % (i, lib.ssde_last_error().decode()))
         return out

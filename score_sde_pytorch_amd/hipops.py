@@ -185,6 +185,18 @@ def attention(qkv, channels):
     return dst
 
 
+def attention_route(n, l, channels, flags=None):
+    """the kernel ssde_attention takes for this shape (L.ATTN_ROUTE_*); raises SsdeError for a launch it would refuse.  No device."""
+    a = L.AttnArgs()
+    a.n, a.l, a.c, a.scale = n, l, channels, float(max(int(channels), 1) ** (-0.5))
+    a.flags = L.attn_route_flags() if flags is None else flags
+    lib = L.load()
+    r = lib.ssde_attention_route(C.byref(a))
+    if r < 0:
+        raise L.SsdeError(lib.ssde_last_error().decode())
+    return r
+
+
 def embed(cond, table, dim, kind):
     _need_cuda(cond, table)
     dst = torch.empty(cond.shape[0], dim, device=cond.device)
