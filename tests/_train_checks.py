@@ -208,6 +208,9 @@ def check_backward_ops(dev):
         o.backward(do)
         dqkv = ops.attention_bwd(d(qkv.detach()), d(o.detach().contiguous()), d(do), Cc)
         assert rel_err(dqkv, qkv.grad) < TOL_OP, ("attention_bwd", n, Lt, Cc)
+        for i, part in enumerate(("dq", "dk", "dv")):       # each part over its own largest value: a wrong dk cannot hide behind dq or dv
+            e = rel_err(dqkv[..., i * Cc:(i + 1) * Cc], qkv.grad[..., i * Cc:(i + 1) * Cc])
+            assert e < TOL_OP, ("attention_bwd", part, n, Lt, Cc, e)
     # ---- DSM loss head
     sc = torch.randn(4, 3, 8, 8, generator=g).requires_grad_()
     z = torch.randn(4, 3, 8, 8, generator=g)
