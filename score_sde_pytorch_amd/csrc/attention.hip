@@ -16,6 +16,11 @@
 //   kernel A (per 64 query rows):  P, D_i = dO_i . O_i;  dP = dO V^T;  dS = P o (dP - D);  dQ = scale dS K
 //   kernel B (per 64 key rows):    P^T from the saved row max / row sum;  dV = P^T dO;
 //                                  dP^T = V dO^T;  dS^T = P^T o (dP^T - D);  dK = scale dS^T Q
+// The fp32 kernels of both sets are cut from one copy of each tile step: gemm_nt (A B^T into the accumulators), pv_pass (the P.V
+// loop of one 256-channel pass; gemm_pv = zero, pv_pass, store per pass), the accumulator <-> tile mapping (acc_row / acc_col) under
+// the epilogues acc_to_tile, acc_to_probs, probs_to_ds, scale_rows and store_acc, online_softmax (softmax_rows is its single
+// window, normalised), row_dot (D) and load_stats (m, l, D into LDS).  attn_x6_kernel alone keeps copies of its own: its loads are
+// issued from asm and its ISA is pinned (tools/isa_inflight_check.py).
 // qkv layout [N, L, 3C]: the fused NIN_0..2 projection output (q | k | v).
 #include "ssde_common.h"
 #include <type_traits>
@@ -25,14 +30,15 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 namespace {
 
 constexpr int kQB = 64;          // rows per workgroup
-constexpr int kLMax = 256;
+constexpr int kLMax = 256;       // tokens of a score tile: all the single-tile kernels take
+constexpr int kKB = kLMax;       // keys (dK / dV: queries) per window of the streaming kernels: the same tile, and one St layout for both kernel sets
 constexpr int kLDC = 36;         // channel-chunk row stride (32 + 4)
 constexpr int kLDP = 260;        // score / V row stride (256 + 4)
 constexpr int kTileFloats = kQB * kLDP;                 // the 64 x L tile
 constexpr int kStageFloats = (kQB + kLMax) * kLDC;      // Q/K chunk staging (phase 1); >= 32 * kLDP (phase 3)
 constexpr int kFwdVch = 8;                              // V tokens per chunk of the forward kernel
 constexpr int kAttnLdsFloats = kQB * kLDP + kFwdVch * kLDP;  // forward: Q/K staging aliases the tile in phase 1; 75 KB: two workgroups per CU
-constexpr int kBwdLdsFloats = kTileFloats + kStageFloats + 3 * kLMax;
+constexpr int kBwdLdsFloats = kTileFloats + kStageFloats + 3 * kLMax;   // backward: tile | staging | St[3][256]: m, l, D per row or column
 
 __device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
 #pragma unroll
@@ -42,6 +48,12 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 }
+
+// The accumulators of a wave's 64 x 64 block (four 32 x 32 results of v_mfma_f32_32x32x2_f32): register r of acc[a][b] holds, in
+// lane li + 32 lh, row acc_row(a, r, lh) of the block and column acc_col(kb, b, li) of the tile or output, kb being the block's first
+// column there.
+__device__ __forceinline__ int acc_row(int a, int r, int lh) { return a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh; }
+__device__ __forceinline__ int acc_col(int kb, int b, int li) { return kb + b * 32 + li; }
 
 // acc (wave: rows 0..63 x columns kb..kb+63, kb = wave*64) = A[64 x C] * B[Lk x C]^T.
 // A: 64 rows from pointer A (row stride lda), rows >= a_valid read as zero; B likewise with b_valid rows.
@@ -102,87 +114,112 @@ __device__ __forceinline__ void gemm_nt(const float* __restrict__ A, int a_valid
   }
 }
 
-// out[64 x C] = out_scale * Ps[64 x Lp] * Bm[L x C]   (Bm token-major rows, row stride ldb, rows >= b_valid zero)
-// VCH = tokens of V staged per chunk (a multiple of 8): 32 in the backward kernels; 8 in the forward kernel, whose LDS
-// footprint (64 x 260 score tile + the chunk) then lets two workgroups share a CU.
+// acc += Ps[64 x Lp] * Bm[rows x (cp .. cp + Cw)]   (Bm token-major rows, row stride ldb, rows >= b_valid zero): the P.V loop of every
+// fp32 kernel, for one 256-channel pass of which the wave takes 64 channels.  VCH = tokens of V staged per chunk (a multiple of 8):
+// 32 in the backward kernels; 8 in the forward kernel, whose LDS footprint (64 x 260 score tile + the chunk) then lets two
+// workgroups share a CU; 16 in the streaming forward.
+template <int VCH>
+__device__ __forceinline__ void pv_pass(const float* Ps, int Lp, const float* __restrict__ Bm, int b_valid, size_t ldb, int cp, int Cw,
+                                        float* Vs, f32x16 (&acc)[2][2]) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 31, lh = lane >> 5;
+  const int cb = wave * 64;
+  constexpr int NIT = VCH / 4;
+  const int f4n = Cw >> 2;
+  int vrow[NIT], vf[NIT];
+  {
+    int row = tid / f4n, ff = tid - row * f4n;
+    const int dr = 256 / f4n, df = 256 - dr * f4n;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      vrow[it] = row; vf[it] = ff;
+      row += dr; ff += df;
+      if (ff >= f4n) { ff -= f4n; ++row; }
+    }
+  }
+  float4 rv[NIT];
+  auto load_chunk = [&](int k0) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int tok = k0 + vrow[it];
+      const float4 v = *reinterpret_cast<const float4*>(Bm + (size_t)max(min(tok, b_valid - 1), 0) * ldb + cp + vf[it] * 4);
+      rv[it] = (vrow[it] < VCH && tok < b_valid) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  load_chunk(0);
+  for (int k0 = 0; k0 < Lp; k0 += VCH) {
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+      if (vrow[it] < VCH) *reinterpret_cast<float4*>(Vs + vrow[it] * kLDP + vf[it] * 4) = rv[it];
+    __syncthreads();
+    if (k0 + VCH < Lp) load_chunk(k0 + VCH);
+    if (cb < Cw) {
+#pragma unroll
+      for (int kk = 0; kk < VCH / 8; ++kk) {
+        float4 af[2];
+        float bf[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const float4*>(Ps + (a * 32 + li) * kLDP + k0 + kk * 8 + lh * 4);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bf[b][j] = Vs[(kk * 8 + lh * 4 + j) * kLDP + cb + b * 32 + li];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].x, bf[b][0], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].y, bf[b][1], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].z, bf[b][2], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].w, bf[b][3], acc[a][b], 0, 0, 0);
+          }
+      }
+    }
+  }
+}
+
+// acc[a][b][r] *= Rs[row of (a, r)]   (Rs: one float per row of the 64-row block, in LDS)
+__device__ __forceinline__ void scale_rows(f32x16 (&acc)[2][2], const float* Rs) {
+  const int lh = (threadIdx.x & 63) >> 5;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float s = Rs[acc_row(a, r, lh)];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[a][b][r] *= s;
+    }
+}
+
+// out[row][cp + wave's 64 channels] = acc * mul for rows < out_valid, channels < C
+__device__ __forceinline__ void store_acc(const f32x16 (&acc)[2][2], float* __restrict__ out, size_t ldo, int out_valid, int cp, int C,
+                                          float mul) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int li = lane & 31, lh = lane >> 5;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int col = acc_col(cp + wave * 64, b, li);
+      if (col >= C) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = acc_row(a, r, lh);
+        if (row < out_valid) out[(size_t)row * ldo + col] = acc[a][b][r] * mul;
+      }
+    }
+}
+
+// out[64 x C] = out_scale * Ps[64 x Lp] * Bm[L x C], one 256-channel pass after the other
 template <int VCH = 32>
 __device__ __forceinline__ void gemm_pv(const float* Ps, int Lp, const float* __restrict__ Bm, int b_valid, size_t ldb, int C,
                                         float* Vs, float* __restrict__ out, size_t ldo, int out_valid, float out_scale) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 31, lh = lane >> 5;
   f32x16 acc[2][2];
   for (int cp = 0; cp < C; cp += 256) {
-    const int Cw = min(256, C - cp);
-    const int cb = wave * 64;
     zero_acc(acc);
-    // VCH-token chunk of V: up to VCH / 4 float4 per thread, prefetched into registers during the MFMAs of the previous chunk
-    constexpr int NIT = VCH / 4;
-    const int f4n = Cw >> 2;
-    int vrow[NIT], vf[NIT];
-    {
-      int row = tid / f4n, ff = tid - row * f4n;
-      const int dr = 256 / f4n, df = 256 - dr * f4n;
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        vrow[it] = row; vf[it] = ff;
-        row += dr; ff += df;
-        if (ff >= f4n) { ff -= f4n; ++row; }
-      }
-    }
-    float4 rv[NIT];
-    auto load_chunk = [&](int k0) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int tok = k0 + vrow[it];
-        const float4 v = *reinterpret_cast<const float4*>(Bm + (size_t)max(min(tok, b_valid - 1), 0) * ldb + cp + vf[it] * 4);
-        rv[it] = (vrow[it] < VCH && tok < b_valid) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    load_chunk(0);
-    for (int k0 = 0; k0 < Lp; k0 += VCH) {
-      __syncthreads();
-#pragma unroll
-      for (int it = 0; it < NIT; ++it)
-        if (vrow[it] < VCH) *reinterpret_cast<float4*>(Vs + vrow[it] * kLDP + vf[it] * 4) = rv[it];
-      __syncthreads();
-      if (k0 + VCH < Lp) load_chunk(k0 + VCH);
-      if (cb < Cw) {
-#pragma unroll
-        for (int kk = 0; kk < VCH / 8; ++kk) {
-          float4 af[2];
-          float bf[2][4];
-#pragma unroll
-          for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const float4*>(Ps + (a * 32 + li) * kLDP + k0 + kk * 8 + lh * 4);
-#pragma unroll
-          for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bf[b][j] = Vs[(kk * 8 + lh * 4 + j) * kLDP + cb + b * 32 + li];
-#pragma unroll
-          for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].x, bf[b][0], acc[a][b], 0, 0, 0);
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].y, bf[b][1], acc[a][b], 0, 0, 0);
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].z, bf[b][2], acc[a][b], 0, 0, 0);
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].w, bf[b][3], acc[a][b], 0, 0, 0);
-            }
-        }
-      }
-    }
-    if (cb < Cw) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const int col = cp + cb + b * 32 + li;
-          if (col >= C) continue;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (row < out_valid) out[(size_t)row * ldo + col] = acc[a][b][r] * out_scale;
-          }
-        }
-    }
+    pv_pass<VCH>(Ps, Lp, Bm, b_valid, ldb, cp, min(256, C - cp), Vs, acc);
+    store_acc(acc, out, ldo, out_valid, cp, C, out_scale);
   }
 }
 
@@ -197,31 +234,51 @@ __device__ __forceinline__ void acc_to_tile(const f32x16 (&acc)[2][2], float* Ps
       for (int b = 0; b < 2; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          Ps[row * kLDP + kb + b * 32 + li] = acc[a][b][r] * mul;
+          const int row = acc_row(a, r, lh), col = acc_col(kb, b, li);
+          Ps[row * kLDP + col] = acc[a][b][r] * mul;
         }
   }
 }
 
-// softmax over the first L columns of each of the 64 rows (4 lanes per row); columns L..Lp-1 zeroed.
-// Optionally returns the row max and the row sum of exp (lane sub == 0 of each row holds them).
-__device__ __forceinline__ void softmax_rows(float* Ps, int L, float* m_out, float* l_out) {
+// One window of the online softmax over the first Lb columns of the tile (4 lanes per row):
+// m_new = max(m, row max), alpha = exp(m - m_new), l = l * alpha + sum_j exp(s_j - m_new).  kWriteP: the tile becomes
+// exp(s - m_new) with columns Lb .. roundup(Lb, 32) - 1 zeroed.  Returns alpha (the same value in the 4 lanes of a row).
+template <bool kWriteP>
+__device__ __forceinline__ float online_softmax(float* Ps, int Lb, float& m_run, float& l_run) {
   const int tid = threadIdx.x;
   const int row = tid >> 2, sub = tid & 3;
   float* prow = Ps + row * kLDP;
   float m = -INFINITY;
-  for (int j = sub; j < L; j += 4) m = fmaxf(m, prow[j]);
+  for (int j = sub; j < Lb; j += 4) m = fmaxf(m, prow[j]);
   m = fmaxf(m, __shfl_xor(m, 1, 64));
   m = fmaxf(m, __shfl_xor(m, 2, 64));
+  m = fmaxf(m, m_run);
+  const float alpha = __expf(m_run - m);                    // first window: exp(-inf) = 0 against l = 0 and O = 0
   float sum = 0.f;
-  for (int j = sub; j < L; j += 4) { const float e = __expf(prow[j] - m); prow[j] = e; sum += e; }
+  for (int j = sub; j < Lb; j += 4) {
+    const float e = __expf(prow[j] - m);
+    if (kWriteP) prow[j] = e;
+    sum += e;
+  }
   sum += __shfl_xor(sum, 1, 64);
   sum += __shfl_xor(sum, 2, 64);
-  const float inv = 1.0f / sum;
-  for (int j = sub; j < L; j += 4) prow[j] *= inv;
-  const int Lp = (L + 31) & ~31;
-  for (int j = L + sub; j < Lp; j += 4) prow[j] = 0.f;
-  *m_out = m; *l_out = sum;
+  if (kWriteP) {
+    const int Lp = (Lb + 31) & ~31;
+    for (int j = Lb + sub; j < Lp; j += 4) prow[j] = 0.f;
+  }
+  l_run = l_run * alpha + sum;
+  m_run = m;
+  return alpha;
+}
+
+// softmax over the first L columns of each of the 64 rows, columns L..Lp-1 zeroed: the only window of an online softmax (alpha =
+// exp(-inf) = 0 against l = 0), normalised in place.  m, l: the row max and the row sum of exp (the same in the 4 lanes of a row).
+__device__ __forceinline__ void softmax_rows(float* Ps, int L, float& m, float& l) {
+  m = -INFINITY; l = 0.f;
+  online_softmax<true>(Ps, L, m, l);
+  float* prow = Ps + (threadIdx.x >> 2) * kLDP;
+  const float inv = 1.0f / l;
+  for (int j = threadIdx.x & 3; j < L; j += 4) prow[j] *= inv;
 }
 
 __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv, float* __restrict__ dst,
@@ -243,7 +300,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv
   acc_to_tile(acc, Ps, Lk, scale);
   __syncthreads();
   float m, l;
-  softmax_rows(Ps, L, &m, &l);
+  softmax_rows(Ps, L, m, l);
   gemm_pv<kFwdVch>(Ps, Lp, base + 2 * C, L, C3, C, Vs, dst + ((size_t)n * L + q0) * C, C, L - q0, 1.0f);
 }
 
@@ -590,6 +647,79 @@ __global__ __launch_bounds__(x6::kT) void attn_x6_kernel(const float* __restrict
 #undef SSDE_X6_WAIT
 }
 
+// ---- what the backward kernels of both sets share -----------------------------------------------------------------------------
+// St[3][kKB] in LDS holds m, l and D = sum_c dO * O of the tile's query rows: indexed by the tile's ROW where a workgroup owns
+// 64 queries (dQ: the first 64 of each), by its COLUMN where it owns 64 keys and the queries are the window (dK / dV).
+
+// sum_c o[row][c] * d_o[row][c] of row tid >> 2 of the 64-row block that starts at row `first` of o / d_o [N * L][C] (4 lanes per
+// row, each returns the sum); 0 for rows >= valid
+__device__ __forceinline__ float row_dot(const float* __restrict__ o, const float* __restrict__ d_o, size_t first, int C, int valid) {
+  const int row = threadIdx.x >> 2, sub = threadIdx.x & 3;
+  float d = 0.f;
+  if (row < valid) {
+    const float* po = o + (first + row) * C;
+    const float* pd = d_o + (first + row) * C;
+    for (int c = sub * 4; c < C; c += 16) {
+      const float4 a = *reinterpret_cast<const float4*>(po + c);
+      const float4 b = *reinterpret_cast<const float4*>(pd + c);
+      d += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+    }
+  }
+  d += __shfl_xor(d, 1, 64);
+  d += __shfl_xor(d, 2, 64);
+  return d;
+}
+
+// Thread tid fills entry tid of St from row first + tid of stats[N * L][4]; entries >= count get (0, 1, 0), which keeps
+// exp(s - m) / l finite where it is computed and then dropped.  (The caller decides which threads call.)
+__device__ __forceinline__ void load_stats(float* St, const float* __restrict__ stats, size_t first, int count) {
+  const int j = threadIdx.x;
+  float m = 0.f, l = 1.f, d = 0.f;
+  if (j < count) { const float* st = stats + (first + j) * 4; m = st[0]; l = st[1]; d = st[2]; }
+  St[j] = m; St[kKB + j] = l; St[2 * kKB + j] = d;
+}
+
+// tile[row][col] = exp(scale * acc - m) / l over the wave's 64 columns; zero for rows >= rows_valid and columns >= cols_valid.
+// kRowStats: m, l belong to the tile's ROWS (dQ), else to its COLUMNS (dK / dV)
+template <bool kRowStats>
+__device__ __forceinline__ void acc_to_probs(const f32x16 (&acc)[2][2], float* Ps, const float* St, int Lk, int rows_valid, int cols_valid,
+                                             float scale) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int li = lane & 31, lh = lane >> 5, kb = wave * 64;
+  if (kb < Lk) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = acc_row(a, r, lh), col = acc_col(kb, b, li);
+          const int s = kRowStats ? row : col;
+          float pv = 0.f;
+          if (row < rows_valid && col < cols_valid) pv = __expf(acc[a][b][r] * scale - St[s]) / St[kKB + s];
+          Ps[row * kLDP + col] = pv;
+        }
+  }
+}
+
+// tile[row][col] *= acc - D over the wave's 64 columns (columns < Lp)
+template <bool kRowStats>
+__device__ __forceinline__ void probs_to_ds(const f32x16 (&acc)[2][2], float* Ps, const float* St, int Lk, int Lp) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int li = lane & 31, lh = lane >> 5, kb = wave * 64;
+  if (kb < Lk) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = acc_row(a, r, lh), col = acc_col(kb, b, li);
+          if (col < Lp) Ps[row * kLDP + col] *= (acc[a][b][r] - St[2 * kKB + (kRowStats ? row : col)]);
+        }
+  }
+}
+
 // ---- backward A: dQ (and the per-row softmax statistics + D for kernel B) ----
 __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                          const float* __restrict__ d_o, float* __restrict__ dqkv,
@@ -599,7 +729,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float* __restrict
   float* Qs = smem + kTileFloats;         // staging
   float* Ks = Qs + kQB * kLDC;
   float* Vs = Qs;
-  float* Ds = smem + kTileFloats + kStageFloats;   // [64]
+  float* St = smem + kTileFloats + kStageFloats;   // [3][256]: only D of the block's 64 rows (P comes from the softmax below)
   const int n = blockIdx.y, q0 = blockIdx.x * kQB, tid = threadIdx.x;
   const int C3 = 3 * C;
   const float* base = qkv + (size_t)n * L * C3;
@@ -612,47 +742,20 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float* __restrict
   acc_to_tile(acc, Ps, Lk, scale);
   __syncthreads();
   float m, l;
-  softmax_rows(Ps, L, &m, &l);
-  {   // D_i = sum_c dO[i,c] * O[i,c]; 4 lanes per row
-    const int row = tid >> 2, sub = tid & 3;
-    float d = 0.f;
+  softmax_rows(Ps, L, m, l);
+  const float d = row_dot(o, d_o, (size_t)n * L + q0, C, valid);
+  if ((tid & 3) == 0) {
+    const int row = tid >> 2;
+    St[2 * kKB + row] = d;
     if (row < valid) {
-      const float* po = o + ((size_t)n * L + q0 + row) * C;
-      const float* pd = d_o + ((size_t)n * L + q0 + row) * C;
-      for (int c = sub * 4; c < C; c += 16) {
-        const float4 a = *reinterpret_cast<const float4*>(po + c);
-        const float4 b = *reinterpret_cast<const float4*>(pd + c);
-        d += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
-      }
-    }
-    d += __shfl_xor(d, 1, 64);
-    d += __shfl_xor(d, 2, 64);
-    if (sub == 0) {
-      Ds[row] = d;
-      if (row < valid) {
-        float* st = stats + ((size_t)n * L + q0 + row) * 4;
-        st[0] = m; st[1] = l; st[2] = d; st[3] = 0.f;
-      }
+      float* st = stats + ((size_t)n * L + q0 + row) * 4;
+      st[0] = m; st[1] = l; st[2] = d; st[3] = 0.f;
     }
   }
   // dP = dO V^T
   gemm_nt(d_o + ((size_t)n * L + q0) * C, valid, C, base + 2 * C, L, C3, C, Lk, Qs, Ks, acc);
   __syncthreads();
-  {   // dS = P o (dP - D), in place over P
-    const int wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5, kb = wave * 64;
-    if (kb < Lk) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int col = kb + b * 32 + li;
-            if (col < Lp) Ps[row * kLDP + col] *= (acc[a][b][r] - Ds[row]);
-          }
-    }
-  }
+  probs_to_ds<true>(acc, Ps, St, Lk, Lp);   // dS = P o (dP - D), in place over P
   // dQ = scale * dS K
   gemm_pv(Ps, Lp, base + C, L, C3, C, Vs, dqkv + ((size_t)n * L + q0) * C3, C3, valid, scale);
 }
@@ -667,64 +770,36 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
   float* Ks = Qs + kQB * kLDC;
   float* Vs = Qs;
   float* St = smem + kTileFloats + kStageFloats;   // [3][256]: m, l, D per query
-  const int n = blockIdx.y, k0 = blockIdx.x * kQB, tid = threadIdx.x;
+  const int n = blockIdx.y, k0 = blockIdx.x * kQB;
   const int C3 = 3 * C;
   const float* base = qkv + (size_t)n * L * C3;
   const int Lk = (L + 63) & ~63, Lp = (L + 31) & ~31;
   const int valid = L - k0;
-  for (int j = tid; j < kLMax; j += 256) {
-    float m = 0.f, l = 1.f, d = 0.f;
-    if (j < L) { const float* st = stats + ((size_t)n * L + j) * 4; m = st[0]; l = st[1]; d = st[2]; }
-    St[j] = m; St[kLMax + j] = l; St[2 * kLMax + j] = d;
-  }
-  const int wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5, kb = wave * 64;
+  load_stats(St, stats, (size_t)n * L, L);
 
   f32x16 acc[2][2];
   // S^T = K_tile Q^T
   gemm_nt(base + (size_t)k0 * C3 + C, valid, C3, base, L, C3, C, Lk, Qs, Ks, acc);
   __syncthreads();
-  if (kb < Lk) {   // P^T[key, query] = exp(scale * s - m_q) / l_q ; rows (keys) >= valid and columns (queries) >= L are zero
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const int col = kb + b * 32 + li;
-          float pv = 0.f;
-          if (row < valid && col < L) pv = __expf(acc[a][b][r] * scale - St[col]) / St[kLMax + col];
-          Ps[row * kLDP + col] = pv;
-        }
-  }
+  // P^T[key, query] = exp(scale * s - m_q) / l_q ; rows (keys) >= valid and columns (queries) >= L are zero
+  acc_to_probs<false>(acc, Ps, St, Lk, valid, L, scale);
   __syncthreads();
   // dV = P^T dO
   gemm_pv(Ps, Lp, d_o + (size_t)n * L * C, L, C, C, Vs, dqkv + ((size_t)n * L + k0) * C3 + 2 * C, C3, valid, 1.0f);
   // dP^T = V_tile dO^T
   gemm_nt(base + (size_t)k0 * C3 + 2 * C, valid, C3, d_o + (size_t)n * L * C, L, C, C, Lk, Qs, Ks, acc);
   __syncthreads();
-  if (kb < Lk) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const int col = kb + b * 32 + li;
-          if (col < Lp) Ps[row * kLDP + col] *= (acc[a][b][r] - St[2 * kLMax + col]);
-        }
-  }
+  probs_to_ds<false>(acc, Ps, St, Lk, Lp);   // dS^T = P^T o (dP^T - D)
   // dK = scale * dS^T Q
   gemm_pv(Ps, Lp, base, L, C3, C, Vs, dqkv + ((size_t)n * L + k0) * C3 + C, C3, valid, scale);
 }
 
 // ---- more than 256 tokens: streaming kernels (ABI 13, added without a layout change) ---------------------------------------------------------------------------
-// The kernels above hold a whole 64 x L score tile in LDS, which is what stops them at L = 256.  The kernels below keep the
-// same tile, the same two GEMM phases and the same fragment handling, but the tile is a WINDOW of at most 256 keys (forward, dQ)
-// or 256 queries (dK / dV) that walks the other axis in a fixed order, and the output stays in the accumulator registers across
-// the windows (4 waves x 64 channels: 64 accumulator VGPRs per 256 channels).  Nothing of size L^2 reaches HBM, there are no
-// atomics, and two runs agree to the bit.
+// The kernels above hold a whole 64 x L score tile in LDS, which is what stops them at L = 256.  The kernels below are built from
+// the same pieces (gemm_nt, pv_pass, the tile epilogues, the online softmax), but the tile is a WINDOW of at most 256 keys
+// (forward, dQ) or 256 queries (dK / dV) that walks the other axis in a fixed order, and the output stays in the accumulator
+// registers across the windows (4 waves x 64 channels: 64 accumulator VGPRs per 256 channels).  Nothing of size L^2 reaches HBM,
+// there are no atomics, and two runs agree to the bit.
 //   forward   attn_stream_kernel<NCP>: per key block S = Q K_blk^T -> tile; online softmax (running row max m and row sum l,
 //             P_blk = exp(S - m_new) left unnormalised); O *= exp(m_old - m_new); O += P_blk V_blk; at the end O /= l, once.
 //             NCP = channel passes of 256 (1: C <= 256, 2: C <= 512) = accumulator sets held by a wave.
@@ -735,136 +810,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
 //             256 accumulator registers of dK and dV beside the 64 of the running product).
 // Rows / keys past L: gemm_nt and pv_pass clamp their addresses and zero what they fetched, the softmax reads the valid columns
 // only and zeroes the tile up to the next multiple of 32, and no row >= L is stored.
-constexpr int kKB = 256;                                    // keys (dK / dV: queries) per window
 constexpr int kStreamCMax = 512;                            // two 256-channel passes held in registers (the widest attention of a shipped config)
 constexpr int kStreamVch = 16;                              // V tokens per chunk of the streaming forward (one workgroup per CU: 290 registers)
 constexpr int kStreamLdsFloats = kQB * kLDP + kStreamVch * kLDP + kQB;   // forward / statistics: tile | V chunk | one float per row (83 KB)
-constexpr int kStreamBwdLdsFloats = kBwdLdsFloats;          // backward: tile | staging | 3 x 256 row constants
-
-// acc += Ps[64 x Lp] * Bm[rows x (cp .. cp + Cw)]: gemm_pv's main loop for one 256-channel pass, without its zeroing and its store
-template <int VCH>
-__device__ __forceinline__ void pv_pass(const float* Ps, int Lp, const float* __restrict__ Bm, int b_valid, size_t ldb, int cp, int Cw,
-                                        float* Vs, f32x16 (&acc)[2][2]) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 31, lh = lane >> 5;
-  const int cb = wave * 64;
-  constexpr int NIT = VCH / 4;
-  const int f4n = Cw >> 2;
-  int vrow[NIT], vf[NIT];
-  {
-    int row = tid / f4n, ff = tid - row * f4n;
-    const int dr = 256 / f4n, df = 256 - dr * f4n;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      vrow[it] = row; vf[it] = ff;
-      row += dr; ff += df;
-      if (ff >= f4n) { ff -= f4n; ++row; }
-    }
-  }
-  float4 rv[NIT];
-  auto load_chunk = [&](int k0) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int tok = k0 + vrow[it];
-      const float4 v = *reinterpret_cast<const float4*>(Bm + (size_t)max(min(tok, b_valid - 1), 0) * ldb + cp + vf[it] * 4);
-      rv[it] = (vrow[it] < VCH && tok < b_valid) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  load_chunk(0);
-  for (int k0 = 0; k0 < Lp; k0 += VCH) {
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < NIT; ++it)
-      if (vrow[it] < VCH) *reinterpret_cast<float4*>(Vs + vrow[it] * kLDP + vf[it] * 4) = rv[it];
-    __syncthreads();
-    if (k0 + VCH < Lp) load_chunk(k0 + VCH);
-    if (cb < Cw) {
-#pragma unroll
-      for (int kk = 0; kk < VCH / 8; ++kk) {
-        float4 af[2];
-        float bf[2][4];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const float4*>(Ps + (a * 32 + li) * kLDP + k0 + kk * 8 + lh * 4);
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bf[b][j] = Vs[(kk * 8 + lh * 4 + j) * kLDP + cb + b * 32 + li];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].x, bf[b][0], acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].y, bf[b][1], acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].z, bf[b][2], acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a].w, bf[b][3], acc[a][b], 0, 0, 0);
-          }
-      }
-    }
-  }
-}
-
-// acc[a][b][r] *= Rs[row of (a, r)]   (Rs: one float per row of the 64-row block, in LDS)
-__device__ __forceinline__ void scale_rows(f32x16 (&acc)[2][2], const float* Rs) {
-  const int lh = (threadIdx.x & 63) >> 5;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float s = Rs[a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh];
-#pragma unroll
-      for (int b = 0; b < 2; ++b) acc[a][b][r] *= s;
-    }
-}
-
-// out[row][cp + wave's 64 channels] = acc * mul for rows < out_valid, channels < C
-__device__ __forceinline__ void store_acc(const f32x16 (&acc)[2][2], float* __restrict__ out, size_t ldo, int out_valid, int cp, int C,
-                                          float mul) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int li = lane & 31, lh = lane >> 5;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int col = cp + wave * 64 + b * 32 + li;
-      if (col >= C) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < out_valid) out[(size_t)row * ldo + col] = acc[a][b][r] * mul;
-      }
-    }
-}
-
-// One window of the online softmax over the first Lb columns of the tile (4 lanes per row, the arithmetic of softmax_rows):
-// m_new = max(m, row max), alpha = exp(m - m_new), l = l * alpha + sum_j exp(s_j - m_new).  kWriteP: the tile becomes
-// exp(s - m_new) with columns Lb .. roundup(Lb, 32) - 1 zeroed.  Returns alpha (the same value in the 4 lanes of a row).
-template <bool kWriteP>
-__device__ __forceinline__ float online_softmax(float* Ps, int Lb, float& m_run, float& l_run) {
-  const int tid = threadIdx.x;
-  const int row = tid >> 2, sub = tid & 3;
-  float* prow = Ps + row * kLDP;
-  float m = -INFINITY;
-  for (int j = sub; j < Lb; j += 4) m = fmaxf(m, prow[j]);
-  m = fmaxf(m, __shfl_xor(m, 1, 64));
-  m = fmaxf(m, __shfl_xor(m, 2, 64));
-  m = fmaxf(m, m_run);
-  const float alpha = __expf(m_run - m);                    // first window: exp(-inf) = 0 against l = 0 and O = 0
-  float sum = 0.f;
-  for (int j = sub; j < Lb; j += 4) {
-    const float e = __expf(prow[j] - m);
-    if (kWriteP) prow[j] = e;
-    sum += e;
-  }
-  sum += __shfl_xor(sum, 1, 64);
-  sum += __shfl_xor(sum, 2, 64);
-  if (kWriteP) {
-    const int Lp = (Lb + 31) & ~31;
-    for (int j = Lb + sub; j < Lp; j += 4) prow[j] = 0.f;
-  }
-  l_run = l_run * alpha + sum;
-  m_run = m;
-  return alpha;
-}
 
 template <int NCP>
 __global__ __launch_bounds__(256) void attn_stream_kernel(const float* __restrict__ qkv, float* __restrict__ dst,
@@ -940,65 +888,11 @@ __global__ __launch_bounds__(256) void attn_stream_stats_kernel(const float* __r
     __syncthreads();
     online_softmax<false>(Ps, Lb, m_run, l_run);
   }
-  const int row = tid >> 2, sub = tid & 3;
-  float d = 0.f;
-  if (row < valid) {
-    const float* po = o + ((size_t)n * L + q0 + row) * C;
-    const float* pd = d_o + ((size_t)n * L + q0 + row) * C;
-    for (int c = sub * 4; c < C; c += 16) {
-      const float4 a = *reinterpret_cast<const float4*>(po + c);
-      const float4 b = *reinterpret_cast<const float4*>(pd + c);
-      d += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
-    }
-  }
-  d += __shfl_xor(d, 1, 64);
-  d += __shfl_xor(d, 2, 64);
-  if (sub == 0 && row < valid) {
+  const float d = row_dot(o, d_o, (size_t)n * L + q0, C, valid);
+  const int row = tid >> 2;
+  if ((tid & 3) == 0 && row < valid) {
     float* st = stats + ((size_t)n * L + q0 + row) * 4;
     st[0] = m_run; st[1] = l_run; st[2] = d; st[3] = 0.f;
-  }
-}
-
-// tile[row][col] = exp(scale * acc - m) / l over the wave's 64 columns; zero for rows >= rows_valid and columns >= cols_valid.
-// kRowStats: m, l belong to the tile's ROWS (dQ: St[row], St[kKB + row]), else to its COLUMNS (dK / dV)
-template <bool kRowStats>
-__device__ __forceinline__ void acc_to_probs(const f32x16 (&acc)[2][2], float* Ps, const float* St, int Lk, int rows_valid, int cols_valid,
-                                             float scale) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int li = lane & 31, lh = lane >> 5, kb = wave * 64;
-  if (kb < Lk) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const int col = kb + b * 32 + li;
-          const int s = kRowStats ? row : col;
-          float pv = 0.f;
-          if (row < rows_valid && col < cols_valid) pv = __expf(acc[a][b][r] * scale - St[s]) / St[kKB + s];
-          Ps[row * kLDP + col] = pv;
-        }
-  }
-}
-
-// tile[row][col] *= acc - D over the wave's 64 columns (columns < Lp)
-template <bool kRowStats>
-__device__ __forceinline__ void probs_to_ds(const f32x16 (&acc)[2][2], float* Ps, const float* St, int Lk, int Lp) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int li = lane & 31, lh = lane >> 5, kb = wave * 64;
-  if (kb < Lk) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const int col = kb + b * 32 + li;
-          if (col < Lp) Ps[row * kLDP + col] *= (acc[a][b][r] - St[2 * kKB + (kRowStats ? row : col)]);
-        }
   }
 }
 
@@ -1017,11 +911,7 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_q_kernel(const float* __r
   const int C3 = 3 * C;
   const float* base = qkv + (size_t)n * L * C3;
   const int valid = L - q0;
-  if (tid < kQB) {
-    float m = 0.f, l = 1.f, d = 0.f;
-    if (tid < valid) { const float* st = stats + ((size_t)n * L + q0 + tid) * 4; m = st[0]; l = st[1]; d = st[2]; }
-    St[tid] = m; St[kKB + tid] = l; St[2 * kKB + tid] = d;
-  }
+  if (tid < kQB) load_stats(St, stats, (size_t)n * L + q0, valid);
   f32x16 dq[NCP][2][2];
 #pragma unroll
   for (int p = 0; p < NCP; ++p) zero_acc(dq[p]);
@@ -1056,7 +946,7 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_kv_kernel(const float* __
   float* Ks = Qs + kQB * kLDC;
   float* Vs = Qs;
   float* St = smem + kTileFloats + kStageFloats;   // [3][256]: m, l, D of the window's queries
-  const int n = blockIdx.y, k0 = blockIdx.x * kQB, tid = threadIdx.x;
+  const int n = blockIdx.y, k0 = blockIdx.x * kQB;
   const int cp = blockIdx.z * 256, Cw = min(256, C - cp);
   const int C3 = 3 * C;
   const float* base = qkv + (size_t)n * L * C3;
@@ -1069,11 +959,7 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_kv_kernel(const float* __
     const int Lb = min(kKB, L - qb0);
     const int Lk = (Lb + 63) & ~63, Lp = (Lb + 31) & ~31;
     __syncthreads();                      // the previous window's readers of St and of the tile are done
-    {
-      float m = 0.f, l = 1.f, d = 0.f;
-      if (tid < Lb) { const float* st = stats + ((size_t)n * L + qb0 + tid) * 4; m = st[0]; l = st[1]; d = st[2]; }
-      St[tid] = m; St[kKB + tid] = l; St[2 * kKB + tid] = d;
-    }
+    load_stats(St, stats, (size_t)n * L + qb0, Lb);
     f32x16 acc[2][2];
     // S^T = K_tile Q_blk^T
     gemm_nt(base + (size_t)k0 * C3 + C, valid, C3, base + (size_t)qb0 * C3, Lb, C3, C, Lk, Qs, Ks, acc);
@@ -1093,12 +979,23 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_kv_kernel(const float* __
   store_acc(dk, out + C, C3, valid, cp, C, scale);
 }
 
-template <typename K>
-int set_lds_once(K kfn, int bytes, std::atomic<bool>* done) {   // idempotent: a lost race only sets the attribute twice
+// Launch of a kernel whose dynamic LDS exceeds the default limit.  The limit is raised at the first launch of each instantiation
+// (one flag each), which the engines make outside any stream capture; idempotent: a lost race only sets the attribute twice.
+template <typename K, typename... Args>
+int launch_lds(K kfn, std::atomic<bool>* done, dim3 grid, dim3 block, int bytes, hipStream_t stream, Args... args) {
   if (!*done) {
     SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     *done = true;
   }
+  hipLaunchKernelGGL(kfn, grid, block, bytes, stream, args...);
+  SSDE_LAUNCH_CHECK();
+  return SSDE_OK;
+}
+
+// what both entry points ask of a launch's sizes
+int check_shape(const char* what, int n, int l, int c) {
+  SSDE_REQUIRE(n > 0 && l > 0 && l <= SSDE_ATTN_L_MAX, "%s: token count %d outside 1..%d", what, l, SSDE_ATTN_L_MAX);
+  SSDE_REQUIRE(c > 0 && c % 32 == 0, "%s: channels must be a multiple of 32 (got %d)", what, c);
   return SSDE_OK;
 }
 
@@ -1107,8 +1004,7 @@ int set_lds_once(K kfn, int bytes, std::atomic<bool>* done) {   // idempotent: a
 // The route of a forward launch (the plan query ssde_attention_route): no device access
 static int attn_route(const ssde_attn_args* a) {
   SSDE_REQUIRE(a, "attention: null args");
-  SSDE_REQUIRE(a->n > 0 && a->l > 0 && a->l <= SSDE_ATTN_L_MAX, "attention: token count %d outside 1..%d", a->l, SSDE_ATTN_L_MAX);
-  SSDE_REQUIRE(a->c > 0 && a->c % 32 == 0, "attention: channels must be a multiple of 32 (got %d)", a->c);
+  if (int rc = check_shape("attention", a->n, a->l, a->c)) return rc;
   if (a->l > kLMax || (a->flags & SSDE_ATTNF_STREAM)) {
     SSDE_REQUIRE(a->c <= kStreamCMax, "attention: the streaming kernels (more than %d tokens, or SSDE_ATTNF_STREAM) take at most %d channels (got %d)",
                  kLMax, kStreamCMax, a->c);
@@ -1124,83 +1020,47 @@ extern "C" int ssde_attention(const ssde_attn_args* a, void* stream) {
   SSDE_REQUIRE(a && a->qkv && a->dst, "attention: null args");
   const int route = attn_route(a);
   if (route < 0) return route;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(ssde_cdiv(a->l, kQB), a->n);
   if (route == SSDE_ATTN_ROUTE_STREAM) {
-    const int lds = kStreamLdsFloats * 4;
-    static std::atomic<bool> stream_set[2];   // set once, outside any stream capture
-    const dim3 grid(ssde_cdiv(a->l, kQB), a->n);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a->c <= 256) {
-      if (int rc = set_lds_once(attn_stream_kernel<1>, lds, &stream_set[0])) return rc;
-      hipLaunchKernelGGL(attn_stream_kernel<1>, grid, dim3(256), lds, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
-    } else {
-      if (int rc = set_lds_once(attn_stream_kernel<2>, lds, &stream_set[1])) return rc;
-      hipLaunchKernelGGL(attn_stream_kernel<2>, grid, dim3(256), lds, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
-    }
-    SSDE_LAUNCH_CHECK();
-    return SSDE_OK;
+    static std::atomic<bool> set[2];
+    if (a->c <= 256) return launch_lds(attn_stream_kernel<1>, &set[0], grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
+    return launch_lds(attn_stream_kernel<2>, &set[1], grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
   }
   if (route == SSDE_ATTN_ROUTE_X6) {
-    static std::atomic<bool> x6_set[4];
-    const dim3 grid(ssde_cdiv(a->n, 8) * 8 * 4);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define SSDE_ATTN_X6_GO(NST, SLOT)                                                                       \
-    do {                                                                                                 \
-      if (int rc = set_lds_once(attn_x6_kernel<NST>, x6::kLds, &x6_set[SLOT])) return rc;                \
-      hipLaunchKernelGGL(attn_x6_kernel<NST>, grid, dim3(x6::kT), x6::kLds, st, a->qkv, a->dst, a->n, a->scale); \
-    } while (0)
+    static std::atomic<bool> set[4];
+    const dim3 grid_x6(ssde_cdiv(a->n, 8) * 8 * 4);
     switch (a->c) {
-      case 64: SSDE_ATTN_X6_GO(4, 0); break;
-      case 128: SSDE_ATTN_X6_GO(8, 1); break;
-      case 192: SSDE_ATTN_X6_GO(12, 2); break;
-      default: SSDE_ATTN_X6_GO(16, 3); break;
+      case 64: return launch_lds(attn_x6_kernel<4>, &set[0], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
+      case 128: return launch_lds(attn_x6_kernel<8>, &set[1], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
+      case 192: return launch_lds(attn_x6_kernel<12>, &set[2], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
+      default: return launch_lds(attn_x6_kernel<16>, &set[3], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
     }
-#undef SSDE_ATTN_X6_GO
-    SSDE_LAUNCH_CHECK();
-    return SSDE_OK;
   }
-  const int lds = kAttnLdsFloats * 4;
-  static std::atomic<bool> attr_set{false};   // set once, outside any stream capture
-  if (int rc = set_lds_once(attn_kernel, lds, &attr_set)) return rc;
-  hipLaunchKernelGGL(attn_kernel, dim3(ssde_cdiv(a->l, kQB), a->n), dim3(256), lds, static_cast<hipStream_t>(stream),
-                     a->qkv, a->dst, a->n, a->l, a->c, a->scale);
-  SSDE_LAUNCH_CHECK();
-  return SSDE_OK;
+  static std::atomic<bool> set{false};
+  return launch_lds(attn_kernel, &set, grid, 256, kAttnLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
 }
 
 extern "C" int ssde_attention_bwd(const ssde_attn_bwd_args* a, void* stream) {
   SSDE_REQUIRE(a && a->qkv && a->o && a->d_o && a->dqkv && a->stats, "attention_bwd: null args");
-  SSDE_REQUIRE(a->n > 0 && a->l > 0 && a->l <= SSDE_ATTN_L_MAX, "attention_bwd: token count %d outside 1..%d", a->l, SSDE_ATTN_L_MAX);
-  SSDE_REQUIRE(a->c > 0 && a->c % 32 == 0, "attention_bwd: channels must be a multiple of 32 (got %d)", a->c);
+  if (int rc = check_shape("attention_bwd", a->n, a->l, a->c)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(ssde_cdiv(a->l, kQB), a->n);
+  const int lds = kBwdLdsFloats * 4;
   if (a->l > kLMax) {   // (no flag field: the backward routes by the token count alone)
     SSDE_REQUIRE(a->c <= kStreamCMax, "attention_bwd: the streaming kernels (more than %d tokens) take at most %d channels (got %d)", kLMax,
                  kStreamCMax, a->c);
-    const int lds_s = kStreamLdsFloats * 4, lds_b = kStreamBwdLdsFloats * 4;
     static std::atomic<bool> set_s{false}, set_sq[2], set_skv{false};
-    if (int rc = set_lds_once(attn_stream_stats_kernel, lds_s, &set_s)) return rc;
-    if (int rc = set_lds_once(attn_stream_bwd_q_kernel<1>, lds_b, &set_sq[0])) return rc;
-    if (int rc = set_lds_once(attn_stream_bwd_q_kernel<2>, lds_b, &set_sq[1])) return rc;
-    if (int rc = set_lds_once(attn_stream_bwd_kv_kernel, lds_b, &set_skv)) return rc;
-    hipLaunchKernelGGL(attn_stream_stats_kernel, grid, dim3(256), lds_s, st, a->qkv, a->o, a->d_o, a->stats, a->n, a->l, a->c, a->scale);
-    SSDE_LAUNCH_CHECK();
-    if (a->c <= 256)
-      hipLaunchKernelGGL(attn_stream_bwd_q_kernel<1>, grid, dim3(256), lds_b, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
-    else
-      hipLaunchKernelGGL(attn_stream_bwd_q_kernel<2>, grid, dim3(256), lds_b, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
-    SSDE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_stream_bwd_kv_kernel, dim3(grid.x, grid.y, ssde_cdiv(a->c, 256)), dim3(256), lds_b, st, a->qkv, a->d_o, a->dqkv,
-                       a->stats, a->n, a->l, a->c, a->scale);
-    SSDE_LAUNCH_CHECK();
-    return SSDE_OK;
+    if (int rc = launch_lds(attn_stream_stats_kernel, &set_s, grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->o, a->d_o, a->stats, a->n, a->l,
+                            a->c, a->scale))
+      return rc;
+    if (int rc = a->c <= 256 ? launch_lds(attn_stream_bwd_q_kernel<1>, &set_sq[0], grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale)
+                             : launch_lds(attn_stream_bwd_q_kernel<2>, &set_sq[1], grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale))
+      return rc;
+    return launch_lds(attn_stream_bwd_kv_kernel, &set_skv, dim3(grid.x, grid.y, ssde_cdiv(a->c, 256)), 256, lds, st, a->qkv, a->d_o, a->dqkv,
+                      a->stats, a->n, a->l, a->c, a->scale);
   }
-  const int lds = kBwdLdsFloats * 4;
   static std::atomic<bool> set_q{false}, set_kv{false};
-  if (int rc = set_lds_once(attn_bwd_q_kernel, lds, &set_q)) return rc;
-  if (int rc = set_lds_once(attn_bwd_kv_kernel, lds, &set_kv)) return rc;
-  hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(256), lds, st, a->qkv, a->o, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
-  SSDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attn_bwd_kv_kernel, grid, dim3(256), lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
-  SSDE_LAUNCH_CHECK();
-  return SSDE_OK;
+  if (int rc = launch_lds(attn_bwd_q_kernel, &set_q, grid, 256, lds, st, a->qkv, a->o, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale)) return rc;
+  return launch_lds(attn_bwd_kv_kernel, &set_kv, grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
 }
