@@ -684,14 +684,23 @@ int ssde_graph_destroy(void* graph);
 enum { SSDE_REGION_ZERO = 0,    /* activations, I/O, sampler state: zero-initialised                      */
        SSDE_REGION_CONST = 1 }; /* initial contents in the blob: packed weights, parameters, tables       */
 enum { SSDE_RELOC_OP = 0, SSDE_RELOC_REFRESH_OP = 1, SSDE_RELOC_REGION = 2 };
-enum { SSDE_PLAN_UNET = 0, SSDE_PLAN_PC = 1, SSDE_PLAN_TRAIN = 2 };
+enum { SSDE_PLAN_UNET = 0, SSDE_PLAN_PC = 1, SSDE_PLAN_TRAIN = 2,
+       SSDE_PLAN_ODE = 3,          /* probability-flow ODE sampler: one program = one drift evaluation (ode.FusedDrift) */
+       SSDE_PLAN_LIKELIHOOD = 4 }; /* likelihood ODE: one program = drift + Hutchinson divergence (ode.FusedLikelihoodRhs) */
 enum { SSDE_IO_X = 0, SSDE_IO_COND = 1, SSDE_IO_SIGMA = 2, SSDE_IO_STD = 3, SSDE_IO_OUT = 4, SSDE_IO_XMEAN = 5,
        SSDE_IO_STEP = 6, SSDE_IO_SEED = 7,
        /* training plans (losses.FusedTrainStep): clean batch, noise, per-sample mean coefficient / std / g^2, scalar loss,
         * the 12-float hyper-parameter record of ssde_adam_clip_ema, the dropout seed word, d loss / d out, d loss / d x,
         * the flat gradient and the flat parameter buffer (reference layouts, state_dict order) */
        SSDE_IO_BATCH = 8, SSDE_IO_Z = 9, SSDE_IO_A = 10, SSDE_IO_S = 11, SSDE_IO_G2 = 12, SSDE_IO_LOSS = 13, SSDE_IO_HYPER = 14,
-       SSDE_IO_DROP_SEED = 15, SSDE_IO_GOUT = 16, SSDE_IO_GX = 17, SSDE_IO_GRAD = 18, SSDE_IO_PARAMS = 19, SSDE_IO_SLOTS = 24 };
+       SSDE_IO_DROP_SEED = 15, SSDE_IO_GOUT = 16, SSDE_IO_GX = 17, SSDE_IO_GRAD = 18, SSDE_IO_PARAMS = 19,
+       /* ODE plans (SSDE_PLAN_ODE, SSDE_PLAN_LIKELIHOOD; state length N = B*C*H*W, plus B running log-density terms in a
+        * likelihood plan): the ssde_ode_dyn record; the seven fp64 slope rows K[7][N]; the solver's state block; the
+        * Hutchinson probe [B*C*H*W] fp32 (likelihood plans only).  Layout of the state block, in doubles:
+        *   [0, N) and [N, 2N) the two state buffers (they swap roles when a step is accepted), [2N, 3N) the stage argument,
+        *   [3N, 3N + SSDE_ODE_PARTIALS) the error-norm partials, [3N + SSDE_ODE_PARTIALS] the error norm */
+       SSDE_IO_ODE_DYN = 20, SSDE_IO_ODE_K = 21, SSDE_IO_ODE_STATE = 22, SSDE_IO_ODE_PROBE = 23, SSDE_IO_SLOTS = 24 };
+#define SSDE_ODE_PARTIALS 1024
 typedef struct ssde_plan_header {
   char magic[8];                /* "SSDEPLN1" */
   int32_t abi_version, sizeof_op;
@@ -753,6 +762,27 @@ int ssde_unet_backward(ssde_plan* p, const float* dout, float* dx, float* dparam
  * (e.g. SSDE_IO_PARAMS: the flat parameter buffer after training steps), 1 writes it */
 int ssde_plan_copy_io(ssde_plan* p, int32_t slot, void* buf, int64_t bytes, int32_t to_plan, void* stream);
 int ssde_pc_state(ssde_plan* p, float* x, float* x_mean, void* stream);
+/* ---- ODE plans (SSDE_PLAN_ODE / SSDE_PLAN_LIKELIHOOD, exported from ode.FusedDrift / ode.FusedLikelihoodRhs by
+ * plan_export.export_ode_plan) ----
+ * replaces scipy.integrate.solve_ivp(method='RK45') around the network as the reference's get_ode_sampler and
+ * get_likelihood_fn drive it (sampling.py:449-483, likelihood.py:69-111): the adaptive Dormand-Prince loop of ode.solve_rk45,
+ * with the exported right-hand-side program run (or replayed as one hipGraph) once per evaluation and the stage arithmetic
+ * done by the rk_combine / rk_error_norm launches.  The library holds no SDE formulas: the host's callback supplies the four
+ * floats of ssde_ode_dyn at time t -- label, the second scalar (marginal std of a VP / sub-VP model, or the sigma a
+ * scale_by_sigma VE model divides by), a and g2 -- and returns non-zero to abort the solve.  x0, probe, x, slope and
+ * delta_logp are DEVICE pointers.  After the solve the host applies what the reference does around the integration
+ * (denoising step, inverse scaler, prior log-density and the bits/dim constant). */
+typedef int (*ssde_ode_scalars_fn)(double t, void* user, float out[4]);
+/* load the initial state (x0 [B,C,H,W] fp32; the log-density terms start at 0) and, in a likelihood plan, the probe */
+int ssde_ode_reset(ssde_plan* p, const float* x0, const float* probe, void* stream);
+/* one evaluation of the right-hand side at the current state: slope receives N doubles */
+int ssde_ode_eval(ssde_plan* p, double t, ssde_ode_scalars_fn scalars, void* user, double* slope, void* stream);
+/* integrate from t0 to t1; use_graph != 0 captures the program once per plan (non-default stream, as for the PC loop);
+ * max_nfev bounds the evaluations (0 = 100000); *nfev receives the count.  The call returns with the stream idle. */
+int ssde_ode_solve(ssde_plan* p, double t0, double t1, double rtol, double atol, ssde_ode_scalars_fn scalars, void* user,
+                   int32_t use_graph, int32_t max_nfev, int32_t* nfev, void* stream);
+/* the current state: x [B,C,H,W] fp32 (or NULL), delta_logp [B] fp64 (likelihood plans; else NULL) */
+int ssde_ode_state(ssde_plan* p, float* x, double* delta_logp, void* stream);
 
 int ssde_abi_version(void);
 int ssde_sizeof_op(void);             /* lets the ctypes mirror verify its layout */

@@ -294,7 +294,8 @@ EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attent
            # plan-level entry points (csrc/plan.hip; argument types: plan_export.bind)
            "ssde_plan_load", "ssde_plan_load_file", "ssde_plan_destroy", "ssde_plan_info", "ssde_plan_param",
            "ssde_plan_refresh_weights", "ssde_unet_forward", "ssde_pc_reset", "ssde_pc_run", "ssde_pc_state",
-           "ssde_train_step", "ssde_train_forward", "ssde_unet_backward", "ssde_plan_copy_io"]
+           "ssde_train_step", "ssde_train_forward", "ssde_unet_backward", "ssde_plan_copy_io",
+           "ssde_ode_reset", "ssde_ode_eval", "ssde_ode_solve", "ssde_ode_state"]
 
 _lib = None
 

@@ -1,5 +1,5 @@
 // Plan-level C entry points: a whole lowered program (U-Net evaluation, or a predictor-corrector iteration) loaded from a
-// PLAN BLOB and driven by a host that has no Python -- SURVEY 8(b): ssde_plan_*, ssde_unet_forward, ssde_pc_*.
+// PLAN BLOB and driven by a host that has no Python -- SURVEY 8(b): ssde_plan_*, ssde_unet_forward, ssde_pc_*, ssde_ode_*.
 //
 // The reference's host is Python (NCSNpp.forward models/ncsnpp.py:232-381, pc_sampler sampling.py:390-409); its lowering
 // to kernels stays in ONE place, score_sde_pytorch_amd/engine.py + pc_engine.py.  plan_export.py serialises what that
@@ -10,6 +10,7 @@
 // program; a C / C++ / Go / Rust host needs only libssde_hip.so, the blob and (optionally) a checkpoint to copy into
 // the parameter regions followed by ssde_plan_refresh_weights.
 #include "ssde_common.h"
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
@@ -28,14 +29,22 @@ struct ssde_plan {
   std::vector<ssde_plan_param_entry> params;
   void* graph = nullptr;
   hipStream_t graph_stream = nullptr;
+  // ODE plans: which of the two state buffers holds y; host ring of per-evaluation records (ode.py: _FusedRhs._upload)
+  int ode_cur = 0;
+  ssde_ode_dyn* ode_ring = nullptr;
+  int ode_slot = 0, ode_inflight = 0;
+  hipStream_t ode_stream = nullptr;
 };
 
 namespace {
+
+void ode_ring_free(ssde_ode_dyn* ring);
 
 int fail_free(ssde_plan* p, int rc) {
   if (p) {
     for (auto& r : p->regions)
       if (r.dev) hipFree(r.dev);
+    ode_ring_free(p->ode_ring);
     delete p;
   }
   return rc;
@@ -238,6 +247,265 @@ extern "C" int ssde_pc_state(ssde_plan* p, float* x, float* x_mean, void* stream
   const size_t img = (size_t)h.batch * h.channels * h.height * h.width * sizeof(float);
   if (x) SSDE_HIP_CHECK(hipMemcpyAsync(x, region_ptr(p, h.io[SSDE_IO_X]), img, hipMemcpyDeviceToDevice, st));
   if (x_mean) SSDE_HIP_CHECK(hipMemcpyAsync(x_mean, region_ptr(p, h.io[SSDE_IO_XMEAN]), img, hipMemcpyDeviceToDevice, st));
+  return SSDE_OK;
+}
+
+// ---- ODE plans (ode.FusedDrift / ode.FusedLikelihoodRhs: one program = one right-hand-side evaluation) ----
+// The driver below is ode._initial_step + ode.solve_rk45 line for line (scipy's RK45: Dormand-Prince 5(4), FSAL, RMS error
+// norm, factor 0.9 err^-0.2 in [0.2, 10]); host arithmetic in double, one scalar read per step.  It holds no SDE formulas:
+// the four floats of the device record come from the host's callback.
+namespace {
+constexpr int kOdeRing = 32;
+const double kC[6] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0};
+const double kA[6][5] = {{0, 0, 0, 0, 0},
+                         {1.0 / 5, 0, 0, 0, 0},
+                         {3.0 / 40, 9.0 / 40, 0, 0, 0},
+                         {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
+                         {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
+                         {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
+const double kB[6] = {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
+const double kE[7] = {-71.0 / 57600, 0.0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+constexpr double kSafety = 0.9, kMinFactor = 0.2, kMaxFactor = 10.0;
+
+// The pinned ring: the six evaluations of a step are enqueued without a host wait, so the record of an evaluation must
+// not be overwritten before its upload has executed.  (The test emulator executes every copy at the call.)
+ssde_ode_dyn* ode_ring_alloc() {
+#ifdef SSDE_EMULATED
+  return static_cast<ssde_ode_dyn*>(malloc(kOdeRing * sizeof(ssde_ode_dyn)));
+#else
+  void* q = nullptr;
+  return hipHostMalloc(&q, kOdeRing * sizeof(ssde_ode_dyn), hipHostMallocDefault) == hipSuccess ? static_cast<ssde_ode_dyn*>(q) : nullptr;
+#endif
+}
+void ode_ring_free(ssde_ode_dyn* ring) {
+  if (!ring) return;
+#ifdef SSDE_EMULATED
+  free(ring);
+#else
+  (void)hipHostFree(ring);
+#endif
+}
+
+struct Ode {                       // the regions of an ODE plan, bounds checked
+  int64_t n = 0, N = 0;            // image elements; state length (n, or n + B)
+  double *K = nullptr, *y[2] = {nullptr, nullptr}, *y_stage = nullptr, *partial = nullptr, *out = nullptr;
+  float* x32 = nullptr;            // the U-Net program's input
+  ssde_ode_dyn* dyn = nullptr;
+};
+
+int ode_view(const ssde_plan* p, Ode* o, const char* who) {
+  SSDE_REQUIRE(p && (p->hdr.kind == SSDE_PLAN_ODE || p->hdr.kind == SSDE_PLAN_LIKELIHOOD), "%s: not an ODE plan", who);
+  const ssde_plan_header& h = p->hdr;
+  o->n = (int64_t)h.batch * h.channels * h.height * h.width;
+  o->N = o->n + (h.kind == SSDE_PLAN_LIKELIHOOD ? h.batch : 0);
+  auto bytes = [&](int slot) { const int id = h.io[slot]; return (id >= 0 && id < (int)p->regions.size()) ? p->regions[id].bytes : (int64_t)0; };
+  SSDE_REQUIRE(o->n > 0 && bytes(SSDE_IO_X) >= o->n * (int64_t)sizeof(float) && bytes(SSDE_IO_ODE_DYN) >= (int64_t)sizeof(ssde_ode_dyn) &&
+                   bytes(SSDE_IO_ODE_K) >= 7 * o->N * (int64_t)sizeof(double) &&
+                   bytes(SSDE_IO_ODE_STATE) >= (3 * o->N + SSDE_ODE_PARTIALS + 1) * (int64_t)sizeof(double),
+               "%s: the plan's solver regions are missing or too small", who);
+  if (h.kind == SSDE_PLAN_LIKELIHOOD)
+    SSDE_REQUIRE(bytes(SSDE_IO_ODE_PROBE) >= o->n * (int64_t)sizeof(float) && bytes(SSDE_IO_GOUT) >= o->n * (int64_t)sizeof(float),
+                 "%s: the likelihood plan has no probe / cotangent region", who);
+  o->x32 = static_cast<float*>(region_ptr(p, h.io[SSDE_IO_X]));
+  o->dyn = static_cast<ssde_ode_dyn*>(region_ptr(p, h.io[SSDE_IO_ODE_DYN]));
+  o->K = static_cast<double*>(region_ptr(p, h.io[SSDE_IO_ODE_K]));
+  double* s = static_cast<double*>(region_ptr(p, h.io[SSDE_IO_ODE_STATE]));
+  o->y[0] = s; o->y[1] = s + o->N; o->y_stage = s + 2 * o->N; o->partial = s + 3 * o->N; o->out = o->partial + SSDE_ODE_PARTIALS;
+  return SSDE_OK;
+}
+
+// dst = y + sum_j coef[j] K[j], and its fp32 copy into the U-Net input (the log-density tail of a likelihood state stays fp64)
+int ode_combine(const Ode& o, const double* y, const double* coef, int n_coef, double* dst, void* stream) {
+  ssde_rk_combine_args a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < n_coef; ++j) {
+    a.coef.v[j] = coef[j];
+    if (coef[j] != 0.0) a.terms = j + 1;
+  }
+  a.y = y; a.k = o.K; a.n = o.N; a.dst = dst; a.dst32 = o.x32; a.n32 = o.n;
+  return ssde_rk_combine(&a, stream);
+}
+
+// scipy's RMS norm of sum_j coef[j] K[j] over atol + max(|y|, |y_new|) rtol: the one host read of a step
+int ode_norm(ssde_plan* p, const Ode& o, const double* y, const double* y_new, const double* coef7, double atol, double rtol, double* value,
+             hipStream_t st) {
+  ssde_rk_error_args a;
+  memset(&a, 0, sizeof(a));
+  a.y = y; a.y_new = y_new; a.k = o.K; a.n = o.N; a.atol = atol; a.rtol = rtol;
+  a.partial = o.partial; a.partial_len = SSDE_ODE_PARTIALS; a.out = o.out;
+  for (int j = 0; j < 7; ++j) a.coef.v[j] = coef7[j];
+  if (int rc = ssde_rk_error_norm(&a, st)) return rc;
+  SSDE_HIP_CHECK(hipMemcpyAsync(value, o.out, sizeof(double), hipMemcpyDeviceToHost, st));
+  SSDE_HIP_CHECK(hipStreamSynchronize(st));
+  p->ode_inflight = 0;
+  return SSDE_OK;
+}
+
+// upload the record of one evaluation (the callback's four floats and the slope row to fill), then run the program
+int ode_evaluate(ssde_plan* p, const Ode& o, double t, ssde_ode_scalars_fn scalars, void* user, double* dst, int use_graph, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  const int cb = scalars(t, user, v);
+  SSDE_REQUIRE(cb == 0, "ode: the scalars callback returned %d at t = %.17g", cb, t);
+  if (!p->ode_ring) {
+    p->ode_ring = ode_ring_alloc();
+    SSDE_REQUIRE(p->ode_ring, "ode: allocating the host record ring failed");
+  }
+  if (p->ode_inflight > 0 && (p->ode_stream != st || p->ode_inflight >= kOdeRing)) {
+    SSDE_HIP_CHECK(hipStreamSynchronize(p->ode_stream));
+    p->ode_inflight = 0;
+  }
+  p->ode_stream = st;
+  ssde_ode_dyn& r = p->ode_ring[p->ode_slot];
+  p->ode_slot = (p->ode_slot + 1) % kOdeRing;
+  p->ode_inflight++;
+  r.label = v[0]; r.std = v[1]; r.a = v[2]; r.g2 = v[3]; r.dst = dst;
+  SSDE_HIP_CHECK(hipMemcpyAsync(o.dyn, &r, sizeof(r), hipMemcpyHostToDevice, st));
+  if (!use_graph) return ssde_program_run(p->ops.data(), (int)p->ops.size(), stream);
+  if (!p->graph || p->graph_stream != st) {
+    if (p->graph) { ssde_graph_destroy(p->graph); p->graph = nullptr; }
+    if (int rc = ssde_graph_capture(p->ops.data(), (int)p->ops.size(), stream, &p->graph)) return rc;
+    p->graph_stream = st;
+  }
+  return ssde_graph_launch(p->graph, stream);
+}
+}  // namespace
+
+extern "C" int ssde_ode_reset(ssde_plan* p, const float* x0, const float* probe, void* stream) {
+  Ode o;
+  if (int rc = ode_view(p, &o, "ode_reset")) return rc;
+  SSDE_REQUIRE(x0, "ode_reset: null x0");
+  const bool lik = p->hdr.kind == SSDE_PLAN_LIKELIHOOD;
+  SSDE_REQUIRE(lik || !probe, "ode_reset: a sampler plan takes no probe");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // y = (double)x0 (exact), log-density terms 0: widened on the host, once per solve
+  std::vector<float> x((size_t)o.n);
+  std::vector<double> y((size_t)o.N, 0.0);
+  SSDE_HIP_CHECK(hipMemcpyAsync(x.data(), x0, (size_t)o.n * sizeof(float), hipMemcpyDeviceToHost, st));
+  SSDE_HIP_CHECK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < o.n; ++i) y[(size_t)i] = (double)x[(size_t)i];
+  p->ode_cur = 0;
+  SSDE_HIP_CHECK(hipMemcpyAsync(o.y[0], y.data(), (size_t)o.N * sizeof(double), hipMemcpyHostToDevice, st));
+  if (probe) {      // fixed for the whole solve (likelihood.py:76-81); it is also the cotangent of the input-gradient program
+    if (int rc = copy_in(p, SSDE_IO_ODE_PROBE, probe, (size_t)o.n * sizeof(float), st)) return rc;
+    if (int rc = copy_in(p, SSDE_IO_GOUT, probe, (size_t)o.n * sizeof(float), st)) return rc;
+  }
+  SSDE_HIP_CHECK(hipStreamSynchronize(st));                           // `y` is this frame's
+  return SSDE_OK;
+}
+
+extern "C" int ssde_ode_eval(ssde_plan* p, double t, ssde_ode_scalars_fn scalars, void* user, double* slope, void* stream) {
+  Ode o;
+  if (int rc = ode_view(p, &o, "ode_eval")) return rc;
+  SSDE_REQUIRE(scalars && slope, "ode_eval: null callback / slope");
+  if (int rc = ode_combine(o, o.y[p->ode_cur], nullptr, 0, o.y_stage, stream)) return rc;
+  return ode_evaluate(p, o, t, scalars, user, slope, 0, stream);
+}
+
+extern "C" int ssde_ode_solve(ssde_plan* p, double t0, double t1, double rtol, double atol, ssde_ode_scalars_fn scalars, void* user,
+                              int32_t use_graph, int32_t max_nfev, int32_t* nfev_out, void* stream) {
+  Ode o;
+  if (int rc = ode_view(p, &o, "ode_solve")) return rc;
+  SSDE_REQUIRE(scalars, "ode_solve: null scalars callback");
+  SSDE_REQUIRE(t0 != t1 && isfinite(t0) && isfinite(t1), "ode_solve: t0 == t1 (or a non-finite time)");
+  SSDE_REQUIRE(rtol > 0 && atol > 0 && max_nfev >= 0, "ode_solve: rtol, atol must be positive and max_nfev >= 0");
+  SSDE_REQUIRE(!use_graph || stream, "ode_solve: graph replay needs a non-default stream");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int limit = max_nfev > 0 ? max_nfev : 100000;
+  int nfev = 0;
+  if (nfev_out) *nfev_out = 0;
+  double t = t0;
+  const double t_bound = t1, direction = t_bound >= t ? 1.0 : -1.0;
+  const size_t row = (size_t)o.N * sizeof(double);
+  double* y = o.y[p->ode_cur];
+  double* y_new = o.y[p->ode_cur ^ 1];
+  auto K = [&](int j) { return o.K + (size_t)j * o.N; };
+  SSDE_REQUIRE(limit >= 2, "ode_solve: max_nfev = %d reached after 0 evaluations", limit);
+  SSDE_HIP_CHECK(hipMemsetAsync(o.K, 0, 7 * row, st));               // the norms read all seven rows (unused ones times 0)
+  if (int rc = ode_combine(o, y, nullptr, 0, o.y_stage, stream)) return rc;   // stage argument of the first evaluation (and its fp32 copy)
+  if (int rc = ode_evaluate(p, o, t, scalars, user, K(0), use_graph, stream)) return rc;
+  nfev = 1;
+  // ---- ode._initial_step (scipy's select_initial_step, order 4); with y_new = y the scale is atol + |y0| rtol
+  double h_abs;
+  {
+    double c[7] = {0, 0, 0, 0, 0, 0, 0}, d0, d1, d2;
+    SSDE_HIP_CHECK(hipMemcpyAsync(K(2), y, row, hipMemcpyDeviceToDevice, st));
+    c[2] = 1.0;
+    if (int rc = ode_norm(p, o, y, y, c, atol, rtol, &d0, st)) return rc;
+    c[2] = 0.0; c[0] = 1.0;
+    if (int rc = ode_norm(p, o, y, y, c, atol, rtol, &d1, st)) return rc;
+    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    const double step[1] = {h0 * direction};
+    if (int rc = ode_combine(o, y, step, 1, o.y_stage, stream)) return rc;
+    if (int rc = ode_evaluate(p, o, t + h0 * direction, scalars, user, K(1), use_graph, stream)) return rc;
+    c[0] = -1.0; c[1] = 1.0;
+    if (int rc = ode_norm(p, o, y, y, c, atol, rtol, &d2, st)) return rc;
+    d2 /= h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
+    h_abs = fmin(100 * h0, h1);
+    SSDE_REQUIRE(isfinite(h_abs), "ode_solve: the initial step is not finite (d0 %g, d1 %g, d2 %g)", d0, d1, d2);
+  }
+  nfev += 1;
+  if (nfev_out) *nfev_out = nfev;
+  while (direction * (t - t_bound) < 0) {
+    const double min_step = 10 * fabs(nextafter(t, direction * INFINITY) - t);
+    h_abs = fmax(h_abs, min_step);
+    bool rejected = false;
+    double t_new;
+    for (;;) {
+      SSDE_REQUIRE(!(h_abs < min_step), "ode_solve: step size underflow at t = %.17g (scipy: 'Required step size is less than spacing between numbers.')", t);
+      SSDE_REQUIRE(nfev + 6 <= limit, "ode_solve: max_nfev = %d reached at t = %.17g after %d evaluations", limit, t, nfev);
+      double h = h_abs * direction;
+      t_new = t + h;
+      if (direction * (t_new - t_bound) > 0) t_new = t_bound;
+      h = t_new - t;
+      h_abs = fabs(h);
+      double c[7];
+      for (int s = 1; s < 6; ++s) {
+        for (int j = 0; j < s; ++j) c[j] = kA[s][j] * h;
+        if (int rc = ode_combine(o, y, c, s, o.y_stage, stream)) return rc;
+        if (int rc = ode_evaluate(p, o, t + kC[s] * h, scalars, user, K(s), use_graph, stream)) return rc;
+      }
+      for (int j = 0; j < 6; ++j) c[j] = kB[j] * h;
+      if (int rc = ode_combine(o, y, c, 6, y_new, stream)) return rc;          // (its fp32 copy feeds the seventh evaluation)
+      if (int rc = ode_evaluate(p, o, t + h, scalars, user, K(6), use_graph, stream)) return rc;
+      nfev += 6;
+      if (nfev_out) *nfev_out = nfev;
+      for (int j = 0; j < 7; ++j) c[j] = kE[j] * h;
+      double err;
+      if (int rc = ode_norm(p, o, y, y_new, c, atol, rtol, &err, st)) return rc;
+      SSDE_REQUIRE(isfinite(err), "ode_solve: the error norm is not finite at t = %.17g (step %g)", t, h);
+      if (err < 1) {
+        double factor = err == 0 ? kMaxFactor : fmin(kMaxFactor, kSafety * pow(err, -0.2));
+        if (rejected) factor = fmin(1.0, factor);
+        h_abs *= factor;
+        break;
+      }
+      h_abs *= fmax(kMinFactor, kSafety * pow(err, -0.2));
+      rejected = true;
+    }
+    t = t_new;
+    p->ode_cur ^= 1;                                                   // accept: swap buffers
+    y = o.y[p->ode_cur];
+    y_new = o.y[p->ode_cur ^ 1];
+    SSDE_HIP_CHECK(hipMemcpyAsync(K(0), K(6), row, hipMemcpyDeviceToDevice, st));   // FSAL: the last slope is the next step's first
+  }
+  SSDE_HIP_CHECK(hipStreamSynchronize(st));
+  p->ode_inflight = 0;
+  return SSDE_OK;
+}
+
+extern "C" int ssde_ode_state(ssde_plan* p, float* x, double* delta_logp, void* stream) {
+  Ode o;
+  if (int rc = ode_view(p, &o, "ode_state")) return rc;
+  SSDE_REQUIRE(p->hdr.kind == SSDE_PLAN_LIKELIHOOD || !delta_logp, "ode_state: a sampler plan has no log-density terms");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const double* y = o.y[p->ode_cur];
+  if (x) {          // the fp32 rounding of the state, formed by the combine launch in the U-Net's input buffer
+    if (int rc = ode_combine(o, y, nullptr, 0, o.y_stage, stream)) return rc;
+    SSDE_HIP_CHECK(hipMemcpyAsync(x, o.x32, (size_t)o.n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  if (delta_logp) SSDE_HIP_CHECK(hipMemcpyAsync(delta_logp, y + o.n, (size_t)p->hdr.batch * sizeof(double), hipMemcpyDeviceToDevice, st));
   return SSDE_OK;
 }
 

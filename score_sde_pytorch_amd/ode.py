@@ -360,6 +360,13 @@ class FusedLikelihoodRhs(_FusedRhs):
         self.unet.gout.tensor[: self.n].copy_(self.eps)
 
 
+def scalars_fn(rhs):
+    """t -> (label, second, a, g2): the four floats a fused right-hand side uploads for an evaluation at t, as a callable.
+    A C-ABI solve of the plan exported from `rhs` (plan_export.LoadedPlan.ode_solve) driven with it sees the very floats
+    the Python solve uploads."""
+    return rhs._scalars
+
+
 def solve_host(fun, t_span, y0, rtol=1e-5, atol=1e-5, method="RK45"):
     """The reference's integrator, scipy.integrate.solve_ivp on the host, around the same tensor right-hand side as
     solve_rk45: `fun(t, y)` takes / returns an fp64 tensor on y0's device; every evaluation crosses to numpy and back

@@ -1,5 +1,6 @@
 """Serialise a lowered program as a position-independent PLAN BLOB for hosts without Python (include/ssde.h, "plans";
-loader and runner: csrc/plan.hip -> ssde_plan_load, ssde_unet_forward, ssde_pc_reset / ssde_pc_run / ssde_pc_state).
+loader and runner: csrc/plan.hip -> ssde_plan_load, ssde_unet_forward, ssde_pc_reset / ssde_pc_run / ssde_pc_state,
+ssde_ode_reset / ssde_ode_eval / ssde_ode_solve / ssde_ode_state).
 
 The lowering of NCSNpp.forward (reference models/ncsnpp.py:232-381) and of the predictor-corrector loop body
 (sampling.py:403-407) exists once, in engine.py / pc_engine.py.  This module walks what that lowering produced:
@@ -25,10 +26,12 @@ from . import _lib as L
 MAGIC = b"SSDEPLN1"
 REGION_ZERO, REGION_CONST = 0, 1
 RELOC_OP, RELOC_REFRESH_OP, RELOC_REGION = 0, 1, 2
-PLAN_UNET, PLAN_PC, PLAN_TRAIN = 0, 1, 2
+PLAN_UNET, PLAN_PC, PLAN_TRAIN, PLAN_ODE, PLAN_LIKELIHOOD = 0, 1, 2, 3, 4
 IO_X, IO_COND, IO_SIGMA, IO_STD, IO_OUT, IO_XMEAN, IO_STEP, IO_SEED = range(8)
 (IO_BATCH, IO_Z, IO_A, IO_S, IO_G2, IO_LOSS, IO_HYPER, IO_DROP_SEED, IO_GOUT, IO_GX, IO_GRAD, IO_PARAMS) = range(8, 20)
+IO_ODE_DYN, IO_ODE_K, IO_ODE_STATE, IO_ODE_PROBE = range(20, 24)
 IO_SLOTS = 24
+ODE_PARTIALS = 1024                      # include/ssde.h: SSDE_ODE_PARTIALS
 
 
 class PlanHeader(C.Structure):
@@ -299,6 +302,41 @@ def export_train_plan(fs, optimizer=None, ema=None):
                  seg=(seg0, seg1, seg2, seg3), n_flat=fs.flat.numel)
 
 
+def export_ode_plan(rhs):
+    """ode.FusedDrift / ode.FusedLikelihoodRhs -> blob for ssde_ode_reset / ssde_ode_eval / ssde_ode_solve / ssde_ode_state
+    (one program = one evaluation of the right-hand side, its scalars read from the `dyn` record).
+
+    Besides the U-Net's regions the blob names the solver state as zero regions: the record, the seven fp64 slope rows, and
+    one block holding y, y_new, the stage argument and the error-norm partials and result (offsets: include/ssde.h,
+    SSDE_IO_ODE_STATE).  State length: B*C*H*W for the sampler, plus B log-density terms for the likelihood, whose plan also
+    carries the probe (set per solve by ssde_ode_reset, which copies it into the cotangent buffer too)."""
+    from . import ode
+    if not isinstance(rhs, (ode.FusedDrift, ode.FusedLikelihoodRhs)):
+        raise TypeError("export_ode_plan: expected an ode.FusedDrift or an ode.FusedLikelihoodRhs, got %s" % type(rhs).__name__)
+    eng = rhs.unet
+    eng.weights.refresh()
+    lik = isinstance(rhs, ode.FusedLikelihoodRhs)
+    B, Cc, H, W = rhs.shape
+    n_state = rhs.n + (B if lik else 0)
+    regions = _Regions()
+    _collect_unet(regions, eng)
+    slopes = torch.zeros(7 * n_state, dtype=torch.float64, device=rhs.dyn.device)
+    state = torch.zeros(3 * n_state + ODE_PARTIALS + 1, dtype=torch.float64, device=rhs.dyn.device)
+    regions.add(rhs.dyn, REGION_ZERO, "ode_dyn")
+    regions.add(slopes, REGION_ZERO, "ode_slopes")
+    regions.add(state, REGION_ZERO, "ode_state")
+    io = {IO_X: eng.x_in.tensor, IO_COND: eng.cond.tensor, IO_OUT: eng.out.tensor, IO_ODE_DYN: rhs.dyn, IO_ODE_K: slopes,
+          IO_ODE_STATE: state}
+    if eng.sig is not eng.cond:
+        io[IO_SIGMA] = eng.sig.tensor
+    if eng.std is not None:
+        io[IO_STD] = eng.std.tensor
+    if lik:
+        regions.add(rhs.eps, REGION_ZERO, "ode_probe")
+        io.update({IO_ODE_PROBE: rhs.eps, IO_GOUT: eng.gout.tensor, IO_GX: eng.gx.tensor})
+    return _emit(PLAN_LIKELIHOOD if lik else PLAN_ODE, regions, rhs.program.ops, rhs.program.n, eng, eng.model, io, B, (Cc, H, W), 1, 0)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # ctypes binding of the plan entry points (what a C host calls; used by the tests and by tools)
 def bind(lib):
@@ -316,7 +354,34 @@ def bind(lib):
     lib.ssde_train_forward.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_void_p]
     lib.ssde_unet_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ssde_plan_copy_io.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.ssde_ode_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ssde_ode_eval.argtypes = [C.c_void_p, C.c_double, ODE_SCALARS_FN, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ssde_ode_solve.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, ODE_SCALARS_FN, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.POINTER(C.c_int32), C.c_void_p]
+    lib.ssde_ode_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
+
+
+# include/ssde.h: ssde_ode_scalars_fn -- (t, user, out[4]) -> 0, or non-zero to abort the solve
+ODE_SCALARS_FN = C.CFUNCTYPE(C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_float))
+
+
+def _ode_callback(scalars):
+    """A Python callable t -> (label, second, a, g2) as an ssde_ode_scalars_fn; an exception aborts the solve (return 1)
+    and is kept in `.error` of the returned object for the caller to re-raise."""
+    def thunk(t, _user, out):
+        try:
+            v = scalars(t)
+            for i in range(4):
+                out[i] = v[i]
+            return 0
+        except Exception as e:      # noqa: BLE001  (must not propagate through the C frames)
+            thunk.error = e
+            return 1
+    thunk.error = None
+    fn = ODE_SCALARS_FN(thunk)
+    fn.thunk = thunk
+    return fn
 
 
 class LoadedPlan:
@@ -366,6 +431,49 @@ class LoadedPlan:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
         L.check(self.lib.ssde_unet_backward(self.handle, p(dout), p(dx), p(dparams), C.c_void_p(stream or 0)), "ssde_unet_backward")
         return dx, dparams
+
+    def _ode_call(self, what, fn, rc):
+        err, fn.thunk.error = fn.thunk.error, None
+        if err is not None:
+            raise err
+        L.check(rc, what)
+
+    def ode_reset(self, x0, probe=None, stream=None):
+        """load the initial state (and the probe of a likelihood plan); x0 / probe: fp32 tensors on the plan's device"""
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        x0 = x0.contiguous()
+        probe = probe.contiguous() if probe is not None else None
+        L.check(self.lib.ssde_ode_reset(self.handle, p(x0), p(probe), C.c_void_p(stream or 0)), "ssde_ode_reset")
+
+    def ode_state_len(self):
+        h = self.header
+        return h.batch * h.channels * h.height * h.width + (h.batch if h.kind == PLAN_LIKELIHOOD else 0)
+
+    def ode_eval(self, t, scalars, like, stream=None):
+        """the right-hand side at the current state and time t: fp64 tensor [n] (sampler) or [n + B] (likelihood) on like's device"""
+        out = torch.empty(self.ode_state_len(), dtype=torch.float64, device=like.device)
+        fn = _ode_callback(scalars)
+        rc = self.lib.ssde_ode_eval(self.handle, float(t), fn, None, C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0))
+        self._ode_call("ssde_ode_eval", fn, rc)
+        return out
+
+    def ode_solve(self, t0, t1, rtol, atol, scalars, use_graph=False, max_nfev=0, stream=None):
+        """integrate the plan's state from t0 to t1 (adaptive RK45 in the library); `scalars`: t -> (label, second, a, g2), e.g.
+        ode.scalars_fn(rhs).  Returns the number of evaluations."""
+        nfev = C.c_int32(0)
+        fn = _ode_callback(scalars)
+        rc = self.lib.ssde_ode_solve(self.handle, float(t0), float(t1), float(rtol), float(atol), fn, None, int(bool(use_graph)),
+                                     int(max_nfev), C.byref(nfev), C.c_void_p(stream or 0))
+        self._ode_call("ssde_ode_solve", fn, rc)
+        return int(nfev.value)
+
+    def ode_state(self, like, stream=None):
+        """(x shaped / placed like `like` in fp32, delta_logp [B] fp64 or None for a sampler plan)"""
+        x = torch.empty_like(like, dtype=torch.float32)
+        dl = torch.empty(int(self.header.batch), dtype=torch.float64, device=like.device) if self.header.kind == PLAN_LIKELIHOOD else None
+        L.check(self.lib.ssde_ode_state(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(dl.data_ptr()) if dl is not None else None,
+                                        C.c_void_p(stream or 0)), "ssde_ode_state")
+        return x, dl
 
     def read_io(self, slot, like):
         """the first like.numel() elements of an I/O region, as a tensor shaped / typed / placed like `like`"""
