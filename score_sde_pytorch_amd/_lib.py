@@ -256,31 +256,38 @@ class PackArgs(C.Structure):
     _fields_ = [("table", _fp), ("count", C.c_int32), ("kind", C.c_int32), ("max_n", C.c_int64)]
 
 
+# The ONE per-kind table: (op kind, union member of ssde_op, argument structure, exported C entry point or None).  The union's
+# fields, the kind -> member / structure maps and the argument types of the per-op entry points (bind) are all derived from it.
+OPS = [(OP_CONV, "conv", ConvArgs, "ssde_conv2d"), (OP_GN_STATS, "gn", GnStatsArgs, "ssde_groupnorm_stats"),
+       (OP_UPFIRDN, "fir", UpfirdnArgs, "ssde_upfirdn2d"), (OP_ATTN, "attn", AttnArgs, "ssde_attention"),
+       (OP_EMBED, "embed", EmbedArgs, "ssde_embed"), (OP_TO_NHWC, "to_nhwc", ToNhwcArgs, "ssde_to_nhwc"),
+       (OP_TO_NCHW, "to_nchw", ToNchwArgs, "ssde_to_nchw"), (OP_BIAS_ACT, "bias_act", BiasActArgs, "ssde_fused_bias_act"),
+       (OP_SUMSQ, "sumsq", SumsqArgs, "ssde_sumsq"), (OP_RANDN, "randn", RandnArgs, "ssde_randn"),
+       (OP_LANGEVIN, "langevin", LangevinArgs, "ssde_langevin_update"),
+       (OP_PREDICTOR, "predictor", PredictorArgs, "ssde_predictor_update"), (OP_FILL, "fill", FillArgs, "ssde_fill_from_table"),
+       (OP_STEP_INC, "step_inc", StepIncArgs, "ssde_step_inc"), (OP_WGRAD, "wgrad", WgradArgs, "ssde_conv_wgrad"),
+       (OP_COLSUM, "colsum", ColsumArgs, "ssde_colsum"), (OP_GN_BWD_REDUCE, "gn_bwd", GnBwdReduceArgs, "ssde_gn_bwd_reduce"),
+       (OP_PROLOGUE_BWD, "pro_bwd", PrologueBwdArgs, "ssde_prologue_bwd"), (OP_ATTN_BWD, "attn_bwd", AttnBwdArgs, "ssde_attention_bwd"),
+       (OP_PERTURB, "perturb", PerturbArgs, "ssde_perturb"), (OP_DSM_LOSS, "dsm_loss", DsmLossArgs, "ssde_dsm_loss"),
+       (OP_SUMSQ_FLAT, "sumsq_flat", SumsqFlatArgs, "ssde_sumsq_flat"), (OP_ADAM, "adam", AdamArgs, "ssde_adam_clip_ema"),
+       (OP_MEMSET, "memset", MemsetArgs, "ssde_memset"), (OP_AXPY, "axpy", AxpyArgs, "ssde_axpy"),
+       (OP_PACK, "pack", PackArgs, "ssde_pack_weights"), (OP_PROJECT, "project", ProjectArgs, "ssde_project_update"),
+       (OP_GN_FINALIZE, "gn_fin", GnFinalizeArgs, "ssde_gn_finalize"), (OP_PF_DRIFT, "pf_drift", PfDriftArgs, "ssde_pf_drift"),
+       (OP_HUTCH_DIV, "hutch_div", HutchDivArgs, "ssde_hutch_div"), (OP_COLSUM_FINISH, "colsum_fin", ColsumFinishArgs, "ssde_colsum_finish"),
+       (OP_GN_BWD_FINISH, "gn_bwd_fin", GnBwdFinishArgs, "ssde_gn_bwd_finish"), (OP_GN_APPLY, "gn_apply", GnApplyArgs, "ssde_gn_apply"),
+       (OP_GN_APPLY_BWD, "gn_apply_bwd", GnApplyBwdArgs, "ssde_gn_apply_bwd")]
+
+
 class _OpUnion(C.Union):
-    _fields_ = [("conv", ConvArgs), ("gn", GnStatsArgs), ("fir", UpfirdnArgs), ("attn", AttnArgs),
-                ("embed", EmbedArgs), ("to_nhwc", ToNhwcArgs), ("to_nchw", ToNchwArgs), ("bias_act", BiasActArgs),
-                ("sumsq", SumsqArgs), ("randn", RandnArgs), ("langevin", LangevinArgs), ("predictor", PredictorArgs),
-                ("fill", FillArgs), ("step_inc", StepIncArgs),
-                ("wgrad", WgradArgs), ("colsum", ColsumArgs), ("gn_bwd", GnBwdReduceArgs), ("pro_bwd", PrologueBwdArgs),
-                ("attn_bwd", AttnBwdArgs), ("perturb", PerturbArgs), ("dsm_loss", DsmLossArgs),
-                ("sumsq_flat", SumsqFlatArgs), ("adam", AdamArgs), ("memset", MemsetArgs), ("axpy", AxpyArgs),
-                ("pack", PackArgs), ("project", ProjectArgs), ("gn_fin", GnFinalizeArgs),
-                ("pf_drift", PfDriftArgs), ("hutch_div", HutchDivArgs), ("colsum_fin", ColsumFinishArgs), ("gn_bwd_fin", GnBwdFinishArgs),
-                ("gn_apply", GnApplyArgs), ("gn_apply_bwd", GnApplyBwdArgs)]
+    _fields_ = [(member, args) for _, member, args, _ in OPS]
 
 
 class Op(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flops_class", C.c_int32), ("u", _OpUnion)]
 
 
-_UNION_FIELD = {OP_CONV: "conv", OP_GN_STATS: "gn", OP_UPFIRDN: "fir", OP_ATTN: "attn", OP_EMBED: "embed",
-                OP_TO_NHWC: "to_nhwc", OP_TO_NCHW: "to_nchw", OP_BIAS_ACT: "bias_act", OP_SUMSQ: "sumsq",
-                OP_RANDN: "randn", OP_LANGEVIN: "langevin", OP_PREDICTOR: "predictor", OP_FILL: "fill",
-                OP_STEP_INC: "step_inc", OP_WGRAD: "wgrad", OP_COLSUM: "colsum", OP_GN_BWD_REDUCE: "gn_bwd",
-                OP_PROLOGUE_BWD: "pro_bwd", OP_ATTN_BWD: "attn_bwd", OP_PERTURB: "perturb", OP_DSM_LOSS: "dsm_loss",
-                OP_SUMSQ_FLAT: "sumsq_flat", OP_ADAM: "adam", OP_MEMSET: "memset", OP_AXPY: "axpy", OP_PACK: "pack", OP_PROJECT: "project",
-                OP_GN_FINALIZE: "gn_fin", OP_PF_DRIFT: "pf_drift", OP_HUTCH_DIV: "hutch_div", OP_COLSUM_FINISH: "colsum_fin",
-                OP_GN_BWD_FINISH: "gn_bwd_fin", OP_GN_APPLY: "gn_apply", OP_GN_APPLY_BWD: "gn_apply_bwd"}
+_UNION_FIELD = {kind: member for kind, member, _, _ in OPS}
+ARGS = {kind: args for kind, _, args, _ in OPS}
 
 EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attention", "ssde_attention_route", "ssde_embed", "ssde_to_nhwc",
            "ssde_to_nchw", "ssde_fused_bias_act", "ssde_sumsq", "ssde_randn", "ssde_langevin_update",
@@ -378,21 +385,12 @@ def bind(lib):
     lib.ssde_graph_capture.argtypes = [C.POINTER(Op), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.ssde_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
     lib.ssde_graph_destroy.argtypes = [C.c_void_p]
-    for name, typ in [("ssde_conv2d", ConvArgs), ("ssde_groupnorm_stats", GnStatsArgs), ("ssde_upfirdn2d", UpfirdnArgs),
-                      ("ssde_attention", AttnArgs), ("ssde_embed", EmbedArgs), ("ssde_to_nhwc", ToNhwcArgs),
-                      ("ssde_to_nchw", ToNchwArgs), ("ssde_fused_bias_act", BiasActArgs), ("ssde_sumsq", SumsqArgs),
-                      ("ssde_randn", RandnArgs), ("ssde_langevin_update", LangevinArgs),
-                      ("ssde_predictor_update", PredictorArgs), ("ssde_fill_from_table", FillArgs),
-                      ("ssde_step_inc", StepIncArgs), ("ssde_conv_wgrad", WgradArgs), ("ssde_colsum", ColsumArgs),
-                      ("ssde_gn_bwd_reduce", GnBwdReduceArgs), ("ssde_prologue_bwd", PrologueBwdArgs),
-                      ("ssde_attention_bwd", AttnBwdArgs), ("ssde_perturb", PerturbArgs), ("ssde_dsm_loss", DsmLossArgs),
-                      ("ssde_sumsq_flat", SumsqFlatArgs), ("ssde_adam_clip_ema", AdamArgs), ("ssde_memset", MemsetArgs),
-                      ("ssde_axpy", AxpyArgs), ("ssde_pack_weights", PackArgs), ("ssde_project_update", ProjectArgs),
-                      ("ssde_gn_finalize", GnFinalizeArgs), ("ssde_rk_combine", RkCombineArgs), ("ssde_hutch_div", HutchDivArgs), ("ssde_sample_update", SampleUpdateArgs),
-                      ("ssde_rk_error_norm", RkErrorArgs), ("ssde_pf_drift", PfDriftArgs),
-                      ("ssde_colsum_finish", ColsumFinishArgs), ("ssde_gn_bwd_finish", GnBwdFinishArgs),
-                      ("ssde_gn_apply", GnApplyArgs), ("ssde_gn_apply_bwd", GnApplyBwdArgs)]:
-        getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
+    for _, _, typ, name in OPS:
+        if name is not None:
+            getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
+    lib.ssde_rk_combine.argtypes = [C.POINTER(RkCombineArgs), C.c_void_p]
+    lib.ssde_rk_error_norm.argtypes = [C.POINTER(RkErrorArgs), C.c_void_p]
+    lib.ssde_sample_update.argtypes = [C.POINTER(SampleUpdateArgs), C.c_void_p]
     lib.ssde_conv_lds_bytes.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_attention_route.argtypes = [C.POINTER(AttnArgs)]
     lib.ssde_conv_gn_slices.argtypes = [C.POINTER(ConvArgs)]
@@ -444,12 +442,46 @@ def pointer_offsets(struct_cls, base=0):
     return out
 
 
+_OP_PTRS = {}
+
+
+def _op_pointer_offsets(kind):
+    """pointer_offsets of an op of this kind, from the start of the ssde_op"""
+    if kind not in _OP_PTRS:
+        _OP_PTRS[kind] = pointer_offsets(ARGS[kind], Op.u.offset)
+    return _OP_PTRS[kind]
+
+
+def pointers_at(raw, offsets, base=0):
+    """(byte offset, address) of every non-null pointer among the 8-byte fields of `raw` at base + offsets"""
+    for off in offsets:
+        addr = int.from_bytes(raw[base + off:base + off + 8], "little")
+        if addr:
+            yield base + off, addr
+
+
+def op_pointers(op):
+    """(byte offset, address) of every non-null pointer field of an op"""
+    return pointers_at(bytes(op), _op_pointer_offsets(int(op.kind)))
+
+
 def make_op(kind, args, flops_class=0):
     op = Op()
     op.kind = kind
     op.flops_class = flops_class
     setattr(op.u, _UNION_FIELD[kind], args)
     return op
+
+
+def make(kind, **fields):
+    """An op from keyword fields of its kind's argument structure: a tensor becomes its data_ptr(), a list or tuple of floats a
+    c_float array, None a null pointer."""
+    args = ARGS[kind]()
+    for k, v in fields.items():
+        if isinstance(v, (list, tuple)):
+            v = (C.c_float * len(v))(*v)
+        setattr(args, k, v.data_ptr() if hasattr(v, "data_ptr") else v)
+    return make_op(kind, args)
 
 
 def op_array(ops):

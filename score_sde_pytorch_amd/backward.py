@@ -544,21 +544,13 @@ class TrainEngine(E.UNetEngine):
         at or beyond the slice's start -- an op whose pointer lies below `lo` but whose run crosses it counts too."""
         if getattr(self, "_buckets", None) is not None and self._buckets[0] == bucket_floats:
             return self._buckets[1]
-        import ctypes as C
         base, end = self.flat.grad.data_ptr(), self.flat.grad.data_ptr() + self.flat.numel * 4
-
-        def pointers(struct):
-            raw = bytes(struct)
-            for off in L.pointer_offsets(type(struct)):
-                v = int.from_bytes(raw[off:off + 8], "little")
-                if v:
-                    yield v
         touch = []                                   # (float offset, op index) of every reference into flat.grad
         for i in range(self.n_fwd, self.program.n):
             op = self.program.ops[i]
             if op.kind == L.OP_MEMSET:
                 continue                             # the zero-fill at the head of the backward program
-            for ptr in pointers(getattr(op.u, L._UNION_FIELD[op.kind])):
+            for _, ptr in L.op_pointers(op):
                 if base <= ptr < end:
                     touch.append(((ptr - base) // 4, i))
         # bucket boundaries at parameter starts; the grouped parameters at the head of the buffer (written as one run by a

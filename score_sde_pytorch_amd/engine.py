@@ -101,18 +101,6 @@ def _fill(struct, fields):
             setattr(struct, k, v)
 
 
-_STRUCT = {L.OP_CONV: L.ConvArgs, L.OP_GN_STATS: L.GnStatsArgs, L.OP_UPFIRDN: L.UpfirdnArgs, L.OP_ATTN: L.AttnArgs,
-           L.OP_EMBED: L.EmbedArgs, L.OP_TO_NHWC: L.ToNhwcArgs, L.OP_TO_NCHW: L.ToNchwArgs,
-           L.OP_BIAS_ACT: L.BiasActArgs, L.OP_SUMSQ: L.SumsqArgs, L.OP_RANDN: L.RandnArgs,
-           L.OP_LANGEVIN: L.LangevinArgs, L.OP_PREDICTOR: L.PredictorArgs, L.OP_FILL: L.FillArgs,
-           L.OP_STEP_INC: L.StepIncArgs, L.OP_WGRAD: L.WgradArgs, L.OP_COLSUM: L.ColsumArgs,
-           L.OP_GN_BWD_REDUCE: L.GnBwdReduceArgs, L.OP_PROLOGUE_BWD: L.PrologueBwdArgs, L.OP_ATTN_BWD: L.AttnBwdArgs,
-           L.OP_PERTURB: L.PerturbArgs, L.OP_DSM_LOSS: L.DsmLossArgs, L.OP_SUMSQ_FLAT: L.SumsqFlatArgs,
-           L.OP_ADAM: L.AdamArgs, L.OP_MEMSET: L.MemsetArgs, L.OP_AXPY: L.AxpyArgs, L.OP_GN_FINALIZE: L.GnFinalizeArgs,
-           L.OP_COLSUM_FINISH: L.ColsumFinishArgs, L.OP_GN_BWD_FINISH: L.GnBwdFinishArgs,
-           L.OP_GN_APPLY: L.GnApplyArgs, L.OP_GN_APPLY_BWD: L.GnApplyBwdArgs}
-
-
 _ROUTE = {L.OP_CONV: L.conv_route_flags, L.OP_WGRAD: L.wgrad_route_flags, L.OP_GN_BWD_REDUCE: L.gn_bwd_route_flags,
           L.OP_ATTN: L.attn_route_flags}
 
@@ -189,7 +177,7 @@ class ProgramBuilder:
                     continue                     # the raw-source half of a pair: issued by its partner through dst2
                 fields = dict(fields, dst2=fused_fir[si])
             for sub_fields, sub_class, sub_fl in _expand(kind, fields, fclass, fl):
-                args = _STRUCT[kind]()
+                args = L.ARGS[kind]()
                 _fill(args, sub_fields)
                 if kind in _ROUTE and "flags" not in sub_fields:
                     args.flags = _ROUTE[kind]()          # A/B switches of the environment, read ONCE here (see _lib.py)
@@ -241,12 +229,41 @@ def _expand(kind, fields, fclass, fl):
     return [(a, fclass, fl - fl1), (b, FC_CONV1, fl1)]
 
 
+class OpList(list):
+    """A slice of a Program: the ops, with their flops classes and flop counts beside them."""
+    __slots__ = ("classes", "flops")
+
+
 class Program:
     def __init__(self, ops, classes, flops, owner):
         self.ops, self.n = ops, len(ops)
         self.classes, self.flops = classes, flops
         self._owner = owner   # keeps buffers / weights alive
         self._graph = None
+
+    @classmethod
+    def of(cls, parts, owner):
+        """One program from a flat sequence of ops, lists of ops, program slices and whole programs, in that order.  Classes and
+        flops are carried where a part has them (a Program, a slice of one); any other op counts as FC_OTHER with no flops."""
+        ops, classes, flops = [], [], []
+        for part in parts:
+            if isinstance(part, Program):
+                part = part[:]
+            elif isinstance(part, L.Op):
+                part = [part]
+            ops.extend(part)
+            classes.extend(getattr(part, "classes", None) or [FC_OTHER] * len(part))
+            flops.extend(getattr(part, "flops", None) or [0.0] * len(part))
+        return cls(L.op_array(ops), classes, flops, owner)
+
+    def __getitem__(self, span):
+        """prog[lo:hi]: the ops of a range, as a list that remembers their classes and flops"""
+        out = OpList(self.ops[span])
+        out.classes, out.flops = self.classes[span], self.flops[span]
+        return out
+
+    def _at(self, start):
+        return C.cast(C.byref(self.ops, start * C.sizeof(L.Op)), C.POINTER(L.Op))
 
     def _launch(self, ops_ptr, count, stream=None):
         lib = L.load()
@@ -261,23 +278,17 @@ class Program:
     def run_range(self, start, count, stream=None):
         """Run ops [start, start+count) (forward and backward halves of a training program)."""
         assert 0 <= start and start + count <= self.n
-        ptr = C.cast(C.byref(self.ops, start * C.sizeof(L.Op)), C.POINTER(L.Op))
-        self._launch(ptr, count, stream)
+        self._launch(self._at(start), count, stream)
 
     def run_range_timed(self, start, count):
         lib = L.load()
         ms = (C.c_float * count)()
-        ptr = C.cast(C.byref(self.ops, start * C.sizeof(L.Op)), C.POINTER(L.Op))
         st = torch.cuda.current_stream().cuda_stream
-        L.check(lib.ssde_program_run_timed(ptr, count, C.c_void_p(st), ms), "ssde_program_run_timed")
+        L.check(lib.ssde_program_run_timed(self._at(start), count, C.c_void_p(st), ms), "ssde_program_run_timed")
         return list(ms)
 
     def run_timed(self):
-        lib = L.load()
-        ms = (C.c_float * self.n)()
-        st = torch.cuda.current_stream().cuda_stream
-        L.check(lib.ssde_program_run_timed(self.ops, self.n, C.c_void_p(st), ms), "ssde_program_run_timed")
-        return list(ms)
+        return self.run_range_timed(0, self.n)
 
     def capture(self, stream):
         """Capture into a hipGraph on `stream` (a torch.cuda.Stream, not the default stream)."""
@@ -290,12 +301,51 @@ class Program:
     def replay(self, stream):
         L.check(L.load().ssde_graph_launch(self._graph, C.c_void_p(stream.cuda_stream)), "ssde_graph_launch")
 
+    def replay_from_current(self, side, times=1):
+        """Replay the program's graph `times` times on `side`, ordered after what the current stream holds and before what it
+        is given next; the graph is captured on `side` on first use.  `side` may be the current stream itself (not the default
+        stream, which cannot capture): then nothing has to wait."""
+        cur = torch.cuda.current_stream()
+        apart = side.cuda_stream != cur.cuda_stream
+        if apart:
+            side.wait_stream(cur)
+        if self._graph is None:
+            self.capture(side)
+        for _ in range(times):
+            self.replay(side)
+        if apart:
+            cur.wait_stream(side)
+
     def __del__(self):
         if getattr(self, "_graph", None):
             try:
                 L.load().ssde_graph_destroy(self._graph)
             except Exception:
                 pass
+
+
+class PinnedRing:
+    """`slots` host staging buffers (pinned when CUDA is available) with one event per slot, for per-call scalars: the H2D copy
+    is asynchronous and nothing else synchronises the host, so a slot is rewritten only after the copy that last read it has
+    completed -- a caller may enqueue more uploads than there are slots without reading anything back."""
+
+    def __init__(self, slots, length, dtype, pinned=None):
+        pinned = torch.cuda.is_available() if pinned is None else pinned
+        self.bufs = [torch.zeros(length, dtype=dtype, pin_memory=pinned) for _ in range(slots)]
+        self.events = [None] * slots
+        self.next = 0
+
+    def upload(self, dst, write):
+        """write(host buffer) fills the next slot; its contents are copied to `dst` on the current stream"""
+        i = self.next % len(self.bufs)
+        self.next += 1
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+        write(self.bufs[i])
+        dst.copy_(self.bufs[i], non_blocking=True)
+        if dst.is_cuda:
+            self.events[i] = self.events[i] or torch.cuda.Event()
+            self.events[i].record(torch.cuda.current_stream(dst.device))
 
 
 # --------------------------------------------------------------------------- weights
@@ -384,6 +434,15 @@ def pack_matrix(w):
     return pack_conv_weight(w.reshape(w.shape[0], w.shape[1], 1, 1))
 
 
+class _Entry:
+    """One packed weight: the kernel-layout copy, the parameters it is made from, the torch packer, the stamp of the sources
+    when it was last packed (None: never), and the descriptors of the device-side re-pack (None: torch packer only)."""
+    __slots__ = ("packed", "sources", "fn", "stamp", "recipe")
+
+    def __init__(self, packed, sources, fn, stamp, recipe):
+        self.packed, self.sources, self.fn, self.stamp, self.recipe = packed, sources, fn, stamp, recipe
+
+
 class WeightStore:
     """Packed copies of module parameters with stable device addresses.
 
@@ -396,8 +455,9 @@ class WeightStore:
 
     def __init__(self, device):
         self.device = device
-        self.entries = []   # [packed, sources, fn, stamp]
+        self.entries = []   # _Entry(packed, sources, fn, stamp, recipe)
         self.meta = {}
+        self._tables = None
 
     def add(self, sources, fn, meta=None, recipe=None):
         """recipe: descriptors for the device-side re-pack (ssde_pack_weights); fn is the same packing in torch, used for
@@ -415,7 +475,7 @@ class WeightStore:
                 packed = torch.zeros(tuple(shape), dtype=torch.float32, device=self.device)
             else:
                 packed = fn(*[s.detach() for s in sources]).to(self.device).contiguous()
-        self.entries.append([packed, list(sources), fn, None if lazy else self._stamp(sources), recipe])
+        self.entries.append(_Entry(packed, list(sources), fn, None if lazy else self._stamp(sources), recipe))
         if meta is not None:
             self.meta[id(packed)] = meta
         self._tables = None
@@ -513,10 +573,13 @@ class WeightStore:
         return self.meta[key]
 
     # -- device-side re-pack -------------------------------------------------------------------------
+    def _source_addresses(self):
+        return tuple(s.data_ptr() for e in self.entries if e.recipe is not None for s in e.sources)
+
     def _build_tables(self):
         descs = {}
         for e in self.entries:
-            packed, recipe = e[0], e[4]
+            packed, recipe = e.packed, e.recipe
             if recipe is None:
                 continue
             for r in recipe:
@@ -536,19 +599,28 @@ class WeightStore:
             args = L.PackArgs()
             args.table, args.count, args.kind, args.max_n = raw.data_ptr(), len(ds), kind, max(int(x.n) for x in ds)
             tables.append((args, raw))
-        stamp = tuple(s.data_ptr() for e in self.entries if e[4] is not None for s in e[1])
-        self._tables = (tables, stamp)
+        self._tables = (tables, self._source_addresses())
+
+    def pack_tables(self):
+        """[(ssde_pack_args, descriptor table on the device)], one per pack kind: the device-side re-pack of every entry that
+        has a recipe.  Rebuilt (a NEW list: holders of the old one, a captured graph for instance, can tell) when a source
+        parameter has moved to another address, the same object otherwise."""
+        if self._tables is None or self._tables[1] != self._source_addresses():
+            self._build_tables()
+        return self._tables[0]
+
+    def pack_ops(self):
+        """the re-pack as OP_PACK ops, one per table of pack_tables()"""
+        return [L.make_op(L.OP_PACK, args) for args, _ in self.pack_tables()]
 
     def device_refresh(self):
         """Re-pack every entry that has a recipe with four launches (one per kind); returns False when nothing has one."""
         from . import hipops
-        if getattr(self, "_tables", None) is None or \
-                self._tables[1] != tuple(s.data_ptr() for e in self.entries if e[4] is not None for s in e[1]):
-            self._build_tables()
+        tables = self.pack_tables()
         lib = L.load()
-        for args, _ in self._tables[0]:
+        for args, _ in tables:
             L.check(lib.ssde_pack_weights(C.byref(args), hipops._stream()), "ssde_pack_weights")
-        return bool(self._tables[0])
+        return bool(tables)
 
     @staticmethod
     def _stamp(sources):
@@ -561,27 +633,29 @@ class WeightStore:
         training step): record the sources' stamps so that the next refresh() does not do it again; entries without a recipe
         are re-packed here."""
         for e in self.entries:
-            st = self._stamp(e[1])
-            if e[4] is None and st != e[3]:
-                with torch.no_grad():
-                    e[0].copy_(e[2](*[s.detach() for s in e[1]]).to(self.device))
-            e[3] = st
+            st = self._stamp(e.sources)
+            if e.recipe is None and st != e.stamp:
+                self._torch_pack(e)
+            e.stamp = st
+
+    def _torch_pack(self, e):
+        with torch.no_grad():
+            e.packed.copy_(e.fn(*[s.detach() for s in e.sources]).to(self.device))
 
     def refresh(self, force=False, on_device=None):
         """Bring packed copies up to date.  force=True (after the fused optimizer wrote the flat parameter buffer behind
         torch's back) re-packs everything: with the device kernels when the library can run here, else in torch."""
         if on_device is None:
             on_device = self._on_device()
-        stamps = [self._stamp(e[1]) for e in self.entries]
-        stale = [force or st != e[3] for e, st in zip(self.entries, stamps)]
+        stamps = [self._stamp(e.sources) for e in self.entries]
+        stale = [force or st != e.stamp for e, st in zip(self.entries, stamps)]
         # any stale entry that has a device recipe (first use, optimizer step, checkpoint load, EMA swap, a user's in-place
         # edit): four device launches re-pack the whole store -- cheaper than one torch packer, and no rocBLAS kernel
-        done_on_device = on_device and any(old and e[4] is not None for e, old in zip(self.entries, stale)) and self.device_refresh()
+        done_on_device = on_device and any(old and e.recipe is not None for e, old in zip(self.entries, stale)) and self.device_refresh()
         for e, st, old in zip(self.entries, stamps, stale):
-            if old and not (done_on_device and e[4] is not None):
-                with torch.no_grad():
-                    e[0].copy_(e[2](*[s.detach() for s in e[1]]).to(self.device))
-            e[3] = st
+            if old and not (done_on_device and e.recipe is not None):
+                self._torch_pack(e)
+            e.stamp = st
 
 
 # --------------------------------------------------------------------------- lowering helpers

@@ -17,10 +17,18 @@ Same names, arguments and error behaviour: `get_optimizer` (:26-35), `optimizati
 Data parallelism (replaces nn.DataParallel): one process per GPU; when torch.distributed is
 initialised the fused step averages gradients with ONE all-reduce per step (parallel.py).
 """
+import os
+import warnings
+
 import numpy as np
 import torch
+import torch.distributed as dist
 import torch.optim as optim
 
+from . import _lib as L
+from . import backward as B
+from . import engine as E
+from . import hipops
 from . import sde_lib
 from .models import utils as mutils
 from .sde_lib import VESDE, VPSDE
@@ -92,7 +100,6 @@ class _DsmHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, score, z, s, g2, reduce_mean, likelihood_weighting):
-        from . import hipops
         loss, _, dscore = hipops.dsm_loss(score.detach().float().contiguous(), z.float().contiguous(), s.float().contiguous(),
                                           None if g2 is None else g2.float().contiguous(), reduce_mean=reduce_mean,
                                           likelihood_weighting=likelihood_weighting, want_grad=True)
@@ -107,7 +114,6 @@ class _DsmHead(torch.autograd.Function):
 
 def _perturb(x, z, s, a=None):
     """a[n] * x + s[n] * z  (ssde_perturb)."""
-    from . import hipops
     return hipops.perturb(x.float().contiguous(), z.float().contiguous(), s.float().contiguous(),
                           None if a is None else a.float().contiguous())
 
@@ -173,10 +179,6 @@ class FusedTrainStep:
     """perturb -> forward -> loss head -> backward -> [all-reduce] -> clip + Adam + EMA, all libssde_hip kernels."""
 
     def __init__(self, model, spec, batch_shape, device):
-        from . import backward as B
-        from . import _lib as L
-        from . import engine as E
-        self.L, self.E = L, E
         self.model, self.spec, self.device = model, spec, device
         sde = spec["sde"]
         self.vp_like = isinstance(sde, (sde_lib.VPSDE, sde_lib.subVPSDE))
@@ -195,11 +197,7 @@ class FusedTrainStep:
         self.losses = torch.zeros(n, **f32)
         self.loss = torch.zeros(1, **f32)
         self.hyper = torch.zeros(12, **f32)
-        # ring of pinned staging buffers for the per-step scalars: the H2D copy is asynchronous and nothing else in the
-        # step synchronises the host, so a slot is rewritten only after the copy that last read it has completed
-        self._hyper_ring = [[torch.zeros(12, dtype=torch.float32, pin_memory=torch.cuda.is_available()), None]
-                            for _ in range(4)]
-        self._hyper_slot = 0
+        self._hyper_ring = E.PinnedRing(4, 12, torch.float32)      # staging of the per-step scalars
         self.gnorm = torch.zeros(1, **f32)
         self.partial = torch.zeros(1024, **f32)
         self._opt_prog = None
@@ -207,13 +205,13 @@ class FusedTrainStep:
         self.steps_done = 0
 
     def _prog(self, entries):
-        b = self.E.ProgramBuilder(self.device)
+        b = E.ProgramBuilder(self.device)
         for kind, fields in entries:
             b.add(kind, fields)
         return b.finalize()
 
     def _build_head(self):
-        L, eng, spec = self.L, self.eng, self.spec
+        eng, spec = self.eng, self.spec
         x_in = eng.x_in.tensor
         perturb = self._prog([(L.OP_PERTURB, dict(x=self.batch, z=self.z, a=self.a, s=self.s, dst=x_in, n=self.n, per=self.per))])
         loss = self._prog([(L.OP_DSM_LOSS, dict(score=eng.out.tensor, z=self.z, s=self.s,
@@ -226,15 +224,12 @@ class FusedTrainStep:
 
     @staticmethod
     def _world():
-        import torch.distributed as dist
         return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
     def _exchanges(self):
         """Is the gradient exchange on?  Data parallel (world > 1); SSDE_FORCE_GRAD_EXCHANGE=1 also turns it on in a
         one-rank process group, so that the bucketed RCCL path and its stream ordering run on a single GPU
         (tests/test_train_gpu.py).  skip_exchange: bench.py times the step without it."""
-        import os
-        import torch.distributed as dist
         if getattr(self, "skip_exchange", False):
             return False
         if self._world() > 1:
@@ -246,7 +241,6 @@ class FusedTrainStep:
         ema_buf = ema.flatten_like(self.flat) if ema is not None else None
         key = (m.data_ptr(), v.data_ptr(), ema_buf.data_ptr() if ema_buf is not None else 0)
         if self._opt_prog is None or self._opt_prog[1] is not optimizer or self._opt_prog[2] is not ema or self._opt_prog[3] != key:
-            L = self.L
             prog = self._prog([
                 (L.OP_SUMSQ_FLAT, dict(x=self.flat.grad, numel=self.flat.numel, partial=self.partial, out=self.gnorm)),
                 (L.OP_ADAM, dict(p=self.flat.data, g=self.flat.grad, m=m, v=v, ema=ema_buf, numel=self.flat.numel,
@@ -306,8 +300,6 @@ class FusedTrainStep:
             if self._exchanges():
                 # data parallel: ~32 MB buckets of the flat gradient are all-reduced (RCCL, its own stream) as soon as the
                 # backward ops that finalise them are enqueued, overlapping the rest of the backward program
-                import torch.distributed as dist
-                import os
                 bucket = int(float(os.environ.get("SSDE_GRAD_BUCKET_MB", "32")) * 262144)
                 eng.run_backward_bucketed(
                     lambda lo, hi: self._pending.append(dist.all_reduce(self.flat.grad[lo:hi], async_op=True)), bucket)
@@ -316,46 +308,43 @@ class FusedTrainStep:
         return self.loss
 
     # ------------------------------------------------------------------ the whole step as ONE hipGraph
+    def _graphs_wanted(self):
+        return os.environ.get("SSDE_TRAIN_GRAPH", "1") != "0" and self.spec["train"] and self.device.type == "cuda" \
+            and getattr(self, "_graph_failed", None) is None
+
+    def _capture(self, programs, what):
+        """Capture every program on the step's side stream, behind what the current stream holds.  A driver that refuses the
+        capture (or the instantiation) must not stop training: the program runs of loss_and_grads + optimizer_step are the same
+        launches, issued one by one.  Remembered (_graph_failed), reported once; returns whether all were captured."""
+        if getattr(self, "_gstream", None) is None:
+            self._gstream = torch.cuda.Stream(device=self.device)
+        self._gstream.wait_stream(torch.cuda.current_stream())
+        try:
+            for prog in programs:
+                prog.capture(self._gstream)
+        except L.SsdeError as exc:
+            self._graph_failed = exc
+            warnings.warn("libssde_hip: capturing the training step as %s failed (%s); running it as program launches" % (what, exc))
+        torch.cuda.current_stream().wait_stream(self._gstream)
+        return getattr(self, "_graph_failed", None) is None
+
     def _step_graph(self, optimizer, ema):
         """perturb -> forward -> loss head -> backward -> clip + Adam + EMA -> weight re-pack as one captured graph (no gradient
         exchange: a single replica, or bench.py's no-exchange leg).  Everything that changes from step to step lives in device
         buffers the host refreshes before the replay (batch, z, per-sample coefficients, the hyper-parameter record, the dropout
         seed word), so the ~1400 launches of a step cost one hipGraphLaunch.  SSDE_TRAIN_GRAPH=0 keeps the program runs."""
-        import os
-        if os.environ.get("SSDE_TRAIN_GRAPH", "1") == "0" or not self.spec["train"] or self.device.type != "cuda":
-            return None
-        if getattr(self, "_graph_failed", None) is not None:
+        if not self._graphs_wanted():
             return None
         opt = self._optimizer_program(optimizer, ema)
-        ws = self.eng.weights
-        if getattr(ws, "_tables", None) is None or \
-                ws._tables[1] != tuple(s_.data_ptr() for e in ws.entries if e[4] is not None for s_ in e[1]):
-            ws._build_tables()
-        key = (id(opt), id(ws._tables))
+        ws, eng = self.eng.weights, self.eng
+        tables = ws.pack_tables()                    # (a new object whenever the tables were rebuilt: part of the key)
+        key = (id(opt), id(tables))
         if getattr(self, "_graph", None) is not None and self._graph[0] == key:
             return self._graph[1]
-        L, E, eng = self.L, self.E, self.eng
-        ops = [self._head[0].ops[0]]
-        ops += [eng.program.ops[i] for i in range(eng.n_fwd)]
-        ops += [self._head[1].ops[0]]
-        ops += [eng.program.ops[i] for i in range(eng.n_fwd, eng.program.n)]
-        ops += [opt.ops[i] for i in range(opt.n)]
-        ops += [L.make_op(L.OP_PACK, args) for args, _ in ws._tables[0]]
-        prog = E.Program(L.op_array(ops), [0] * len(ops), [0.0] * len(ops), (self, opt, ws._tables))
-        if getattr(self, "_gstream", None) is None:
-            self._gstream = torch.cuda.Stream(device=self.device)
-        self._gstream.wait_stream(torch.cuda.current_stream())
-        try:
-            prog.capture(self._gstream)
-        except L.SsdeError as exc:
-            # a driver that refuses the capture (or the instantiation) must not stop training: the program runs of
-            # loss_and_grads + optimizer_step are the same launches, issued one by one.  Remembered, reported once.
-            import warnings
-            self._graph_failed = exc
-            warnings.warn("libssde_hip: capturing the training step as a hipGraph failed (%s); running it as program launches" % exc)
-            torch.cuda.current_stream().wait_stream(self._gstream)
+        fwd, bwd = eng.program[:eng.n_fwd], eng.program[eng.n_fwd:]
+        prog = E.Program.of([self._head[0], fwd, self._head[1], bwd, opt, ws.pack_ops()], (self, opt, tables))
+        if not self._capture([prog], "a hipGraph"):
             return None
-        torch.cuda.current_stream().wait_stream(self._gstream)
         self._graph = (key, prog)
         return prog
 
@@ -367,53 +356,31 @@ class FusedTrainStep:
         the last bucket a closing graph holds clip + Adam + EMA + weight re-pack behind the collectives.  At the default 32 MB
         bucket that is 9 + 1 graph launches and 8 all-reduces per step.  Returns [(program, (lo, hi) or None)], or None when
         graphs are off / unavailable (the program runs of loss_and_grads + optimizer_step are the fallback)."""
-        import os
-        if os.environ.get("SSDE_TRAIN_GRAPH", "1") == "0" or not self.spec["train"] or self.device.type != "cuda":
-            return None
-        if getattr(self, "_graph_failed", None) is not None:
+        if not self._graphs_wanted():
             return None
         opt = self._optimizer_program(optimizer, ema)
-        ws = self.eng.weights
-        if getattr(ws, "_tables", None) is None or \
-                ws._tables[1] != tuple(s_.data_ptr() for e in ws.entries if e[4] is not None for s_ in e[1]):
-            ws._build_tables()
+        ws, eng = self.eng.weights, self.eng
+        tables = ws.pack_tables()
         bucket = int(float(os.environ.get("SSDE_GRAD_BUCKET_MB", "32")) * 262144)
-        key = (id(opt), id(ws._tables), bucket)
+        key = (id(opt), id(tables), bucket)
         if getattr(self, "_graph_seg", None) is not None and self._graph_seg[0] == key:
             return self._graph_seg[1]
-        L, E, eng = self.L, self.E, self.eng
-        head = [self._head[0].ops[0]] + [eng.program.ops[i] for i in range(eng.n_fwd)] + [self._head[1].ops[0]]
+        head = [self._head[0], eng.program[:eng.n_fwd], self._head[1]]
         plan, cur = [], eng.n_fwd
         for lo, hi, op_end in eng.grad_buckets(bucket):
-            ops = head + [eng.program.ops[i] for i in range(cur, max(op_end, cur))]
+            plan.append((head + [eng.program[cur:max(op_end, cur)]], (lo, hi)))
             head, cur = [], max(op_end, cur)
-            plan.append((ops, (lo, hi)))
-        tail = [eng.program.ops[i] for i in range(cur, eng.program.n)]
-        tail += [opt.ops[i] for i in range(opt.n)] + [L.make_op(L.OP_PACK, args) for args, _ in ws._tables[0]]
-        plan.append((tail, None))
-        if getattr(self, "_gstream", None) is None:
-            self._gstream = torch.cuda.Stream(device=self.device)
-        self._gstream.wait_stream(torch.cuda.current_stream())
+        plan.append(([eng.program[cur:], opt, ws.pack_ops()], None))
         segs = []
-        try:
-            for ops, span in plan:
-                prog = None
-                if ops:                              # (a bucket that is final at the same op as its predecessor: no launch)
-                    prog = E.Program(L.op_array(ops), [0] * len(ops), [0.0] * len(ops), (self, opt, ws._tables))
-                    prog.capture(self._gstream)
-                segs.append((prog, span))
-        except L.SsdeError as exc:
-            import warnings
-            self._graph_failed = exc
-            warnings.warn("libssde_hip: capturing the training step as hipGraphs failed (%s); running it as program launches" % exc)
-            torch.cuda.current_stream().wait_stream(self._gstream)
+        for parts, span in plan:
+            prog = E.Program.of(parts, (self, opt, tables))
+            segs.append((prog if prog.n else None, span))      # (a bucket that is final at the same op as its predecessor: no launch)
+        if not self._capture([prog for prog, _ in segs if prog is not None], "hipGraphs"):
             return None
-        torch.cuda.current_stream().wait_stream(self._gstream)
         self._graph_seg = (key, segs)
         return segs
 
     def _train_step_exchange_graphs(self, segs, batch, optimizer, ema, step, hyper, t, z, seed):
-        import torch.distributed as dist
         self._draw_and_perturb(batch, t, z)
         self.eng.weights.refresh()
         self.eng.set_dropout_seed(self._dropout_seed() if seed is None else seed)
@@ -454,10 +421,7 @@ class FusedTrainStep:
         self.eng.weights.refresh()                    # (a no-op unless somebody wrote parameters behind the step's back)
         self.eng.set_dropout_seed(self._dropout_seed() if seed is None else seed)
         self._upload_hyper(optimizer, ema, step, hyper)
-        s = self._gstream
-        s.wait_stream(torch.cuda.current_stream())
-        prog.replay(s)
-        torch.cuda.current_stream().wait_stream(s)
+        prog.replay_from_current(self._gstream)
         self._after_update(optimizer, repacked=True)
         return self.loss.clone()
 
@@ -465,14 +429,12 @@ class FusedTrainStep:
         """Mask stream of this step: torch's seed (torch.manual_seed), the data-parallel rank and a per-call counter
         that a resumed run continues from `state['step']` (the reference's dropout draws from torch's generator, so
         replicas and resumed runs never replay the same masks)."""
-        import torch.distributed as dist
         rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
         count = self.steps_done + int(getattr(self, "step_offset", 0))
         word = (int(torch.initial_seed()) * 1000003 + rank * 7919 + 17) & 0xFFFFFFFFFFFF
         return (word * 2654435761 + count * 40503) & 0x7FFFFFFF
 
     def optimizer_step(self, optimizer, ema, step, hyper):
-        import torch.distributed as dist
         if self._exchanges():     # gradients were pre-scaled by 1/world in the loss head
             self.collectives_last_step = len(getattr(self, "_pending", None) or []) or 1
             if getattr(self, "_pending", None):
@@ -498,18 +460,12 @@ class FusedTrainStep:
         t_adam = float(st0["step"]) + 1.0
         b1, b2 = group["betas"]
         decay = ema.next_decay() if ema is not None else 1.0
-        slot = self._hyper_ring[self._hyper_slot % len(self._hyper_ring)]
-        self._hyper_slot += 1
-        if slot[1] is not None:
-            slot[1].synchronize()
-        h = slot[0]
-        h[0], h[1], h[2], h[3], h[4] = lr, b1, b2, group["eps"], group["weight_decay"]
-        h[5] = hyper["grad_clip"]
-        h[6], h[7], h[8] = 1.0 - b1 ** t_adam, float(np.sqrt(1.0 - b2 ** t_adam)), 1.0 - decay
-        self.hyper.copy_(h, non_blocking=True)
-        if self.hyper.is_cuda:
-            slot[1] = torch.cuda.Event()
-            slot[1].record()
+
+        def write(h):
+            h[0], h[1], h[2], h[3], h[4] = lr, b1, b2, group["eps"], group["weight_decay"]
+            h[5] = hyper["grad_clip"]
+            h[6], h[7], h[8] = 1.0 - b1 ** t_adam, float(np.sqrt(1.0 - b2 ** t_adam)), 1.0 - decay
+        self._hyper_ring.upload(self.hyper, write)
 
     def _after_update(self, optimizer, repacked):
         for p in self.flat.params:

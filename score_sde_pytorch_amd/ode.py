@@ -7,9 +7,18 @@ FSAL, RMS error norm over the whole state, step factor 0.9 * err^(-1/5) clamped 
 `select_initial_step` -- with the state kept as an fp64 tensor on the GPU, so only one scalar (the error norm) crosses
 the PCIe bus per step.  `fun(t, y)` receives and returns fp64 device tensors.
 """
+import ctypes as C
 import math
+import os
+import struct
 
+import numpy as np
 import torch
+
+from . import _lib as L
+from . import engine as E
+from . import hipops
+from . import sde_lib
 
 _C = [0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0]
 _A = [[], [1 / 5], [3 / 40, 9 / 40], [44 / 45, -56 / 15, 32 / 9], [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
@@ -65,36 +74,32 @@ class _HipStages:
     the fused drift (FusedDrift) -- and the error norm comes back as ONE scalar per step."""
 
     def __init__(self, n, like, x32=None, n32=0):
-        from . import _lib as L
-        self.L, self.lib, self.n, self.n32 = L, L.load(), n, int(n32)
+        self.lib, self.n, self.n32 = L.load(), n, int(n32)
         self.K = torch.empty(7, n, dtype=torch.float64, device=like.device)
         self.partial = torch.empty(1024, dtype=torch.float64, device=like.device)
         self.out = torch.empty(1, dtype=torch.float64, device=like.device)
         self.x32 = x32
 
     def _stream(self):
-        from . import hipops
         return hipops._stream()
 
     def combine(self, y, coefs, dst):
-        import ctypes as C
-        a = self.L.RkCombineArgs()
+        a = L.RkCombineArgs()
         terms = max([j + 1 for j, c in enumerate(coefs) if c != 0.0], default=0)
         a.y, a.k, a.n, a.terms, a.dst = y.data_ptr(), self.K.data_ptr(), self.n, terms, dst.data_ptr()
         a.dst32 = self.x32.data_ptr() if self.x32 is not None else None
         a.n32 = self.n32
         for j in range(terms):
             a.coef[j] = coefs[j]
-        self.L.check(self.lib.ssde_rk_combine(C.byref(a), self._stream()), "ssde_rk_combine")
+        L.check(self.lib.ssde_rk_combine(C.byref(a), self._stream()), "ssde_rk_combine")
 
     def error_norm(self, y, y_new, coefs, atol, rtol):
-        import ctypes as C
-        a = self.L.RkErrorArgs()
+        a = L.RkErrorArgs()
         a.y, a.y_new, a.k, a.n, a.atol, a.rtol = y.data_ptr(), y_new.data_ptr(), self.K.data_ptr(), self.n, atol, rtol
         a.partial, a.partial_len, a.out = self.partial.data_ptr(), self.partial.numel(), self.out.data_ptr()
         for j in range(7):
             a.coef[j] = coefs[j]
-        self.L.check(self.lib.ssde_rk_error_norm(C.byref(a), self._stream()), "ssde_rk_error_norm")
+        L.check(self.lib.ssde_rk_error_norm(C.byref(a), self._stream()), "ssde_rk_error_norm")
         return float(self.out.item())          # the one host read of the step
 
 
@@ -140,8 +145,6 @@ def solve_rk45(fun, t_span, y0, rtol=1e-5, atol=1e-5, stages=None):
                 stages.combine(y, [a * h for a in _A[s_]], y_stage)
                 evaluate(t + _C[s_] * h, y_stage, s_)
             stages.combine(y, [b * h for b in _B], y_new)
-            if stages.x32 is not None:                   # the fp32 copy must hold y_new for the seventh evaluation
-                pass                                     # (combine wrote it: dst32 accompanies every combine)
             evaluate(t + h, y_new, 6)
             nfev += 6
             error_norm = stages.error_norm(y, y_new, [e * h for e in _E], atol, rtol)
@@ -177,7 +180,6 @@ def rhs_cache_get(model, key, make, limit=None):
     growing until the device runs out of memory -- and a loop that alternates sampling and likelihood evaluation over a few
     shapes does not make the two kinds evict each other (every eviction is a re-lowering and a re-capture on the next call).
     limit: entries kept per kind (default 4; SSDE_ODE_RHS_CACHE=<n> overrides)."""
-    import os
     if limit is None:
         limit = max(1, int(os.environ.get("SSDE_ODE_RHS_CACHE", "4")))
     cache = model.__dict__.setdefault("_ode_rhs", {})
@@ -203,14 +205,12 @@ class _FusedRhs:
     _RING = 32
 
     def _init_dyn(self, device):
-        import os
         self.device = torch.device(device)
         self.dyn = torch.zeros(24, dtype=torch.uint8, device=self.device)
         on_gpu = self.device.type == "cuda"
-        self._host = [torch.zeros(24, dtype=torch.uint8).pin_memory() if on_gpu else torch.zeros(24, dtype=torch.uint8)
-                      for _ in range(self._RING if on_gpu else 1)]
-        self._slot = 0
-        self._slot_events = [None] * len(self._host)     # the copy out of a pinned slot, recorded when it was enqueued
+        # a driver that enqueues more than _RING evaluations without reading anything back (a fixed-step integrator) must
+        # not overwrite a record whose upload has not executed yet
+        self._ring = E.PinnedRing(self._RING if on_gpu else 1, 24, torch.uint8, pinned=on_gpu)
         self.use_graph = on_gpu and os.environ.get("SSDE_ODE_GRAPH", "1") != "0"
         self.graph_stream = torch.cuda.Stream(device=self.device) if self.use_graph else None
         self.nfev = 0
@@ -234,59 +234,28 @@ class _FusedRhs:
         return float(label), second, float(drift1.reshape(-1)[0]), float((diffusion ** 2).reshape(-1)[0])
 
     def _upload(self, t, out):
-        import struct
-        label, second, a, g2 = self._scalars(t)
-        i = self._slot % len(self._host)
-        h = self._host[i]
-        self._slot += 1
-        # a driver that enqueues more than _RING evaluations without reading anything back (a fixed-step integrator) must
-        # not overwrite a record whose upload has not executed yet (as losses.FusedTrainStep's hyper ring)
-        if self._slot_events[i] is not None:
-            self._slot_events[i].synchronize()
-        import numpy as np
-        h.numpy()[:] = np.frombuffer(struct.pack("<ffffQ", label, second, a, g2, out.data_ptr()), dtype=np.uint8)
-        self.dyn.copy_(h, non_blocking=True)
-        if self.device.type == "cuda":
-            ev = self._slot_events[i] or torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            self._slot_events[i] = ev
+        record = np.frombuffer(struct.pack("<ffffQ", *self._scalars(t), out.data_ptr()), dtype=np.uint8)
 
-    def _head_ops(self, emit):
-        from . import _lib as L
+        def write(h):
+            h.numpy()[:] = record
+        self._ring.upload(self.dyn, write)
+
+    def _head_ops(self):
         eng, n = self.unet, self.shape[0]
         p = self.dyn.data_ptr()
-        emit(L.OP_FILL, L.FillArgs, dst=eng.cond.tensor, tab=p, step_ptr=None, n=n)
+        ops = [L.make(L.OP_FILL, dst=eng.cond.tensor, tab=p, step_ptr=None, n=n)]
         if eng.sig is not eng.cond:
-            emit(L.OP_FILL, L.FillArgs, dst=eng.sig.tensor, tab=p + 4, step_ptr=None, n=n)
+            ops.append(L.make(L.OP_FILL, dst=eng.sig.tensor, tab=p + 4, step_ptr=None, n=n))
         if self.vp_like:
-            emit(L.OP_FILL, L.FillArgs, dst=eng.std.tensor, tab=p + 4, step_ptr=None, n=n)
-
-    def _build(self, assemble):
-        import ctypes as C
-        from . import _lib as L, engine as E
-        ops = []
-
-        def emit(kind, struct_cls, **fields):
-            a = struct_cls()
-            for k, v in fields.items():
-                setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-            ops.append(L.make_op(kind, a))
-        assemble(emit, ops)
-        self.program = E.Program(L.op_array(ops), [E.FC_OTHER] * len(ops), [0.0] * len(ops), self)
+            ops.append(L.make(L.OP_FILL, dst=eng.std.tensor, tab=p + 4, step_ptr=None, n=n))
+        return ops
 
     def __call__(self, t, y, out):
         self.unet.weights.refresh()
         self._upload(t, out)
         if self.use_graph:
             cur = torch.cuda.current_stream()
-            s = cur if cur.cuda_stream != 0 else self.graph_stream      # (capture needs a non-default stream)
-            if s is not cur:
-                s.wait_stream(cur)
-            if self.program._graph is None:
-                self.program.capture(s)
-            self.program.replay(s)
-            if s is not cur:
-                cur.wait_stream(s)
+            self.program.replay_from_current(cur if cur.cuda_stream != 0 else self.graph_stream)    # (capture needs a non-default stream)
             self.last_path = "graph"
         else:
             self.program.run()
@@ -295,7 +264,6 @@ class _FusedRhs:
 
     @staticmethod
     def applies(model, sde, x):
-        from . import sde_lib
         from .models.ncsnpp import HipUNet
         if not isinstance(model, HipUNet) or not x.is_cuda or type(sde) not in (sde_lib.VESDE, sde_lib.VPSDE, sde_lib.subVPSDE):
             return False
@@ -309,20 +277,14 @@ class FusedDrift(_FusedRhs):
     runs (score head included: -h / std for VP / sub-VP), ssde_pf_drift forms the fp64 slope."""
 
     def __init__(self, model, sde, shape, device):
-        from . import engine as E, sde_lib, _lib as L
         self.sde, self.shape = sde, tuple(shape)
         self.vp_like = isinstance(sde, (sde_lib.VPSDE, sde_lib.subVPSDE))
         self.unet = E.UNetEngine(model, shape[0], shape[2], shape[3], device, vp_score=self.vp_like)
         self.n = int(torch.tensor(self.shape).prod())
         self.x32, self.n32 = self.unet.x_in.tensor[: self.n], self.n
         self._init_dyn(device)
-
-        def assemble(emit, ops):
-            self._head_ops(emit)
-            ops.extend(self.unet.program.ops[i] for i in range(self.unet.program.n))
-            emit(L.OP_PF_DRIFT, L.PfDriftArgs, x=self.x32, score=self.unet.out.tensor, dst=None, numel=self.n, a=0.0, g2=0.0,
-                 dyn=self.dyn)
-        self._build(assemble)
+        drift = L.make(L.OP_PF_DRIFT, x=self.x32, score=self.unet.out.tensor, dst=None, numel=self.n, a=0.0, g2=0.0, dyn=self.dyn)
+        self.program = E.Program.of([self._head_ops(), self.unet.program, drift], self)
 
 
 class FusedLikelihoodRhs(_FusedRhs):
@@ -333,7 +295,7 @@ class FusedLikelihoodRhs(_FusedRhs):
     the same vector-Jacobian product from torch.autograd.grad (likelihood.py:29-35)."""
 
     def __init__(self, model, sde, shape, probe, device):
-        from . import backward as B, sde_lib, _lib as L
+        from . import backward as B
         self.sde, self.shape = sde, tuple(shape)
         self.vp_like = isinstance(sde, (sde_lib.VPSDE, sde_lib.subVPSDE))
         eng = self.unet = B.TrainEngine(model, shape[0], shape[2], shape[3], device, vp_score=self.vp_like, input_grad=True,
@@ -344,15 +306,10 @@ class FusedLikelihoodRhs(_FusedRhs):
         self.eps = probe.detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
         eng.gout.tensor[: self.n].copy_(self.eps)        # the cotangent never changes: d(sum(score * eps)) / d score = eps
         self._init_dyn(device)
-
-        def assemble(emit, ops):
-            self._head_ops(emit)
-            ops.extend(eng.program.ops[i] for i in range(eng.n_fwd))
-            emit(L.OP_PF_DRIFT, L.PfDriftArgs, x=self.x32, score=eng.out.tensor, dst=None, numel=self.n, a=0.0, g2=0.0, dyn=self.dyn)
-            ops.extend(eng.program.ops[i] for i in range(eng.n_fwd, eng.program.n))
-            emit(L.OP_HUTCH_DIV, L.HutchDivArgs, gx=eng.gx.tensor, eps=self.eps, dst=None, dst_off=self.n, n=self.shape[0],
-                 per=self.per, a=0.0, g2=0.0, dyn=self.dyn)
-        self._build(assemble)
+        drift = L.make(L.OP_PF_DRIFT, x=self.x32, score=eng.out.tensor, dst=None, numel=self.n, a=0.0, g2=0.0, dyn=self.dyn)
+        div = L.make(L.OP_HUTCH_DIV, gx=eng.gx.tensor, eps=self.eps, dst=None, dst_off=self.n, n=self.shape[0], per=self.per,
+                     a=0.0, g2=0.0, dyn=self.dyn)
+        self.program = E.Program.of([self._head_ops(), eng.program[:eng.n_fwd], drift, eng.program[eng.n_fwd:], div], self)
 
     def set_probe(self, probe):
         """a new Hutchinson probe for the next solve (the reference draws one per likelihood_fn call, likelihood.py:76-81)"""
@@ -371,7 +328,6 @@ def solve_host(fun, t_span, y0, rtol=1e-5, atol=1e-5, method="RK45"):
     """The reference's integrator, scipy.integrate.solve_ivp on the host, around the same tensor right-hand side as
     solve_rk45: `fun(t, y)` takes / returns an fp64 tensor on y0's device; every evaluation crosses to numpy and back
     (what models/utils.py:181-188 does in the reference).  Used for methods other than RK45 and with SSDE_HOST_ODE=1."""
-    import numpy as np
     from scipy import integrate
     dev = y0.device
 
@@ -386,7 +342,6 @@ def solve_host(fun, t_span, y0, rtol=1e-5, atol=1e-5, method="RK45"):
 def integrate_ode(fun, t_span, y0, rtol, atol, method):
     """Device RK45 when the state lives on the GPU and nothing asks for the host path, else scipy on the host.
     A right-hand side with `writes_out` (FusedDrift) gets the fp32 copy of every stage argument written into its input."""
-    import os
     if method == "RK45" and y0.is_cuda and os.environ.get("SSDE_HOST_ODE", "0") != "1":
         side = getattr(fun, "graph_stream", None)
         if side is None:

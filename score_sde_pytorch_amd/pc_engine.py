@@ -22,7 +22,6 @@ a device-resident step counter -- the captured graph is replayed with identical 
 The Langevin step size needs a batch-wide reduction between the score evaluation and the update
 (SURVEY F10), which is why the loop body is a kernel sequence rather than one persistent kernel.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -154,26 +153,19 @@ class FusedPCSampler:
 
     # -------------------------------------------------------------- program assembly
     def _assemble(self, with_rng):
-        unet_ops = [self.unet.program.ops[i] for i in range(self.unet.program.n)]
-        unet_cls, unet_fl = list(self.unet.program.classes), list(self.unet.program.flops)
-        ops, classes, flops = [], [], []
+        parts = []
 
-        def emit(kind, struct_cls, **fields):
-            a = struct_cls()
-            for k, v in fields.items():
-                if isinstance(v, (list, tuple)):
-                    v = (C.c_float * len(v))(*v)
-                setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-            ops.append(L.make_op(kind, a)); classes.append(E.FC_OTHER); flops.append(0.0)
+        def emit(kind, **fields):
+            parts.append(L.make(kind, **fields))
 
         def emit_projection(noise, stream_id):
             pj = self.projection
             if pj is None:
                 return
             if with_rng:
-                emit(L.OP_RANDN, L.RandnArgs, dst=noise, numel=self.B * self.per, seed=0, seed_ptr=self.seed_word, step_ptr=self.step, stream_id=stream_id)
+                emit(L.OP_RANDN, dst=noise, numel=self.B * self.per, seed=0, seed_ptr=self.seed_word, step_ptr=self.step, stream_id=stream_id)
             Cc = self.shape[1]
-            emit(L.OP_PROJECT, L.ProjectArgs, x=self.x, x_mean=self.x_mean, data=self.proj_data, mask=self.proj_mask, noise=noise,
+            emit(L.OP_PROJECT, x=self.x, x_mean=self.x_mean, data=self.proj_data, mask=self.proj_mask, noise=noise,
                  coef=self.tabs["proj"], step_ptr=self.step, n=self.B, c=Cc, hw=self.per // Cc,
                  use_matrix=int(pj.get("M") is not None), M=list(pj.get("M") or [0.0] * 9), invM=list(pj.get("invM") or [0.0] * 9))
 
@@ -184,40 +176,38 @@ class FusedPCSampler:
         # headline counts two FULL evaluations per iteration, as the reference runs them.
         share = os.environ.get("SSDE_PC_SHARE_COND", "0") == "1"
         n_cond = self.unet.cond_only_ops if share else 0
-        emitted = [0]
+        unet = self.unet.program
 
-        def emit_unet():
-            lo = n_cond if emitted[0] else 0
-            emitted[0] += 1
-            ops.extend(unet_ops[lo:]); classes.extend(unet_cls[lo:]); flops.extend(unet_fl[lo:])
+        def emit_unet():     # (a program or a slice of one brings its flops classes and counts: bench.py groups by them)
+            parts.append(unet[n_cond:] if any(p is unet for p in parts) else unet)
 
         score = self.unet.out.tensor
-        emit(L.OP_FILL, L.FillArgs, dst=self.unet.cond.tensor, tab=self.tabs["label"], step_ptr=self.step, n=self.B)
+        emit(L.OP_FILL, dst=self.unet.cond.tensor, tab=self.tabs["label"], step_ptr=self.step, n=self.B)
         if self.plan["vp_like"]:
-            emit(L.OP_FILL, L.FillArgs, dst=self.unet.std.tensor, tab=self.tabs["std"], step_ptr=self.step, n=self.B)
+            emit(L.OP_FILL, dst=self.unet.std.tensor, tab=self.tabs["std"], step_ptr=self.step, n=self.B)
         if self.plan["corrector"] == "ald":
-            emit(L.OP_FILL, L.FillArgs, dst=self.gss, tab=self.tabs["ald_one"], step_ptr=self.step, n=self.B)
-            emit(L.OP_FILL, L.FillArgs, dst=self.zss, tab=self.tabs["ald_std2"], step_ptr=self.step, n=self.B)
+            emit(L.OP_FILL, dst=self.gss, tab=self.tabs["ald_one"], step_ptr=self.step, n=self.B)
+            emit(L.OP_FILL, dst=self.zss, tab=self.tabs["ald_std2"], step_ptr=self.step, n=self.B)
         if self.plan["corrector"] in ("langevin", "ald"):
             for k in range(self.n_steps):
                 emit_unet()
                 if with_rng:
-                    emit(L.OP_RANDN, L.RandnArgs, dst=self.z_c, numel=self.B * self.per, seed=0, seed_ptr=self.seed_word, step_ptr=self.step, stream_id=k)
+                    emit(L.OP_RANDN, dst=self.z_c, numel=self.B * self.per, seed=0, seed_ptr=self.seed_word, step_ptr=self.step, stream_id=k)
                 if self.plan["corrector"] == "langevin":
-                    emit(L.OP_SUMSQ, L.SumsqArgs, a=score, b=self.z_c, out_a=self.gss, out_b=self.zss, n=self.B, per=self.per)
-                emit(L.OP_LANGEVIN, L.LangevinArgs, x=self.x, x_mean=self.x_mean, grad=score, noise=self.z_c,
+                    emit(L.OP_SUMSQ, a=score, b=self.z_c, out_a=self.gss, out_b=self.zss, n=self.B, per=self.per)
+                emit(L.OP_LANGEVIN, x=self.x, x_mean=self.x_mean, grad=score, noise=self.z_c,
                      grad_sumsq=self.gss, noise_sumsq=self.zss, alpha_tab=self.tabs.get("alpha"), step_ptr=self.step,
                      n=self.B, per=self.per, snr=self.snr)
         emit_projection(self.z_pc if self.projection is not None else None, 9)
         if self.plan["predictor"] != "none":
             emit_unet()
             if with_rng:
-                emit(L.OP_RANDN, L.RandnArgs, dst=self.z_p, numel=self.B * self.per, seed=0, seed_ptr=self.seed_word, step_ptr=self.step, stream_id=8)
-            emit(L.OP_PREDICTOR, L.PredictorArgs, x=self.x, x_mean=self.x_mean, score=score, noise=self.z_p,
+                emit(L.OP_RANDN, dst=self.z_p, numel=self.B * self.per, seed=0, seed_ptr=self.seed_word, step_ptr=self.step, stream_id=8)
+            emit(L.OP_PREDICTOR, x=self.x, x_mean=self.x_mean, score=score, noise=self.z_p,
                  coef=self.tabs["coef"], step_ptr=self.step, numel=self.B * self.per)
         emit_projection(self.z_pp if self.projection is not None else None, 10)
-        emit(L.OP_STEP_INC, L.StepIncArgs, step_ptr=self.step, delta=1)
-        return E.Program(L.op_array(ops), classes, flops, self)
+        emit(L.OP_STEP_INC, step_ptr=self.step, delta=1)
+        return E.Program.of(parts, self)
 
     def step_program(self, with_rng=True):
         if with_rng not in self._programs:
@@ -278,11 +268,5 @@ class FusedPCSampler:
             return
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=self.device)
-        s = self._stream
-        s.wait_stream(torch.cuda.current_stream())
-        if prog._graph is None:
-            prog.capture(s)
-        for _ in range(steps):
-            prog.replay(s)
-        torch.cuda.current_stream().wait_stream(s)
+        prog.replay_from_current(self._stream, times=steps)
         self.last_path = "fused-graph"

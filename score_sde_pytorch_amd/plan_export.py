@@ -22,6 +22,7 @@ import struct
 import torch
 
 from . import _lib as L
+from . import engine as E
 
 MAGIC = b"SSDEPLN1"
 REGION_ZERO, REGION_CONST = 0, 1
@@ -56,18 +57,7 @@ class PlanParam(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("region", C.c_int32), ("_pad0", C.c_int32), ("offset", C.c_int64), ("numel", C.c_int64)]
 
 
-_pointer_fields = L.pointer_offsets      # (byte offset, ) of every pointer field: nested structures and arrays of them included
-
-
-_OP_PTRS = {}
-
-
-def _op_pointer_offsets(kind):
-    if kind not in _OP_PTRS:
-        member = L._UNION_FIELD[kind]
-        cls = dict(L._OpUnion._fields_)[member]
-        _OP_PTRS[kind] = _pointer_fields(cls, L.Op.u.offset)
-    return _OP_PTRS[kind]
+_op_pointer_offsets = L._op_pointer_offsets      # byte offset of every pointer field of an op of a kind
 
 
 class _Regions:
@@ -115,54 +105,39 @@ def _collect_unet(regions, eng):
     for i, t in enumerate(eng.b.keep):
         regions.add(t, REGION_CONST, "table%d" % i)
     for i, e in enumerate(eng.weights.entries):
-        regions.add(e[0], REGION_CONST, "packed%d" % i)
-        for s in e[1]:
+        regions.add(e.packed, REGION_CONST, "packed%d" % i)
+        for s in e.sources:
             regions.add(s.detach(), REGION_CONST, "param")
-    if getattr(eng.weights, "_tables", None) is None:
-        eng.weights._build_tables()
-    for i, (_, raw) in enumerate(eng.weights._tables[0]):
+    for i, (_, raw) in enumerate(eng.weights.pack_tables()):
         regions.add(raw, REGION_CONST, "packtab%d" % i)
 
 
 def _emit(kind, regions, ops, n_ops, eng_unet, model, io_tensors, batch, shape, nfe, sde_steps, seg=(0, 0, 0, 0), n_flat=0):
     regions.freeze()
     relocs = []
+
+    def relocate(raw, offsets, target_kind, index, base=0):
+        """zero every pointer of `raw` at base + offsets and record it as a relocation of target (target_kind, index)"""
+        for off, addr in L.pointers_at(raw, offsets, base):
+            relocs.append((target_kind, index, off) + regions.find(addr))
+            struct.pack_into("<Q", raw, off, 0)
+        return raw
+
     op_bytes = bytearray()
     for i in range(n_ops):
-        raw = bytearray(bytes(ops[i]))
-        for off in _op_pointer_offsets(int(ops[i].kind)):
-            (addr,) = struct.unpack_from("<Q", raw, off)
-            if addr:
-                rid, roff = regions.find(addr)
-                relocs.append((RELOC_OP, i, off, rid, roff))
-                struct.pack_into("<Q", raw, off, 0)
-        op_bytes += raw
+        op_bytes += relocate(bytearray(bytes(ops[i])), _op_pointer_offsets(int(ops[i].kind)), RELOC_OP, i)
     # ---- weight refresh program: one ssde_pack_weights launch per descriptor table
     refresh = bytearray()
-    tables = eng_unet.weights._tables[0]
-    desc_ptrs = _pointer_fields(L.PackDesc)
+    tables = eng_unet.weights.pack_tables()
+    desc_ptrs = L.pointer_offsets(L.PackDesc)
     table_patches = {}
-    for j, (args, raw_t) in enumerate(tables):
-        op = L.make_op(L.OP_PACK, args)
-        rawop = bytearray(bytes(op))
-        for off in _op_pointer_offsets(L.OP_PACK):
-            (addr,) = struct.unpack_from("<Q", rawop, off)
-            if addr:
-                rid, roff = regions.find(addr)
-                relocs.append((RELOC_REFRESH_OP, j, off, rid, roff))
-                struct.pack_into("<Q", rawop, off, 0)
-        refresh += rawop
+    for j, ((args, raw_t), op) in enumerate(zip(tables, eng_unet.weights.pack_ops())):
+        refresh += relocate(bytearray(bytes(op)), _op_pointer_offsets(L.OP_PACK), RELOC_REFRESH_OP, j)
         # pointers inside the table
         tid, toff0 = regions.find(raw_t.data_ptr())
         tb = bytearray(regions.data(tid))
         for d in range(int(args.count)):
-            for off in desc_ptrs:
-                pos = toff0 + d * C.sizeof(L.PackDesc) + off
-                (addr,) = struct.unpack_from("<Q", tb, pos)
-                if addr:
-                    rid, roff = regions.find(addr)
-                    relocs.append((RELOC_REGION, tid, pos, rid, roff))
-                    struct.pack_into("<Q", tb, pos, 0)
+            relocate(tb, desc_ptrs, RELOC_REGION, tid, toff0 + d * C.sizeof(L.PackDesc))
         table_patches[tid] = bytes(tb)
     # ---- parameters by state_dict name
     params = []
@@ -268,14 +243,10 @@ def export_train_plan(fs, optimizer=None, ema=None):
     regions.add(fs.flat.grad, REGION_ZERO, "flat_grad")
     for name in ("z", "batch", "a", "s", "g2", "losses", "loss", "hyper", "gnorm", "partial"):
         regions.add(getattr(fs, name), REGION_ZERO, name)
-    head_ops = lambda prog: [prog.ops[i] for i in range(prog.n)]                 # noqa: E731
-    ops = head_ops(fs._head[0])
-    seg0 = len(ops)
-    ops += [eng.program.ops[i] for i in range(eng.n_fwd)]
-    seg1 = len(ops)
-    ops += head_ops(fs._head[1])
-    seg2 = len(ops)
-    ops += [eng.program.ops[i] for i in range(eng.n_fwd, eng.program.n)]
+    parts = [fs._head[0], eng.program[:eng.n_fwd], fs._head[1], eng.program[eng.n_fwd:]]
+    seg0 = fs._head[0].n
+    seg1 = seg0 + eng.n_fwd
+    seg2 = seg1 + fs._head[1].n
     seg3 = 0
     if optimizer is not None:
         m, v = optimizer.flatten_like(fs.flat)
@@ -283,8 +254,9 @@ def export_train_plan(fs, optimizer=None, ema=None):
         regions.add(v, REGION_CONST, "adam_v")
         if ema is not None:
             regions.add(ema.flatten_like(fs.flat), REGION_CONST, "ema")
-        seg3 = len(ops)
-        ops += head_ops(fs._optimizer_program(optimizer, ema))
+        seg3 = seg2 + eng.program.n - eng.n_fwd
+        parts.append(fs._optimizer_program(optimizer, ema))
+    prog = E.Program.of(parts, fs)
     io = {IO_X: eng.x_in.tensor, IO_COND: eng.cond.tensor, IO_OUT: eng.out.tensor, IO_BATCH: fs.batch, IO_Z: fs.z, IO_A: fs.a,
           IO_S: fs.s, IO_LOSS: fs.loss, IO_HYPER: fs.hyper, IO_GOUT: eng.gout.tensor, IO_GRAD: fs.flat.grad, IO_PARAMS: fs.flat.data}
     if fs.spec["likelihood_weighting"]:
@@ -297,8 +269,7 @@ def export_train_plan(fs, optimizer=None, ema=None):
         io[IO_DROP_SEED] = eng.drop_seed
     if eng.gx is not None:
         io[IO_GX] = eng.gx.tensor
-    arr = L.op_array(ops)
-    return _emit(PLAN_TRAIN, regions, arr, len(ops), eng, fs.model, io, eng.n, (eng.channels, eng.h, eng.w), 1, 0,
+    return _emit(PLAN_TRAIN, regions, prog.ops, prog.n, eng, fs.model, io, eng.n, (eng.channels, eng.h, eng.w), 1, 0,
                  seg=(seg0, seg1, seg2, seg3), n_flat=fs.flat.numel)
 
 

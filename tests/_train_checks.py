@@ -841,19 +841,19 @@ def check_device_repack(dev, kind="ncsnpp", need_kind=None):
     ws = eng.weights
     eng.flat.data.add_(torch.randn(eng.flat.numel, generator=torch.Generator().manual_seed(5)).to(dev) * 0.1)
     ws.refresh(force=True, on_device=False)
-    ref = [e[0].clone() for e in ws.entries]
+    ref = [e.packed.clone() for e in ws.entries]
     for e in ws.entries:
-        if e[4] is not None:
-            e[0].fill_(7.0) if e[4][0]["kind"] in (1, 2) else e[0].zero_()   # matrix / vector kernels keep the zero padding
+        if e.recipe is not None:
+            e.packed.fill_(7.0) if e.recipe[0]["kind"] in (1, 2) else e.packed.zero_()   # matrix / vector kernels keep the zero padding
     assert ws.device_refresh()
     n = 0
     for e, r in zip(ws.entries, ref):
-        if e[4] is not None:
-            assert float((e[0] - r).abs().max()) < 1e-6, (e[4][0]["kind"], e[4][0].get("flags"), tuple(e[0].shape))
+        if e.recipe is not None:
+            assert float((e.packed - r).abs().max()) < 1e-6, (e.recipe[0]["kind"], e.recipe[0].get("flags"), tuple(e.packed.shape))
             n += 1
     assert n >= len(ws.entries) - 2
     if need_kind is not None:                     # the pack kind under test is really in this store, forward and input-gradient
-        flags = {d.get("flags", 0) for e in ws.entries if e[4] is not None for d in e[4] if d["kind"] == need_kind}
+        flags = {d.get("flags", 0) for e in ws.entries if e.recipe is not None for d in e.recipe if d["kind"] == need_kind}
         assert flags == {0, 1}, flags
 
 

@@ -321,17 +321,17 @@ def test_ema_swap_and_restore_invalidate_packed_weights():
         for s in ema.shadow_params:
             s.mul_(1.25)
     w = model.all_modules[3].weight                                    # first conv
-    entry = next(e for e in eng.weights.entries if any(src is w for src in e[1]))
-    before = entry[0].clone()
+    entry = next(e for e in eng.weights.entries if any(src is w for src in e.sources))
+    before = entry.packed.clone()
     ema.store(model.parameters())
     ema.copy_to(model.parameters())
     eng.weights.refresh(on_device=False)
-    swapped = entry[0].clone()
+    swapped = entry.packed.clone()
     assert not torch.equal(before, swapped)
     assert torch.allclose(swapped, before * 1.25)
     ema.restore(model.parameters())
     eng.weights.refresh(on_device=False)
-    assert torch.equal(entry[0], before)
+    assert torch.equal(entry.packed, before)
 
 
 def test_grad_run_extents_are_recorded():
