@@ -548,8 +548,8 @@ typedef struct ssde_axpy_args {   /* dst = (acc ? dst : 0) + alpha * x, optional
   const float* x; const float* gate; float* dst; int64_t numel; float alpha; int32_t acc;
 } ssde_axpy_args;
 
-/* ---- adaptive RK45 (Dormand-Prince) stage arithmetic on the device ------------------
- * replaces the numpy side of scipy.integrate.solve_ivp(method='RK45') as the reference drives it
+/* ---- adaptive explicit Runge-Kutta (scipy's RK45, RK23, DOP853) stage arithmetic on the device ------------------
+ * replaces the numpy side of scipy.integrate.solve_ivp(method=...) as the reference drives it
  * (sampling.py:466-475, likelihood.py:90-99): fp64 state and stage slopes K[7][n] stay in HBM. */
 typedef struct ssde_rk_coefs { double v[7]; } ssde_rk_coefs;
 typedef struct ssde_rk_combine_args {     /* dst = y + sum_{j < terms} coef[j] * K[j]   (coef = a_sj * h); dst32 = (float)dst or NULL */
@@ -560,6 +560,26 @@ typedef struct ssde_rk_error_args {       /* out[0] = sqrt(mean(((sum_j coef[j] 
   const double* y; const double* y_new; const double* k; int64_t n; ssde_rk_coefs coef; double atol, rtol;
   double* partial; int32_t partial_len; int32_t _pad0; double* out;
 } ssde_rk_error_args;
+/* The same two launches for any explicit Runge-Kutta table of up to 12 stages (scipy's RK23, RK45, DOP853): K holds up to
+ * SSDE_RK_MAX_ROWS slope rows of n doubles.  A row whose coefficient is zero (in both rows of the pair form) is NOT read, so
+ * rows a method never fills may hold anything.  The two entry points above are these with 7 rows. */
+#define SSDE_RK_MAX_TERMS 12
+#define SSDE_RK_MAX_ROWS 13
+typedef struct ssde_rk_combine_rows_args { /* dst = y + sum_{j < terms} coef[j] * K[j], j ascending; dst32 / n32 as above */
+  const double* y; const double* k; int64_t n; int32_t terms; int32_t _pad0; double coef[SSDE_RK_MAX_TERMS]; double* dst; float* dst32;
+  int64_t n32;
+} ssde_rk_combine_rows_args;
+typedef struct ssde_rk_error_rows_args {
+  /* scale_i = atol + max(|y_i|, |y_new_i|) rtol, over `rows` <= 13 slope rows.
+   * pair == 0 (RK23, RK45): out[0] = sqrt(mean_i((sum_j coef[j] K[j][i] / scale_i)^2)), coef = E_j * h; coef2, h_abs unused.
+   * pair != 0 (DOP853): s5 = sum_i (sum_j coef[j] K[j][i] / scale_i)^2 with coef = E5, s3 likewise with coef2 = E3 (neither
+   *   scaled by h); out[0] = 0 if s5 == 0 and s3 == 0, else h_abs * s5 / sqrt((s5 + 0.01 s3) n).
+   * partial: per-block sums in block order, finished by one thread (no atomics: accept / reject decisions are deterministic).
+   * The single form uses up to 1024 of them; the pair form up to 512 per sum, s5's then s3's: partial_len >= 2 * blocks. */
+  const double* y; const double* y_new; const double* k; int64_t n; int32_t rows; int32_t pair;
+  double coef[SSDE_RK_MAX_ROWS]; double coef2[SSDE_RK_MAX_ROWS]; double h_abs; double atol, rtol;
+  double* partial; int32_t partial_len; int32_t _pad0; double* out;
+} ssde_rk_error_rows_args;
 /* Per-evaluation scalars of an ODE right-hand side, in DEVICE memory, so that one captured hipGraph (fill labels ->
  * U-Net program -> drift [-> input-gradient program -> divergence]) serves every evaluation of an adaptive solve: the
  * host uploads this record (24 bytes) before each replay.  label / std are read by SSDE_OP_FILL (tab = &rec.label, ...). */
@@ -608,6 +628,8 @@ int ssde_step_inc(const ssde_step_inc_args* a, void* stream);
 int ssde_project_update(const ssde_project_args* a, void* stream);
 int ssde_rk_combine(const ssde_rk_combine_args* a, void* stream);
 int ssde_rk_error_norm(const ssde_rk_error_args* a, void* stream);
+int ssde_rk_combine_rows(const ssde_rk_combine_rows_args* a, void* stream);
+int ssde_rk_error_norm_rows(const ssde_rk_error_rows_args* a, void* stream);
 int ssde_pf_drift(const ssde_pf_drift_args* a, void* stream);
 int ssde_hutch_div(const ssde_hutch_div_args* a, void* stream);
 int ssde_conv_wgrad(const ssde_wgrad_args* a, void* stream);
@@ -695,7 +717,8 @@ enum { SSDE_IO_X = 0, SSDE_IO_COND = 1, SSDE_IO_SIGMA = 2, SSDE_IO_STD = 3, SSDE
        SSDE_IO_BATCH = 8, SSDE_IO_Z = 9, SSDE_IO_A = 10, SSDE_IO_S = 11, SSDE_IO_G2 = 12, SSDE_IO_LOSS = 13, SSDE_IO_HYPER = 14,
        SSDE_IO_DROP_SEED = 15, SSDE_IO_GOUT = 16, SSDE_IO_GX = 17, SSDE_IO_GRAD = 18, SSDE_IO_PARAMS = 19,
        /* ODE plans (SSDE_PLAN_ODE, SSDE_PLAN_LIKELIHOOD; state length N = B*C*H*W, plus B running log-density terms in a
-        * likelihood plan): the ssde_ode_dyn record; the seven fp64 slope rows K[7][N]; the solver's state block; the
+        * likelihood plan): the ssde_ode_dyn record; the fp64 slope rows K[rows][N] -- rows = region bytes / (8 N), at least the
+        * 7 of RK45 (which RK23 fits in), 13 in a plan exported for DOP853 (n_stages + 1) --; the solver's state block; the
         * Hutchinson probe [B*C*H*W] fp32 (likelihood plans only).  Layout of the state block, in doubles:
         *   [0, N) and [N, 2N) the two state buffers (they swap roles when a step is accepted), [2N, 3N) the stage argument,
         *   [3N, 3N + SSDE_ODE_PARTIALS) the error-norm partials, [3N + SSDE_ODE_PARTIALS] the error norm */
@@ -764,14 +787,19 @@ int ssde_plan_copy_io(ssde_plan* p, int32_t slot, void* buf, int64_t bytes, int3
 int ssde_pc_state(ssde_plan* p, float* x, float* x_mean, void* stream);
 /* ---- ODE plans (SSDE_PLAN_ODE / SSDE_PLAN_LIKELIHOOD, exported from ode.FusedDrift / ode.FusedLikelihoodRhs by
  * plan_export.export_ode_plan) ----
- * replaces scipy.integrate.solve_ivp(method='RK45') around the network as the reference's get_ode_sampler and
- * get_likelihood_fn drive it (sampling.py:449-483, likelihood.py:69-111): the adaptive Dormand-Prince loop of ode.solve_rk45,
- * with the exported right-hand-side program run (or replayed as one hipGraph) once per evaluation and the stage arithmetic
- * done by the rk_combine / rk_error_norm launches.  The library holds no SDE formulas: the host's callback supplies the four
+ * replaces scipy.integrate.solve_ivp(method=...) around the network as the reference's get_ode_sampler and
+ * get_likelihood_fn drive it (sampling.py:449-483, likelihood.py:69-111): the adaptive loop of ode.solve_rk, with the
+ * exported right-hand-side program run (or replayed as one hipGraph) once per evaluation and the stage arithmetic done by
+ * the rk_combine / rk_error_norm launches.  Methods: scipy's explicit ones, reproduced step for step -- RK45 (Dormand-Prince
+ * 5(4), the reference's default; 6 evaluations a step), RK23 (Bogacki-Shampine 3(2); 3) and DOP853 (8(5,3); 12).  A solve
+ * needs n_stages + 1 slope rows in SSDE_IO_ODE_K: every plan holds the 7 of RK45, which RK23 fits in; DOP853 needs a plan
+ * exported for it (13 rows) and fails on a smaller one, naming both counts.  The implicit methods (Radau, BDF, LSODA) need
+ * Jacobians and have no device driver.  The library holds no SDE formulas: the host's callback supplies the four
  * floats of ssde_ode_dyn at time t -- label, the second scalar (marginal std of a VP / sub-VP model, or the sigma a
  * scale_by_sigma VE model divides by), a and g2 -- and returns non-zero to abort the solve.  x0, probe, x, slope and
  * delta_logp are DEVICE pointers.  After the solve the host applies what the reference does around the integration
  * (denoising step, inverse scaler, prior log-density and the bits/dim constant). */
+enum { SSDE_ODE_RK45 = 0, SSDE_ODE_RK23 = 1, SSDE_ODE_DOP853 = 2 };
 typedef int (*ssde_ode_scalars_fn)(double t, void* user, float out[4]);
 /* load the initial state (x0 [B,C,H,W] fp32; the log-density terms start at 0) and, in a likelihood plan, the probe */
 int ssde_ode_reset(ssde_plan* p, const float* x0, const float* probe, void* stream);
@@ -781,6 +809,9 @@ int ssde_ode_eval(ssde_plan* p, double t, ssde_ode_scalars_fn scalars, void* use
  * max_nfev bounds the evaluations (0 = 100000); *nfev receives the count.  The call returns with the stream idle. */
 int ssde_ode_solve(ssde_plan* p, double t0, double t1, double rtol, double atol, ssde_ode_scalars_fn scalars, void* user,
                    int32_t use_graph, int32_t max_nfev, int32_t* nfev, void* stream);
+/* the same with the integrator chosen (SSDE_ODE_*); ssde_ode_solve is this with SSDE_ODE_RK45 */
+int ssde_ode_solve_method(ssde_plan* p, int32_t method, double t0, double t1, double rtol, double atol, ssde_ode_scalars_fn scalars,
+                          void* user, int32_t use_graph, int32_t max_nfev, int32_t* nfev, void* stream);
 /* the current state: x [B,C,H,W] fp32 (or NULL), delta_logp [B] fp64 (likelihood plans; else NULL) */
 int ssde_ode_state(ssde_plan* p, float* x, double* delta_logp, void* stream);
 

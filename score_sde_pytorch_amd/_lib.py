@@ -79,6 +79,19 @@ class RkErrorArgs(C.Structure):
                 ("rtol", C.c_double), ("partial", _fp), ("partial_len", C.c_int32), ("_pad0", C.c_int32), ("out", _fp)]
 
 
+class RkCombineRowsArgs(C.Structure):
+    """include/ssde.h: ssde_rk_combine_rows_args (up to 12 terms)"""
+    _fields_ = [("y", _fp), ("k", _fp), ("n", C.c_int64), ("terms", C.c_int32), ("_pad0", C.c_int32), ("coef", C.c_double * 12),
+                ("dst", _fp), ("dst32", _fp), ("n32", C.c_int64)]
+
+
+class RkErrorRowsArgs(C.Structure):
+    """include/ssde.h: ssde_rk_error_rows_args (up to 13 slope rows; pair form: coef = E5, coef2 = E3, h_abs = |h|)"""
+    _fields_ = [("y", _fp), ("y_new", _fp), ("k", _fp), ("n", C.c_int64), ("rows", C.c_int32), ("pair", C.c_int32),
+                ("coef", C.c_double * 13), ("coef2", C.c_double * 13), ("h_abs", C.c_double), ("atol", C.c_double), ("rtol", C.c_double),
+                ("partial", _fp), ("partial_len", C.c_int32), ("_pad0", C.c_int32), ("out", _fp)]
+
+
 class PfDriftArgs(C.Structure):
     _fields_ = [("x", _fp), ("score", _fp), ("dst", _fp), ("numel", C.c_int64), ("a", C.c_float), ("g2", C.c_float), ("dyn", _fp)]
 
@@ -296,13 +309,13 @@ EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attent
            "ssde_abi_version", "ssde_sizeof_op", "ssde_last_error", "ssde_conv_lds_bytes",
            "ssde_conv_wgrad", "ssde_colsum", "ssde_gn_bwd_reduce", "ssde_prologue_bwd", "ssde_attention_bwd",
            "ssde_perturb", "ssde_dsm_loss", "ssde_sumsq_flat", "ssde_adam_clip_ema", "ssde_memset", "ssde_axpy",
-           "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_conv_ws_floats", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
+           "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_conv_ws_floats", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_rk_combine_rows", "ssde_rk_error_norm_rows", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
            "ssde_gn_apply", "ssde_gn_apply_bwd",
            # plan-level entry points (csrc/plan.hip; argument types: plan_export.bind)
            "ssde_plan_load", "ssde_plan_load_file", "ssde_plan_destroy", "ssde_plan_info", "ssde_plan_param",
            "ssde_plan_refresh_weights", "ssde_unet_forward", "ssde_pc_reset", "ssde_pc_run", "ssde_pc_state",
            "ssde_train_step", "ssde_train_forward", "ssde_unet_backward", "ssde_plan_copy_io",
-           "ssde_ode_reset", "ssde_ode_eval", "ssde_ode_solve", "ssde_ode_state"]
+           "ssde_ode_reset", "ssde_ode_eval", "ssde_ode_solve", "ssde_ode_solve_method", "ssde_ode_state"]
 
 _lib = None
 
@@ -390,6 +403,8 @@ def bind(lib):
             getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
     lib.ssde_rk_combine.argtypes = [C.POINTER(RkCombineArgs), C.c_void_p]
     lib.ssde_rk_error_norm.argtypes = [C.POINTER(RkErrorArgs), C.c_void_p]
+    lib.ssde_rk_combine_rows.argtypes = [C.POINTER(RkCombineRowsArgs), C.c_void_p]
+    lib.ssde_rk_error_norm_rows.argtypes = [C.POINTER(RkErrorRowsArgs), C.c_void_p]
     lib.ssde_sample_update.argtypes = [C.POINTER(SampleUpdateArgs), C.c_void_p]
     lib.ssde_conv_lds_bytes.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_attention_route.argtypes = [C.POINTER(AttnArgs)]

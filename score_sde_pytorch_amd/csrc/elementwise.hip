@@ -4,6 +4,8 @@
 // bit-for-bit against the reference's torch expression order uses __fmul_rn /
 // __fadd_rn so hipcc cannot contract it into FMAs.
 #include "ssde_common.h"
+#include <math.h>
+#include <string.h>
 #include <rocrand/rocrand_kernel.h>
 
 namespace {
@@ -314,47 +316,78 @@ extern "C" int ssde_sumsq(const ssde_sumsq_args* a, void* stream) {
   return SSDE_OK;
 }
 
-// ---- Dormand-Prince RK45 stage arithmetic for the probability-flow ODE sampler / likelihood (sampling.py:466-475,
-// likelihood.py:90-99: scipy.integrate.solve_ivp on fp64 numpy state in the reference).  The fp64 state and the 7 stage
-// slopes K_j live on the device; one launch forms a stage argument (and its fp32 copy, the U-Net input: the reference
-// casts the state to float32 per evaluation, models/utils.py:186-188), one launch + a fixed-order finish form scipy's
-// RMS error norm -- the only scalar the host reads per step.
-__global__ __launch_bounds__(256) void rk_combine_kernel(const double* __restrict__ y, const double* __restrict__ k, size_t n, int terms,
-                                                         ssde_rk_coefs c, double* __restrict__ dst, float* __restrict__ dst32, size_t n32) {
+// ---- explicit Runge-Kutta stage arithmetic for the probability-flow ODE sampler / likelihood (sampling.py:466-475,
+// likelihood.py:90-99: scipy.integrate.solve_ivp on fp64 numpy state in the reference; its RK23, RK45 and DOP853).  The
+// fp64 state and the stage slopes K_j (up to 13 rows) live on the device; one launch forms a stage argument (and its fp32
+// copy, the U-Net input: the reference casts the state to float32 per evaluation, models/utils.py:186-188), one launch +
+// a fixed-order finish form scipy's error norm -- the only scalar the host reads per step.  One kernel each for every
+// method: the launcher passes the rows with a non-zero coefficient, in ascending order, so a row a method never fills
+// (or fills later in the step) is not read.  Adding a row times zero changes no bit of a finite sum, so leaving it out
+// gives what the seven-row kernels of the Dormand-Prince driver gave.
+struct rk_terms {
+  int count;                          // rows read
+  int row[SSDE_RK_MAX_ROWS];          // their indices into K, ascending
+  double c[SSDE_RK_MAX_ROWS];         // coefficient per row read
+  double c2[SSDE_RK_MAX_ROWS];        // pair form of the error norm: the second coefficient row (E3 beside E5)
+};
+
+__global__ __launch_bounds__(256) void rk_combine_kernel(const double* __restrict__ y, const double* __restrict__ k, size_t n, rk_terms c,
+                                                         double* __restrict__ dst, float* __restrict__ dst32, size_t n32) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     // scipy: dy = np.dot(K[:s].T, a[:s]) * h ; y + dy   -- here a_j * h is folded on the host, summed j = 0, 1, ...
     double dy = 0.0;
-    for (int j = 0; j < terms; ++j) dy += k[(size_t)j * n + i] * c.v[j];
+    for (int t = 0; t < c.count; ++t) dy += k[(size_t)c.row[t] * n + i] * c.c[t];
     const double v = y[i] + dy;
     dst[i] = v;
     if (dst32 && i < n32) dst32[i] = (float)v;
   }
 }
 
+// partial[blockIdx.x] = this block's sum of (sum_j c_j K_j / scale)^2; pair form: partial[gridDim.x + blockIdx.x] the same with c2
 __global__ __launch_bounds__(256) void rk_error_kernel(const double* __restrict__ y, const double* __restrict__ y_new, const double* __restrict__ k,
-                                                       size_t n, ssde_rk_coefs c, double atol, double rtol, double* __restrict__ partial) {
+                                                       size_t n, rk_terms c, int pair, double atol, double rtol, double* __restrict__ partial) {
   SSDE_LDS(smem);
-  double* red = reinterpret_cast<double*>(smem);      // [4]
-  double acc = 0.0;
+  double* red = reinterpret_cast<double*>(smem);      // [2][4]
+  double acc = 0.0, acc2 = 0.0;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    double e = 0.0;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) e += k[(size_t)j * n + i] * c.v[j];          // E_j * h folded on the host
+    double e = 0.0, e2 = 0.0;
+    for (int t = 0; t < c.count; ++t) {
+      const double v = k[(size_t)c.row[t] * n + i];
+      e += v * c.c[t];                                                         // single form: E_j * h folded on the host
+      if (pair) e2 += v * c.c2[t];
+    }
     const double scale = atol + fmax(fabs(y[i]), fabs(y_new[i])) * rtol;
-    const double q = e / scale;
+    const double q = e / scale, q2 = e2 / scale;
     acc += q * q;
+    acc2 += q2 * q2;
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  for (int o = 32; o > 0; o >>= 1) {
+    acc += __shfl_xor(acc, o, 64);
+    acc2 += __shfl_xor(acc2, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = acc;
+    red[4 + (threadIdx.x >> 6)] = acc2;
+  }
   __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (pair) partial[gridDim.x + blockIdx.x] = (red[4] + red[5]) + (red[6] + red[7]);
+  }
 }
-__global__ void rk_error_finish_kernel(const double* __restrict__ partial, int blocks, size_t n, double* __restrict__ out) {
+// single form: sqrt(s / n), scipy's RMS norm.  Pair form (scipy's DOP853._estimate_error_norm):
+// |h| s5 / sqrt((s5 + 0.01 s3) n), and 0 when both sums are 0.
+__global__ void rk_error_finish_kernel(const double* __restrict__ partial, int blocks, size_t n, int pair, double h_abs, double* __restrict__ out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    double s = 0.0;
+    double s = 0.0, s3 = 0.0;
     for (int i = 0; i < blocks; ++i) s += partial[i];       // fixed order: deterministic accept / reject decisions
-    out[0] = sqrt(s / (double)n);
+    if (!pair) {
+      out[0] = sqrt(s / (double)n);
+      return;
+    }
+    for (int i = 0; i < blocks; ++i) s3 += partial[blocks + i];
+    out[0] = (s == 0.0 && s3 == 0.0) ? 0.0 : h_abs * s / sqrt((s + 0.01 * s3) * (double)n);
   }
 }
 
@@ -394,24 +427,64 @@ __global__ __launch_bounds__(256) void hutch_div_kernel(const float* __restrict_
   if (threadIdx.x == 0) dst[dst_off + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-extern "C" int ssde_rk_combine(const ssde_rk_combine_args* a, void* stream) {
-  SSDE_REQUIRE(a && a->y && a->dst && a->n > 0 && a->terms >= 0 && a->terms <= 7 && (a->terms == 0 || a->k), "rk_combine: bad args");
+// the rows with a non-zero coefficient (in either row of the pair form), ascending
+static rk_terms rk_active_terms(const double* coef, const double* coef2, int rows) {
+  rk_terms t;
+  memset(&t, 0, sizeof(t));
+  for (int j = 0; j < rows; ++j) {
+    if (coef[j] == 0.0 && !(coef2 && coef2[j] != 0.0)) continue;
+    t.row[t.count] = j;
+    t.c[t.count] = coef[j];
+    t.c2[t.count] = coef2 ? coef2[j] : 0.0;
+    t.count++;
+  }
+  return t;
+}
+
+extern "C" int ssde_rk_combine_rows(const ssde_rk_combine_rows_args* a, void* stream) {
+  SSDE_REQUIRE(a && a->y && a->dst && a->n > 0 && a->n32 >= 0, "rk_combine: bad args");
+  SSDE_REQUIRE(a->terms >= 0 && a->terms <= SSDE_RK_MAX_TERMS && (a->terms == 0 || a->k), "rk_combine: terms = %d, at most %d (with K)",
+               a->terms, SSDE_RK_MAX_TERMS);
   hipLaunchKernelGGL(rk_combine_kernel, dim3(grid_for((size_t)a->n)), dim3(256), 0, static_cast<hipStream_t>(stream), a->y, a->k, (size_t)a->n,
-                     a->terms, a->coef, a->dst, a->dst32, a->n32 > 0 ? (size_t)a->n32 : (size_t)a->n);
+                     rk_active_terms(a->coef, nullptr, a->terms), a->dst, a->dst32, a->n32 > 0 ? (size_t)a->n32 : (size_t)a->n);
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
 }
 
-extern "C" int ssde_rk_error_norm(const ssde_rk_error_args* a, void* stream) {
+extern "C" int ssde_rk_error_norm_rows(const ssde_rk_error_rows_args* a, void* stream) {
   SSDE_REQUIRE(a && a->y && a->y_new && a->k && a->partial && a->out && a->n > 0, "rk_error_norm: bad args");
-  const unsigned blocks = grid_for((size_t)a->n, 256, 1024);
-  SSDE_REQUIRE((int)blocks <= a->partial_len, "rk_error_norm: partial buffer needs %u doubles", blocks);
+  SSDE_REQUIRE(a->rows >= 1 && a->rows <= SSDE_RK_MAX_ROWS, "rk_error_norm: rows = %d, 1 to %d", a->rows, SSDE_RK_MAX_ROWS);
+  SSDE_REQUIRE(!a->pair || (a->h_abs >= 0 && isfinite(a->h_abs)), "rk_error_norm: the pair form needs a finite |h|");
+  const int pair = a->pair != 0;
+  const unsigned blocks = grid_for((size_t)a->n, 256, pair ? 512 : 1024);
+  SSDE_REQUIRE((int64_t)blocks * (pair ? 2 : 1) <= (int64_t)a->partial_len, "rk_error_norm: partial buffer needs %u doubles", blocks * (pair ? 2 : 1));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rk_error_kernel, dim3(blocks), dim3(256), 64, st, a->y, a->y_new, a->k, (size_t)a->n, a->coef, a->atol, a->rtol, a->partial);
+  hipLaunchKernelGGL(rk_error_kernel, dim3(blocks), dim3(256), 64, st, a->y, a->y_new, a->k, (size_t)a->n,
+                     rk_active_terms(a->coef, pair ? a->coef2 : nullptr, a->rows), pair, a->atol, a->rtol, a->partial);
   SSDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rk_error_finish_kernel, dim3(1), dim3(64), 0, st, a->partial, (int)blocks, (size_t)a->n, a->out);
+  hipLaunchKernelGGL(rk_error_finish_kernel, dim3(1), dim3(64), 0, st, a->partial, (int)blocks, (size_t)a->n, pair, a->h_abs, a->out);
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
+}
+
+// the Dormand-Prince entry points: the same launches with seven rows
+extern "C" int ssde_rk_combine(const ssde_rk_combine_args* a, void* stream) {
+  SSDE_REQUIRE(a && a->y && a->dst && a->n > 0 && a->terms >= 0 && a->terms <= 7 && (a->terms == 0 || a->k), "rk_combine: bad args");
+  ssde_rk_combine_rows_args r;
+  memset(&r, 0, sizeof(r));
+  r.y = a->y; r.k = a->k; r.n = a->n; r.terms = a->terms; r.dst = a->dst; r.dst32 = a->dst32; r.n32 = a->n32;
+  for (int j = 0; j < a->terms; ++j) r.coef[j] = a->coef.v[j];
+  return ssde_rk_combine_rows(&r, stream);
+}
+
+extern "C" int ssde_rk_error_norm(const ssde_rk_error_args* a, void* stream) {
+  SSDE_REQUIRE(a && a->y && a->y_new && a->k && a->partial && a->out && a->n > 0, "rk_error_norm: bad args");
+  ssde_rk_error_rows_args r;
+  memset(&r, 0, sizeof(r));
+  r.y = a->y; r.y_new = a->y_new; r.k = a->k; r.n = a->n; r.rows = 7; r.atol = a->atol; r.rtol = a->rtol;
+  r.partial = a->partial; r.partial_len = a->partial_len; r.out = a->out;
+  for (int j = 0; j < 7; ++j) r.coef[j] = a->coef.v[j];
+  return ssde_rk_error_norm_rows(&r, stream);
 }
 
 extern "C" int ssde_pf_drift(const ssde_pf_drift_args* a, void* stream) {

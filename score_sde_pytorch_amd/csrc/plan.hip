@@ -251,20 +251,55 @@ extern "C" int ssde_pc_state(ssde_plan* p, float* x, float* x_mean, void* stream
 }
 
 // ---- ODE plans (ode.FusedDrift / ode.FusedLikelihoodRhs: one program = one right-hand-side evaluation) ----
-// The driver below is ode._initial_step + ode.solve_rk45 line for line (scipy's RK45: Dormand-Prince 5(4), FSAL, RMS error
-// norm, factor 0.9 err^-0.2 in [0.2, 10]); host arithmetic in double, one scalar read per step.  It holds no SDE formulas:
-// the four floats of the device record come from the host's callback.
+// The driver below is ode._initial_step + ode.solve_rk line for line (scipy's explicit methods RK23, RK45 and DOP853: the
+// method's table, FSAL, RMS error norm -- DOP853: its combined 5th / 3rd-order estimate --, factor 0.9 err^(-1/(order+1))
+// in [0.2, 10]); host arithmetic in double, one scalar read per step.  It holds no SDE formulas: the four floats of the
+// device record come from the host's callback.
 namespace {
 constexpr int kOdeRing = 32;
-const double kC[6] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0};
-const double kA[6][5] = {{0, 0, 0, 0, 0},
-                         {1.0 / 5, 0, 0, 0, 0},
-                         {3.0 / 40, 9.0 / 40, 0, 0, 0},
-                         {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
-                         {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
-                         {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
-const double kB[6] = {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
-const double kE[7] = {-71.0 / 57600, 0.0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+// scipy 1.15's tables (scipy/integrate/_ivp/rk.py, dop853_coefficients.py: the first 12 stages), the values of ode.TABLEAUS.
+// A is stored with 12 columns for every method; e2 is the second error row of DOP853's estimator (then e = E5, e2 = E3).
+struct Tableau {
+  const char* name;
+  int n_stages, order;
+  const double* c;
+  const double (*a)[12];
+  const double* b;
+  const double* e;
+  const double* e2;
+};
+const double kRk23C[3] = {0.0, 1.0 / 2, 3.0 / 4};
+const double kRk23A[3][12] = {{0}, {1.0 / 2}, {0.0, 3.0 / 4}};
+const double kRk23B[3] = {2.0 / 9, 1.0 / 3, 4.0 / 9};
+const double kRk23E[4] = {5.0 / 72, -1.0 / 12, -1.0 / 9, 1.0 / 8};
+const double kRk45C[6] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0};
+const double kRk45A[6][12] = {{0},
+                              {1.0 / 5},
+                              {3.0 / 40, 9.0 / 40},
+                              {44.0 / 45, -56.0 / 15, 32.0 / 9},
+                              {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729},
+                              {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
+const double kRk45B[6] = {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
+const double kRk45E[7] = {-71.0 / 57600, 0.0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+const double kDopC[12] = {0.0, 0.05260015195876773, 0.0789002279381516, 0.1183503419072274, 0.2816496580927726, 0.3333333333333333, 0.25, 0.3076923076923077, 0.6512820512820513, 0.6, 0.8571428571428571, 1.0};
+const double kDopA[12][12] = {{0},
+    {0.05260015195876773},
+    {0.0197250569845379, 0.0591751709536137},
+    {0.02958758547680685, 0.0, 0.08876275643042054},
+    {0.2413651341592667, 0.0, -0.8845494793282861, 0.924834003261792},
+    {0.037037037037037035, 0.0, 0.0, 0.17082860872947386, 0.12546768756682242},
+    {0.037109375, 0.0, 0.0, 0.17025221101954405, 0.06021653898045596, -0.017578125},
+    {0.03709200011850479, 0.0, 0.0, 0.17038392571223998, 0.10726203044637328, -0.015319437748624402, 0.008273789163814023},
+    {0.6241109587160757, 0.0, 0.0, -3.3608926294469414, -0.868219346841726, 27.59209969944671, 20.154067550477894, -43.48988418106996},
+    {0.47766253643826434, 0.0, 0.0, -2.4881146199716677, -0.590290826836843, 21.230051448181193, 15.279233632882423, -33.28821096898486, -0.020331201708508627},
+    {-0.9371424300859873, 0.0, 0.0, 5.186372428844064, 1.0914373489967295, -8.149787010746927, -18.52006565999696, 22.739487099350505, 2.4936055526796523, -3.0467644718982196},
+    {2.273310147516538, 0.0, 0.0, -10.53449546673725, -2.0008720582248625, -17.9589318631188, 27.94888452941996, -2.8589982771350235, -8.87285693353063, 12.360567175794303, 0.6433927460157636}};
+const double kDopB[12] = {0.054293734116568765, 0.0, 0.0, 0.0, 0.0, 4.450312892752409, 1.8915178993145003, -5.801203960010585, 0.3111643669578199, -0.1521609496625161, 0.20136540080403034, 0.04471061572777259};
+const double kDopE3[13] = {-0.18980075407240762, 0.0, 0.0, 0.0, 0.0, 4.450312892752409, 1.8915178993145003, -5.801203960010585, -0.4226823213237919, -0.1521609496625161, 0.20136540080403034, 0.02265179219836082, 0.0};
+const double kDopE5[13] = {0.01312004499419488, 0.0, 0.0, 0.0, 0.0, -1.2251564463762044, -0.4957589496572502, 1.6643771824549864, -0.35032884874997366, 0.3341791187130175, 0.08192320648511571, -0.022355307863886294, 0.0};
+const Tableau kTableaus[3] = {{"RK45", 6, 4, kRk45C, kRk45A, kRk45B, kRk45E, nullptr},      // indexed by SSDE_ODE_*
+                              {"RK23", 3, 2, kRk23C, kRk23A, kRk23B, kRk23E, nullptr},
+                              {"DOP853", 12, 7, kDopC, kDopA, kDopB, kDopE5, kDopE3}};
 constexpr double kSafety = 0.9, kMinFactor = 0.2, kMaxFactor = 10.0;
 
 // The pinned ring: the six evaluations of a step are enqueued without a host wait, so the record of an evaluation must
@@ -288,6 +323,7 @@ void ode_ring_free(ssde_ode_dyn* ring) {
 
 struct Ode {                       // the regions of an ODE plan, bounds checked
   int64_t n = 0, N = 0;            // image elements; state length (n, or n + B)
+  int rows = 0;                    // slope rows of K the plan holds (>= 7)
   double *K = nullptr, *y[2] = {nullptr, nullptr}, *y_stage = nullptr, *partial = nullptr, *out = nullptr;
   float* x32 = nullptr;            // the U-Net program's input
   ssde_ode_dyn* dyn = nullptr;
@@ -307,6 +343,7 @@ int ode_view(const ssde_plan* p, Ode* o, const char* who) {
     SSDE_REQUIRE(bytes(SSDE_IO_ODE_PROBE) >= o->n * (int64_t)sizeof(float) && bytes(SSDE_IO_GOUT) >= o->n * (int64_t)sizeof(float),
                  "%s: the likelihood plan has no probe / cotangent region", who);
   o->x32 = static_cast<float*>(region_ptr(p, h.io[SSDE_IO_X]));
+  o->rows = (int)(bytes(SSDE_IO_ODE_K) / (o->N * (int64_t)sizeof(double)));
   o->dyn = static_cast<ssde_ode_dyn*>(region_ptr(p, h.io[SSDE_IO_ODE_DYN]));
   o->K = static_cast<double*>(region_ptr(p, h.io[SSDE_IO_ODE_K]));
   double* s = static_cast<double*>(region_ptr(p, h.io[SSDE_IO_ODE_STATE]));
@@ -316,25 +353,29 @@ int ode_view(const ssde_plan* p, Ode* o, const char* who) {
 
 // dst = y + sum_j coef[j] K[j], and its fp32 copy into the U-Net input (the log-density tail of a likelihood state stays fp64)
 int ode_combine(const Ode& o, const double* y, const double* coef, int n_coef, double* dst, void* stream) {
-  ssde_rk_combine_args a;
+  ssde_rk_combine_rows_args a;
   memset(&a, 0, sizeof(a));
   for (int j = 0; j < n_coef; ++j) {
-    a.coef.v[j] = coef[j];
+    a.coef[j] = coef[j];
     if (coef[j] != 0.0) a.terms = j + 1;
   }
   a.y = y; a.k = o.K; a.n = o.N; a.dst = dst; a.dst32 = o.x32; a.n32 = o.n;
-  return ssde_rk_combine(&a, stream);
+  return ssde_rk_combine_rows(&a, stream);
 }
 
-// scipy's RMS norm of sum_j coef[j] K[j] over atol + max(|y|, |y_new|) rtol: the one host read of a step
-int ode_norm(ssde_plan* p, const Ode& o, const double* y, const double* y_new, const double* coef7, double atol, double rtol, double* value,
-             hipStream_t st) {
-  ssde_rk_error_args a;
+// scipy's error norm over atol + max(|y|, |y_new|) rtol, the one host read of a step.  coef2 == NULL: the RMS norm of
+// sum_j coef[j] K[j] (coef = E_j h); else DOP853's norm of the pair (coef = E5, coef2 = E3, not scaled) and |h|.
+int ode_norm(ssde_plan* p, const Ode& o, const double* y, const double* y_new, const double* coef, const double* coef2, int rows, double h_abs,
+             double atol, double rtol, double* value, hipStream_t st) {
+  ssde_rk_error_rows_args a;
   memset(&a, 0, sizeof(a));
-  a.y = y; a.y_new = y_new; a.k = o.K; a.n = o.N; a.atol = atol; a.rtol = rtol;
+  a.y = y; a.y_new = y_new; a.k = o.K; a.n = o.N; a.rows = rows; a.pair = coef2 != nullptr; a.h_abs = h_abs; a.atol = atol; a.rtol = rtol;
   a.partial = o.partial; a.partial_len = SSDE_ODE_PARTIALS; a.out = o.out;
-  for (int j = 0; j < 7; ++j) a.coef.v[j] = coef7[j];
-  if (int rc = ssde_rk_error_norm(&a, st)) return rc;
+  for (int j = 0; j < rows; ++j) {
+    a.coef[j] = coef[j];
+    if (coef2) a.coef2[j] = coef2[j];
+  }
+  if (int rc = ssde_rk_error_norm_rows(&a, st)) return rc;
   SSDE_HIP_CHECK(hipMemcpyAsync(value, o.out, sizeof(double), hipMemcpyDeviceToHost, st));
   SSDE_HIP_CHECK(hipStreamSynchronize(st));
   p->ode_inflight = 0;
@@ -402,16 +443,22 @@ extern "C" int ssde_ode_eval(ssde_plan* p, double t, ssde_ode_scalars_fn scalars
   return ode_evaluate(p, o, t, scalars, user, slope, 0, stream);
 }
 
-extern "C" int ssde_ode_solve(ssde_plan* p, double t0, double t1, double rtol, double atol, ssde_ode_scalars_fn scalars, void* user,
-                              int32_t use_graph, int32_t max_nfev, int32_t* nfev_out, void* stream) {
+extern "C" int ssde_ode_solve_method(ssde_plan* p, int32_t method, double t0, double t1, double rtol, double atol, ssde_ode_scalars_fn scalars,
+                                     void* user, int32_t use_graph, int32_t max_nfev, int32_t* nfev_out, void* stream) {
   Ode o;
   if (int rc = ode_view(p, &o, "ode_solve")) return rc;
+  SSDE_REQUIRE(method >= 0 && method < 3, "ode_solve: method %d is none of SSDE_ODE_RK45, SSDE_ODE_RK23, SSDE_ODE_DOP853", method);
+  const Tableau& tab = kTableaus[method];
+  const int S = tab.n_stages;
+  SSDE_REQUIRE(o.rows >= S + 1, "ode_solve: %s needs %d slope rows, the plan holds %d (export_ode_plan(rhs, method=...) sizes them)", tab.name,
+               S + 1, o.rows);
   SSDE_REQUIRE(scalars, "ode_solve: null scalars callback");
   SSDE_REQUIRE(t0 != t1 && isfinite(t0) && isfinite(t1), "ode_solve: t0 == t1 (or a non-finite time)");
   SSDE_REQUIRE(rtol > 0 && atol > 0 && max_nfev >= 0, "ode_solve: rtol, atol must be positive and max_nfev >= 0");
   SSDE_REQUIRE(!use_graph || stream, "ode_solve: graph replay needs a non-default stream");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int limit = max_nfev > 0 ? max_nfev : 100000;
+  const double exponent = -1.0 / (tab.order + 1);
   int nfev = 0;
   if (nfev_out) *nfev_out = 0;
   double t = t0;
@@ -421,27 +468,30 @@ extern "C" int ssde_ode_solve(ssde_plan* p, double t0, double t1, double rtol, d
   double* y_new = o.y[p->ode_cur ^ 1];
   auto K = [&](int j) { return o.K + (size_t)j * o.N; };
   SSDE_REQUIRE(limit >= 2, "ode_solve: max_nfev = %d reached after 0 evaluations", limit);
-  SSDE_HIP_CHECK(hipMemsetAsync(o.K, 0, 7 * row, st));               // the norms read all seven rows (unused ones times 0)
+  // The Dormand-Prince solve keeps the launches it always had, this clear of its rows among them; the stage kernels do not
+  // read a row whose coefficient is zero, so no method needs it.
+  if (method == SSDE_ODE_RK45) SSDE_HIP_CHECK(hipMemsetAsync(o.K, 0, 7 * row, st));
   if (int rc = ode_combine(o, y, nullptr, 0, o.y_stage, stream)) return rc;   // stage argument of the first evaluation (and its fp32 copy)
   if (int rc = ode_evaluate(p, o, t, scalars, user, K(0), use_graph, stream)) return rc;
   nfev = 1;
-  // ---- ode._initial_step (scipy's select_initial_step, order 4); with y_new = y the scale is atol + |y0| rtol
+  // ---- ode._initial_step (scipy's select_initial_step with the method's order); with y_new = y the scale is atol + |y0| rtol.
+  // Row 2 (every method has one) holds a copy of y for d0, before any stage fills it.
   double h_abs;
   {
-    double c[7] = {0, 0, 0, 0, 0, 0, 0}, d0, d1, d2;
+    double c[3] = {0, 0, 0}, d0, d1, d2;
     SSDE_HIP_CHECK(hipMemcpyAsync(K(2), y, row, hipMemcpyDeviceToDevice, st));
     c[2] = 1.0;
-    if (int rc = ode_norm(p, o, y, y, c, atol, rtol, &d0, st)) return rc;
+    if (int rc = ode_norm(p, o, y, y, c, nullptr, 3, 0.0, atol, rtol, &d0, st)) return rc;
     c[2] = 0.0; c[0] = 1.0;
-    if (int rc = ode_norm(p, o, y, y, c, atol, rtol, &d1, st)) return rc;
+    if (int rc = ode_norm(p, o, y, y, c, nullptr, 3, 0.0, atol, rtol, &d1, st)) return rc;
     const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
     const double step[1] = {h0 * direction};
     if (int rc = ode_combine(o, y, step, 1, o.y_stage, stream)) return rc;
     if (int rc = ode_evaluate(p, o, t + h0 * direction, scalars, user, K(1), use_graph, stream)) return rc;
     c[0] = -1.0; c[1] = 1.0;
-    if (int rc = ode_norm(p, o, y, y, c, atol, rtol, &d2, st)) return rc;
+    if (int rc = ode_norm(p, o, y, y, c, nullptr, 3, 0.0, atol, rtol, &d2, st)) return rc;
     d2 /= h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / (tab.order + 1));
     h_abs = fmin(100 * h0, h1);
     SSDE_REQUIRE(isfinite(h_abs), "ode_solve: the initial step is not finite (d0 %g, d1 %g, d2 %g)", d0, d1, d2);
   }
@@ -454,45 +504,54 @@ extern "C" int ssde_ode_solve(ssde_plan* p, double t0, double t1, double rtol, d
     double t_new;
     for (;;) {
       SSDE_REQUIRE(!(h_abs < min_step), "ode_solve: step size underflow at t = %.17g (scipy: 'Required step size is less than spacing between numbers.')", t);
-      SSDE_REQUIRE(nfev + 6 <= limit, "ode_solve: max_nfev = %d reached at t = %.17g after %d evaluations", limit, t, nfev);
+      SSDE_REQUIRE(nfev + S <= limit, "ode_solve: max_nfev = %d reached at t = %.17g after %d evaluations", limit, t, nfev);
       double h = h_abs * direction;
       t_new = t + h;
       if (direction * (t_new - t_bound) > 0) t_new = t_bound;
       h = t_new - t;
       h_abs = fabs(h);
-      double c[7];
-      for (int s = 1; s < 6; ++s) {
-        for (int j = 0; j < s; ++j) c[j] = kA[s][j] * h;
+      double c[SSDE_RK_MAX_ROWS];
+      for (int s = 1; s < S; ++s) {
+        for (int j = 0; j < s; ++j) c[j] = tab.a[s][j] * h;
         if (int rc = ode_combine(o, y, c, s, o.y_stage, stream)) return rc;
-        if (int rc = ode_evaluate(p, o, t + kC[s] * h, scalars, user, K(s), use_graph, stream)) return rc;
+        if (int rc = ode_evaluate(p, o, t + tab.c[s] * h, scalars, user, K(s), use_graph, stream)) return rc;
       }
-      for (int j = 0; j < 6; ++j) c[j] = kB[j] * h;
-      if (int rc = ode_combine(o, y, c, 6, y_new, stream)) return rc;          // (its fp32 copy feeds the seventh evaluation)
-      if (int rc = ode_evaluate(p, o, t + h, scalars, user, K(6), use_graph, stream)) return rc;
-      nfev += 6;
+      for (int j = 0; j < S; ++j) c[j] = tab.b[j] * h;
+      if (int rc = ode_combine(o, y, c, S, y_new, stream)) return rc;          // (its fp32 copy feeds the last evaluation)
+      if (int rc = ode_evaluate(p, o, t + h, scalars, user, K(S), use_graph, stream)) return rc;
+      nfev += S;
       if (nfev_out) *nfev_out = nfev;
-      for (int j = 0; j < 7; ++j) c[j] = kE[j] * h;
       double err;
-      if (int rc = ode_norm(p, o, y, y_new, c, atol, rtol, &err, st)) return rc;
+      if (tab.e2) {
+        if (int rc = ode_norm(p, o, y, y_new, tab.e, tab.e2, S + 1, h_abs, atol, rtol, &err, st)) return rc;
+      } else {
+        for (int j = 0; j <= S; ++j) c[j] = tab.e[j] * h;
+        if (int rc = ode_norm(p, o, y, y_new, c, nullptr, S + 1, 0.0, atol, rtol, &err, st)) return rc;
+      }
       SSDE_REQUIRE(isfinite(err), "ode_solve: the error norm is not finite at t = %.17g (step %g)", t, h);
       if (err < 1) {
-        double factor = err == 0 ? kMaxFactor : fmin(kMaxFactor, kSafety * pow(err, -0.2));
+        double factor = err == 0 ? kMaxFactor : fmin(kMaxFactor, kSafety * pow(err, exponent));
         if (rejected) factor = fmin(1.0, factor);
         h_abs *= factor;
         break;
       }
-      h_abs *= fmax(kMinFactor, kSafety * pow(err, -0.2));
+      h_abs *= fmax(kMinFactor, kSafety * pow(err, exponent));
       rejected = true;
     }
     t = t_new;
     p->ode_cur ^= 1;                                                   // accept: swap buffers
     y = o.y[p->ode_cur];
     y_new = o.y[p->ode_cur ^ 1];
-    SSDE_HIP_CHECK(hipMemcpyAsync(K(0), K(6), row, hipMemcpyDeviceToDevice, st));   // FSAL: the last slope is the next step's first
+    SSDE_HIP_CHECK(hipMemcpyAsync(K(0), K(S), row, hipMemcpyDeviceToDevice, st));   // FSAL: the last slope is the next step's first
   }
   SSDE_HIP_CHECK(hipStreamSynchronize(st));
   p->ode_inflight = 0;
   return SSDE_OK;
+}
+
+extern "C" int ssde_ode_solve(ssde_plan* p, double t0, double t1, double rtol, double atol, ssde_ode_scalars_fn scalars, void* user,
+                              int32_t use_graph, int32_t max_nfev, int32_t* nfev_out, void* stream) {
+  return ssde_ode_solve_method(p, SSDE_ODE_RK45, t0, t1, rtol, atol, scalars, user, use_graph, max_nfev, nfev_out, stream);
 }
 
 extern "C" int ssde_ode_state(ssde_plan* p, float* x, double* delta_logp, void* stream) {

@@ -7,9 +7,10 @@ the cotangent, per-sample divergence kernel; captured into a hipGraph).  Other m
 below: the drift and its vector-Jacobian product run on the HIP forward / backward programs through the autograd bridge
 (autograd.py).  Only d drift / d x is needed, so the parameters are frozen for the duration of a call: the backward
 program is then lowered without its weight-gradient kernels (backward.TrainEngine(param_grads=False)).
-The augmented state [x (B*D values) | accumulated log-density change (B values)] is one fp64 tensor; with method='RK45'
-on GPU data it is integrated by ode.solve_rk45 (scipy's RK45 algorithm, state resident on the device), otherwise -- or
-with SSDE_HOST_ODE=1 -- by scipy.integrate.solve_ivp on the host, as the reference does (ode.solve_host).
+The augmented state [x (B*D values) | accumulated log-density change (B values)] is one fp64 tensor; with one of scipy's
+explicit methods ('RK45', 'RK23', 'DOP853') on GPU data it is integrated by ode.solve_rk (scipy's algorithm, state resident
+on the device), otherwise -- an implicit method, or SSDE_HOST_ODE=1 -- by scipy.integrate.solve_ivp on the host, as the
+reference does (ode.solve_host).
 """
 import contextlib
 import math
@@ -54,14 +55,16 @@ def _probe(data, kind):
 
 
 def get_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e-5, atol=1e-5, method='RK45', eps=1e-5):
-    """Returns likelihood_fn(model, data) -> (bpd [B], z, nfe)  (likelihood.py:40-113)."""
+    """Returns likelihood_fn(model, data) -> (bpd [B], z, nfe)  (likelihood.py:40-113).  method: as the reference, any
+    scipy.integrate.solve_ivp method; 'RK45', 'RK23' and 'DOP853' run on the device (ode.integrate_ode) around the same
+    cached fused right-hand side, whichever of them a call names."""
 
     def likelihood_fn(model, data):
         batch, dims = data.shape[0], data[0].numel()
         with torch.no_grad(), _frozen(model):
             probe = _probe(data, hutchinson_type)
             y0 = torch.cat([data.reshape(-1), data.new_zeros(batch)]).to(torch.float64)
-            if method == 'RK45' and ode.FusedLikelihoodRhs.applies(model, sde, data):
+            if method in ode.TABLEAUS and ode.FusedLikelihoodRhs.applies(model, sde, data):
                 # the whole right-hand side as one device program per evaluation (ode.FusedLikelihoodRhs): no torch
                 # arithmetic, no autograd graph, no dtype round trips between U-Net evaluations
                 # shared by every likelihood_fn of this SDE object; a small LRU (ode.rhs_cache_get)

@@ -1,11 +1,12 @@
-"""On-device adaptive Dormand-Prince RK45.
+"""On-device adaptive explicit Runge-Kutta: scipy's RK45, RK23 and DOP853.
 
-The reference drives its probability-flow ODE sampler and likelihood with `scipy.integrate.solve_ivp(method='RK45')`
-(sampling.py:473, likelihood.py:99): every function evaluation converts the fp64 numpy state to an fp32 device tensor
-and back (models/utils.py:181-188).  This is the same algorithm -- scipy's `RK45` class: Dormand-Prince 5(4) pair,
-FSAL, RMS error norm over the whole state, step factor 0.9 * err^(-1/5) clamped to [0.2, 10], scipy's
-`select_initial_step` -- with the state kept as an fp64 tensor on the GPU, so only one scalar (the error norm) crosses
-the PCIe bus per step.  `fun(t, y)` receives and returns fp64 device tensors.
+The reference drives its probability-flow ODE sampler and likelihood with `scipy.integrate.solve_ivp(method=...)`
+(sampling.py:473, likelihood.py:99; 'RK45' by default): every function evaluation converts the fp64 numpy state to an
+fp32 device tensor and back (models/utils.py:181-188).  This is the same algorithm -- scipy's `RungeKutta` classes: the
+method's table (TABLEAUS), FSAL, RMS error norm over the whole state (DOP853: its combined 5th / 3rd-order estimate),
+step factor 0.9 * err^(-1/(order+1)) clamped to [0.2, 10], scipy's `select_initial_step` -- with the state kept as an
+fp64 tensor on the GPU, so only one scalar (the error norm) crosses the PCIe bus per step.  `fun(t, y)` receives and
+returns fp64 device tensors.
 """
 import ctypes as C
 import math
@@ -20,11 +21,36 @@ from . import engine as E
 from . import hipops
 from . import sde_lib
 
-_C = [0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0]
-_A = [[], [1 / 5], [3 / 40, 9 / 40], [44 / 45, -56 / 15, 32 / 9], [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
-      [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656]]
-_B = [35 / 384, 0.0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84]
-_E = [-71 / 57600, 0.0, 71 / 16695, -71 / 1920, 17253 / 339200, -22 / 525, 1 / 40]
+# scipy 1.15's tables (scipy/integrate/_ivp/rk.py: RK23, RK45; dop853_coefficients.py: the first 12 stages of its extended
+# table, which is all a step uses), value for value: tests/test_ode_methods_cpu.py compares them with `==`.  Row s of A
+# holds its s entries; `order` is scipy's error_estimator_order; E has n_stages + 1 entries (the last slope row is
+# f(t + h, y_new)); DOP853 has the two error rows of its 8(5,3) estimator.
+_DOP853_C = [0.0, 0.05260015195876773, 0.0789002279381516, 0.1183503419072274, 0.2816496580927726, 0.3333333333333333, 0.25, 0.3076923076923077, 0.6512820512820513, 0.6, 0.8571428571428571, 1.0]
+_DOP853_A = [[],
+             [0.05260015195876773],
+             [0.0197250569845379, 0.0591751709536137],
+             [0.02958758547680685, 0.0, 0.08876275643042054],
+             [0.2413651341592667, 0.0, -0.8845494793282861, 0.924834003261792],
+             [0.037037037037037035, 0.0, 0.0, 0.17082860872947386, 0.12546768756682242],
+             [0.037109375, 0.0, 0.0, 0.17025221101954405, 0.06021653898045596, -0.017578125],
+             [0.03709200011850479, 0.0, 0.0, 0.17038392571223998, 0.10726203044637328, -0.015319437748624402, 0.008273789163814023],
+             [0.6241109587160757, 0.0, 0.0, -3.3608926294469414, -0.868219346841726, 27.59209969944671, 20.154067550477894, -43.48988418106996],
+             [0.47766253643826434, 0.0, 0.0, -2.4881146199716677, -0.590290826836843, 21.230051448181193, 15.279233632882423, -33.28821096898486, -0.020331201708508627],
+             [-0.9371424300859873, 0.0, 0.0, 5.186372428844064, 1.0914373489967295, -8.149787010746927, -18.52006565999696, 22.739487099350505, 2.4936055526796523, -3.0467644718982196],
+             [2.273310147516538, 0.0, 0.0, -10.53449546673725, -2.0008720582248625, -17.9589318631188, 27.94888452941996, -2.8589982771350235, -8.87285693353063, 12.360567175794303, 0.6433927460157636]]
+_DOP853_B = [0.054293734116568765, 0.0, 0.0, 0.0, 0.0, 4.450312892752409, 1.8915178993145003, -5.801203960010585, 0.3111643669578199, -0.1521609496625161, 0.20136540080403034, 0.04471061572777259]
+_DOP853_E3 = [-0.18980075407240762, 0.0, 0.0, 0.0, 0.0, 4.450312892752409, 1.8915178993145003, -5.801203960010585, -0.4226823213237919, -0.1521609496625161, 0.20136540080403034, 0.02265179219836082, 0.0]
+_DOP853_E5 = [0.01312004499419488, 0.0, 0.0, 0.0, 0.0, -1.2251564463762044, -0.4957589496572502, 1.6643771824549864, -0.35032884874997366, 0.3341791187130175, 0.08192320648511571, -0.022355307863886294, 0.0]
+TABLEAUS = {
+    "RK23": dict(n_stages=3, order=2, C=[0.0, 1 / 2, 3 / 4], A=[[], [1 / 2], [0.0, 3 / 4]], B=[2 / 9, 1 / 3, 4 / 9],
+                 E=[5 / 72, -1 / 12, -1 / 9, 1 / 8]),
+    "RK45": dict(n_stages=6, order=4, C=[0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0],
+                 A=[[], [1 / 5], [3 / 40, 9 / 40], [44 / 45, -56 / 15, 32 / 9], [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
+                    [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656]],
+                 B=[35 / 384, 0.0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84],
+                 E=[-71 / 57600, 0.0, 71 / 16695, -71 / 1920, 17253 / 339200, -22 / 525, 1 / 40]),
+    "DOP853": dict(n_stages=12, order=7, C=_DOP853_C, A=_DOP853_A, B=_DOP853_B, E3=_DOP853_E3, E5=_DOP853_E5),
+}
 SAFETY, MIN_FACTOR, MAX_FACTOR = 0.9, 0.2, 10.0
 
 
@@ -32,15 +58,15 @@ def _rms(x):
     return float(torch.sqrt(torch.mean(x * x)))
 
 
-def _initial_step(fun, t0, y0, f0, direction, rtol, atol):
-    """scipy.integrate._ivp.common.select_initial_step with order = 4 (runs once per solve)."""
+def _initial_step(fun, t0, y0, f0, direction, rtol, atol, order=4):
+    """scipy.integrate._ivp.common.select_initial_step (runs once per solve); order: the method's error-estimator order."""
     scale = atol + torch.abs(y0) * rtol
     d0, d1 = _rms(y0 / scale), _rms(f0 / scale)
     h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
     y1 = y0 + h0 * direction * f0
     f1 = fun(t0 + h0 * direction, y1)
     d2 = _rms((f1 - f0) / scale) / h0
-    h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else (0.01 / max(d1, d2)) ** (1 / 5)
+    h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else (0.01 / max(d1, d2)) ** (1 / (order + 1))
     return min(100 * h0, h1)
 
 
@@ -48,34 +74,44 @@ class _TorchStages:
     """Stage arithmetic with torch ops.  Reached only with host tensors (the CPU unit tests of the step-size controller
     against scipy on analytic right-hand sides): the model's right-hand side cannot run there."""
 
-    def __init__(self, n, like):
-        self.K = torch.empty(7, n, dtype=torch.float64, device=like.device)
+    def __init__(self, n, like, rows=7):
+        self.K = torch.empty(rows, n, dtype=torch.float64, device=like.device)
         self.x32 = None
 
-    def combine(self, y, coefs, dst):
+    def _dot(self, coefs):
         acc = None
         for j, c in enumerate(coefs):
             if c != 0.0:
                 acc = self.K[j] * c if acc is None else acc + self.K[j] * c
+        return acc
+
+    def combine(self, y, coefs, dst):
+        acc = self._dot(coefs)
         dst.copy_(y if acc is None else y + acc)
 
     def error_norm(self, y, y_new, coefs, atol, rtol):
-        err = None
-        for j, c in enumerate(coefs):
-            if c != 0.0:
-                err = self.K[j] * c if err is None else err + self.K[j] * c
         scale = atol + torch.maximum(torch.abs(y), torch.abs(y_new)) * rtol
-        return _rms(err / scale)
+        return _rms(self._dot(coefs) / scale)
+
+    def error_norm_pair(self, y, y_new, coefs5, coefs3, h_abs, atol, rtol):
+        """scipy's DOP853._estimate_error_norm: the 5th- and 3rd-order estimates combined; the coefficients are not scaled by h"""
+        scale = atol + torch.maximum(torch.abs(y), torch.abs(y_new)) * rtol
+        s5 = float(torch.sum((self._dot(coefs5) / scale) ** 2))
+        s3 = float(torch.sum((self._dot(coefs3) / scale) ** 2))
+        if s5 == 0 and s3 == 0:
+            return 0.0
+        return h_abs * s5 / math.sqrt((s5 + 0.01 * s3) * y.numel())
 
 
 class _HipStages:
-    """Stage arithmetic on the device (libssde_hip: ssde_rk_combine, ssde_rk_error_norm): one launch forms a stage
+    """Stage arithmetic on the device (libssde_hip: ssde_rk_combine_rows, ssde_rk_error_norm_rows): one launch forms a stage
     argument together with its fp32 copy -- written straight into the U-Net's input buffer when the right-hand side is
-    the fused drift (FusedDrift) -- and the error norm comes back as ONE scalar per step."""
+    the fused drift (FusedDrift) -- and the error norm comes back as ONE scalar per step.  rows: slope rows of K, the
+    method's n_stages + 1 (7: RK45).  The kernels read only rows with a non-zero coefficient, so K starts uninitialised."""
 
-    def __init__(self, n, like, x32=None, n32=0):
+    def __init__(self, n, like, x32=None, n32=0, rows=7):
         self.lib, self.n, self.n32 = L.load(), n, int(n32)
-        self.K = torch.empty(7, n, dtype=torch.float64, device=like.device)
+        self.K = torch.empty(rows, n, dtype=torch.float64, device=like.device)
         self.partial = torch.empty(1024, dtype=torch.float64, device=like.device)
         self.out = torch.empty(1, dtype=torch.float64, device=like.device)
         self.x32 = x32
@@ -84,37 +120,55 @@ class _HipStages:
         return hipops._stream()
 
     def combine(self, y, coefs, dst):
-        a = L.RkCombineArgs()
+        a = L.RkCombineRowsArgs()
         terms = max([j + 1 for j, c in enumerate(coefs) if c != 0.0], default=0)
         a.y, a.k, a.n, a.terms, a.dst = y.data_ptr(), self.K.data_ptr(), self.n, terms, dst.data_ptr()
         a.dst32 = self.x32.data_ptr() if self.x32 is not None else None
         a.n32 = self.n32
         for j in range(terms):
             a.coef[j] = coefs[j]
-        L.check(self.lib.ssde_rk_combine(C.byref(a), self._stream()), "ssde_rk_combine")
+        L.check(self.lib.ssde_rk_combine_rows(C.byref(a), self._stream()), "ssde_rk_combine_rows")
 
-    def error_norm(self, y, y_new, coefs, atol, rtol):
-        a = L.RkErrorArgs()
+    def _norm(self, y, y_new, coefs, coefs2, h_abs, atol, rtol):
+        a = L.RkErrorRowsArgs()
         a.y, a.y_new, a.k, a.n, a.atol, a.rtol = y.data_ptr(), y_new.data_ptr(), self.K.data_ptr(), self.n, atol, rtol
         a.partial, a.partial_len, a.out = self.partial.data_ptr(), self.partial.numel(), self.out.data_ptr()
-        for j in range(7):
-            a.coef[j] = coefs[j]
-        L.check(self.lib.ssde_rk_error_norm(C.byref(a), self._stream()), "ssde_rk_error_norm")
+        a.rows, a.pair, a.h_abs = len(coefs), int(coefs2 is not None), h_abs
+        for j, c in enumerate(coefs):
+            a.coef[j] = c
+        for j, c in enumerate(coefs2 or ()):
+            a.coef2[j] = c
+        L.check(self.lib.ssde_rk_error_norm_rows(C.byref(a), self._stream()), "ssde_rk_error_norm_rows")
         return float(self.out.item())          # the one host read of the step
 
+    def error_norm(self, y, y_new, coefs, atol, rtol):
+        return self._norm(y, y_new, coefs, None, 0.0, atol, rtol)
 
-def solve_rk45(fun, t_span, y0, rtol=1e-5, atol=1e-5, stages=None):
-    """Integrate dy/dt = fun(t, y) from t_span[0] to t_span[1]; returns (y_final, nfev).
+    def error_norm_pair(self, y, y_new, coefs5, coefs3, h_abs, atol, rtol):
+        return self._norm(y, y_new, coefs5, coefs3, h_abs, atol, rtol)
+
+
+def solve_rk(fun, t_span, y0, rtol=1e-5, atol=1e-5, method="RK45", stages=None):
+    """Integrate dy/dt = fun(t, y) from t_span[0] to t_span[1] with scipy's explicit method `method` (a key of TABLEAUS);
+    returns (y_final, nfev).
 
     `fun(t, y)` returns the fp64 slope, or -- for right-hand sides that write their result in place (FusedDrift) --
-    `fun(t, y, out=K_row)` fills `out`.  `stages`: the arithmetic backend (device kernels for CUDA tensors)."""
+    `fun(t, y, out=K_row)` fills `out`.  `stages`: the arithmetic backend (device kernels for CUDA tensors), with at least
+    n_stages + 1 rows of K."""
+    if method not in TABLEAUS:
+        raise ValueError("solve_rk: method must be one of %s, got %r" % (sorted(TABLEAUS), method))
+    tab = TABLEAUS[method]
+    n_stages, tab_a, tab_b, tab_c = tab["n_stages"], tab["A"], tab["B"], tab["C"]
+    exponent = -1 / (tab["order"] + 1)
     t, t_bound = float(t_span[0]), float(t_span[1])
     direction = 1.0 if t_bound >= t else -1.0
     y = y0.to(torch.float64).clone()
     n = y.numel()
     if stages is None:
-        stages = _HipStages(n, y) if y.is_cuda else _TorchStages(n, y)
+        stages = (_HipStages if y.is_cuda else _TorchStages)(n, y, rows=n_stages + 1)
     K = stages.K
+    if K.shape[0] < n_stages + 1:
+        raise ValueError("solve_rk: %s needs %d slope rows, the stages hold %d" % (method, n_stages + 1, K.shape[0]))
     in_place = getattr(fun, "writes_out", False)
 
     def evaluate(tt, yy, row):
@@ -126,7 +180,8 @@ def solve_rk45(fun, t_span, y0, rtol=1e-5, atol=1e-5, stages=None):
     stages.combine(y, [], y_stage)                       # stage argument of the first evaluation (and its fp32 copy)
     evaluate(t, y_stage, 0)
     nfev = 1
-    h_abs = _initial_step((lambda tt, yy: _once(fun, stages, tt, yy, in_place)), t, y, K[0].clone(), direction, rtol, atol)
+    h_abs = _initial_step((lambda tt, yy: _once(fun, stages, tt, yy, in_place)), t, y, K[0].clone(), direction, rtol, atol,
+                          order=tab["order"])
     nfev += 1
     while direction * (t - t_bound) < 0:
         min_step = 10 * abs(math.nextafter(t, direction * math.inf) - t)
@@ -134,32 +189,40 @@ def solve_rk45(fun, t_span, y0, rtol=1e-5, atol=1e-5, stages=None):
         rejected = False
         while True:
             if h_abs < min_step:
-                raise RuntimeError("solve_rk45: step size underflow (scipy: 'Required step size is less than spacing')")
+                raise RuntimeError("solve_rk: step size underflow (scipy: 'Required step size is less than spacing')")
             h = h_abs * direction
             t_new = t + h
             if direction * (t_new - t_bound) > 0:
                 t_new = t_bound
             h = t_new - t
             h_abs = abs(h)
-            for s_ in range(1, 6):
-                stages.combine(y, [a * h for a in _A[s_]], y_stage)
-                evaluate(t + _C[s_] * h, y_stage, s_)
-            stages.combine(y, [b * h for b in _B], y_new)
-            evaluate(t + h, y_new, 6)
-            nfev += 6
-            error_norm = stages.error_norm(y, y_new, [e * h for e in _E], atol, rtol)
+            for s_ in range(1, n_stages):
+                stages.combine(y, [a * h for a in tab_a[s_]], y_stage)
+                evaluate(t + tab_c[s_] * h, y_stage, s_)
+            stages.combine(y, [b * h for b in tab_b], y_new)
+            evaluate(t + h, y_new, n_stages)
+            nfev += n_stages
+            if "E" in tab:
+                error_norm = stages.error_norm(y, y_new, [e * h for e in tab["E"]], atol, rtol)
+            else:
+                error_norm = stages.error_norm_pair(y, y_new, tab["E5"], tab["E3"], h_abs, atol, rtol)
             if error_norm < 1:
-                factor = MAX_FACTOR if error_norm == 0 else min(MAX_FACTOR, SAFETY * error_norm ** -0.2)
+                factor = MAX_FACTOR if error_norm == 0 else min(MAX_FACTOR, SAFETY * error_norm ** exponent)
                 if rejected:
                     factor = min(1.0, factor)
                 h_abs *= factor
                 break
-            h_abs *= max(MIN_FACTOR, SAFETY * error_norm ** -0.2)
+            h_abs *= max(MIN_FACTOR, SAFETY * error_norm ** exponent)
             rejected = True
         t = t_new
         y, y_new = y_new, y                              # accept: swap buffers
-        K[0].copy_(K[6])                                 # FSAL: the last slope is the next step's first
+        K[0].copy_(K[n_stages])                          # FSAL: the last slope is the next step's first
     return y, nfev
+
+
+def solve_rk45(fun, t_span, y0, rtol=1e-5, atol=1e-5, stages=None):
+    """solve_rk with scipy's RK45 (Dormand-Prince 5(4))."""
+    return solve_rk(fun, t_span, y0, rtol=rtol, atol=atol, method="RK45", stages=stages)
 
 
 def _once(fun, stages, t, yy, in_place):
@@ -326,8 +389,8 @@ def scalars_fn(rhs):
 
 def solve_host(fun, t_span, y0, rtol=1e-5, atol=1e-5, method="RK45"):
     """The reference's integrator, scipy.integrate.solve_ivp on the host, around the same tensor right-hand side as
-    solve_rk45: `fun(t, y)` takes / returns an fp64 tensor on y0's device; every evaluation crosses to numpy and back
-    (what models/utils.py:181-188 does in the reference).  Used for methods other than RK45 and with SSDE_HOST_ODE=1."""
+    solve_rk: `fun(t, y)` takes / returns an fp64 tensor on y0's device; every evaluation crosses to numpy and back
+    (what models/utils.py:181-188 does in the reference).  Used for the implicit methods and with SSDE_HOST_ODE=1."""
     from scipy import integrate
     dev = y0.device
 
@@ -339,22 +402,30 @@ def solve_host(fun, t_span, y0, rtol=1e-5, atol=1e-5, method="RK45"):
     return torch.from_numpy(sol.y[:, -1].copy()).to(dev), int(sol.nfev)
 
 
+last_driver = None      # which integrator the latest integrate_ode call ran: "device" (solve_rk) or "host" (solve_host)
+
+
 def integrate_ode(fun, t_span, y0, rtol, atol, method):
-    """Device RK45 when the state lives on the GPU and nothing asks for the host path, else scipy on the host.
+    """The device driver (solve_rk) for scipy's explicit methods -- RK23, RK45, DOP853 -- when the state lives on the GPU
+    and nothing asks for the host path, else scipy on the host (implicit methods need Jacobians; SSDE_HOST_ODE=1).
     A right-hand side with `writes_out` (FusedDrift) gets the fp32 copy of every stage argument written into its input."""
-    if method == "RK45" and y0.is_cuda and os.environ.get("SSDE_HOST_ODE", "0") != "1":
+    global last_driver
+    if method in TABLEAUS and y0.is_cuda and os.environ.get("SSDE_HOST_ODE", "0") != "1":
+        last_driver = "device"
+        rows = TABLEAUS[method]["n_stages"] + 1
         side = getattr(fun, "graph_stream", None)
         if side is None:
-            stages = _HipStages(y0.numel(), y0, x32=getattr(fun, "x32", None), n32=getattr(fun, "n32", 0))
-            return solve_rk45(fun, t_span, y0, rtol=rtol, atol=atol, stages=stages)
+            stages = _HipStages(y0.numel(), y0, x32=getattr(fun, "x32", None), n32=getattr(fun, "n32", 0), rows=rows)
+            return solve_rk(fun, t_span, y0, rtol=rtol, atol=atol, method=method, stages=stages)
         # graph-captured right-hand side: the whole solve (stage kernels, graph replays, the one scalar read per step)
         # runs on the side stream the graph was captured on
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            stages = _HipStages(y0.numel(), y0, x32=getattr(fun, "x32", None), n32=getattr(fun, "n32", 0))
-            res = solve_rk45(fun, t_span, y0, rtol=rtol, atol=atol, stages=stages)
+            stages = _HipStages(y0.numel(), y0, x32=getattr(fun, "x32", None), n32=getattr(fun, "n32", 0), rows=rows)
+            res = solve_rk(fun, t_span, y0, rtol=rtol, atol=atol, method=method, stages=stages)
         torch.cuda.current_stream().wait_stream(side)
         return res
+    last_driver = "host"
     if getattr(fun, "writes_out", False):
         inner = fun
 
@@ -364,4 +435,3 @@ def integrate_ode(fun, t_span, y0, rtol, atol, method):
             inner(t, y, out=out)
             return out
     return solve_host(fun, t_span, y0, rtol=rtol, atol=atol, method=method)
-

@@ -33,6 +33,7 @@ IO_X, IO_COND, IO_SIGMA, IO_STD, IO_OUT, IO_XMEAN, IO_STEP, IO_SEED = range(8)
 IO_ODE_DYN, IO_ODE_K, IO_ODE_STATE, IO_ODE_PROBE = range(20, 24)
 IO_SLOTS = 24
 ODE_PARTIALS = 1024                      # include/ssde.h: SSDE_ODE_PARTIALS
+ODE_METHODS = {"RK45": 0, "RK23": 1, "DOP853": 2}   # include/ssde.h: SSDE_ODE_*
 
 
 class PlanHeader(C.Structure):
@@ -273,17 +274,21 @@ def export_train_plan(fs, optimizer=None, ema=None):
                  seg=(seg0, seg1, seg2, seg3), n_flat=fs.flat.numel)
 
 
-def export_ode_plan(rhs):
-    """ode.FusedDrift / ode.FusedLikelihoodRhs -> blob for ssde_ode_reset / ssde_ode_eval / ssde_ode_solve / ssde_ode_state
-    (one program = one evaluation of the right-hand side, its scalars read from the `dyn` record).
+def export_ode_plan(rhs, method="RK45"):
+    """ode.FusedDrift / ode.FusedLikelihoodRhs -> blob for ssde_ode_reset / ssde_ode_eval / ssde_ode_solve[_method] /
+    ssde_ode_state (one program = one evaluation of the right-hand side, its scalars read from the `dyn` record).
 
-    Besides the U-Net's regions the blob names the solver state as zero regions: the record, the seven fp64 slope rows, and
-    one block holding y, y_new, the stage argument and the error-norm partials and result (offsets: include/ssde.h,
+    Besides the U-Net's regions the blob names the solver state as zero regions: the record, the fp64 slope rows -- the
+    n_stages + 1 of `method` (ode.TABLEAUS) and never fewer than the 7 of RK45, so every blob runs RK45 and RK23 and the
+    default blob is what it always was --, and one block holding y, y_new, the stage argument and the error-norm partials and result (offsets: include/ssde.h,
     SSDE_IO_ODE_STATE).  State length: B*C*H*W for the sampler, plus B log-density terms for the likelihood, whose plan also
     carries the probe (set per solve by ssde_ode_reset, which copies it into the cotangent buffer too)."""
     from . import ode
     if not isinstance(rhs, (ode.FusedDrift, ode.FusedLikelihoodRhs)):
         raise TypeError("export_ode_plan: expected an ode.FusedDrift or an ode.FusedLikelihoodRhs, got %s" % type(rhs).__name__)
+    if method not in ode.TABLEAUS:
+        raise ValueError("export_ode_plan: method must be one of %s, got %r" % (sorted(ode.TABLEAUS), method))
+    rows = max(7, ode.TABLEAUS[method]["n_stages"] + 1)
     eng = rhs.unet
     eng.weights.refresh()
     lik = isinstance(rhs, ode.FusedLikelihoodRhs)
@@ -291,7 +296,7 @@ def export_ode_plan(rhs):
     n_state = rhs.n + (B if lik else 0)
     regions = _Regions()
     _collect_unet(regions, eng)
-    slopes = torch.zeros(7 * n_state, dtype=torch.float64, device=rhs.dyn.device)
+    slopes = torch.zeros(rows * n_state, dtype=torch.float64, device=rhs.dyn.device)
     state = torch.zeros(3 * n_state + ODE_PARTIALS + 1, dtype=torch.float64, device=rhs.dyn.device)
     regions.add(rhs.dyn, REGION_ZERO, "ode_dyn")
     regions.add(slopes, REGION_ZERO, "ode_slopes")
@@ -329,6 +334,8 @@ def bind(lib):
     lib.ssde_ode_eval.argtypes = [C.c_void_p, C.c_double, ODE_SCALARS_FN, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ssde_ode_solve.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, ODE_SCALARS_FN, C.c_void_p, C.c_int32,
                                    C.c_int32, C.POINTER(C.c_int32), C.c_void_p]
+    lib.ssde_ode_solve_method.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, ODE_SCALARS_FN, C.c_void_p,
+                                          C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]
     lib.ssde_ode_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
 
@@ -428,14 +435,16 @@ class LoadedPlan:
         self._ode_call("ssde_ode_eval", fn, rc)
         return out
 
-    def ode_solve(self, t0, t1, rtol, atol, scalars, use_graph=False, max_nfev=0, stream=None):
-        """integrate the plan's state from t0 to t1 (adaptive RK45 in the library); `scalars`: t -> (label, second, a, g2), e.g.
-        ode.scalars_fn(rhs).  Returns the number of evaluations."""
+    def ode_solve(self, t0, t1, rtol, atol, scalars, use_graph=False, max_nfev=0, stream=None, method="RK45"):
+        """integrate the plan's state from t0 to t1 (the library's adaptive driver; method: a key of ODE_METHODS);
+        `scalars`: t -> (label, second, a, g2), e.g. ode.scalars_fn(rhs).  Returns the number of evaluations."""
+        if method not in ODE_METHODS:
+            raise ValueError("ode_solve: method must be one of %s, got %r" % (sorted(ODE_METHODS), method))
         nfev = C.c_int32(0)
         fn = _ode_callback(scalars)
-        rc = self.lib.ssde_ode_solve(self.handle, float(t0), float(t1), float(rtol), float(atol), fn, None, int(bool(use_graph)),
-                                     int(max_nfev), C.byref(nfev), C.c_void_p(stream or 0))
-        self._ode_call("ssde_ode_solve", fn, rc)
+        rc = self.lib.ssde_ode_solve_method(self.handle, ODE_METHODS[method], float(t0), float(t1), float(rtol), float(atol), fn, None,
+                                            int(bool(use_graph)), int(max_nfev), C.byref(nfev), C.c_void_p(stream or 0))
+        self._ode_call("ssde_ode_solve_method", fn, rc)
         return int(nfev.value)
 
     def ode_state(self, like, stream=None):

@@ -308,12 +308,13 @@ def get_pc_sampler(sde, shape, predictor, corrector, inverse_scaler, snr, n_step
 
 def get_ode_sampler(sde, shape, inverse_scaler, denoise=False, rtol=1e-5, atol=1e-5, method='RK45', eps=1e-3,
                     device='cuda'):
-    """Probability-flow ODE sampler with adaptive RK45 (sampling.py:414-485).
+    """Probability-flow ODE sampler with an adaptive Runge-Kutta method (sampling.py:414-485).
 
-    The drift evaluation (one U-Net forward per function evaluation) runs as a HIP program.  With method='RK45' on a
-    GPU tensor the integrator is ode.solve_rk45 -- scipy's RK45 algorithm with the fp64 state resident on the device
-    (no per-evaluation host round trip, models/utils.py:181-188); other methods, or SSDE_HOST_ODE=1, use
-    scipy.integrate.solve_ivp on the host exactly as the reference does."""
+    The drift evaluation (one U-Net forward per function evaluation) runs as a HIP program.  With one of scipy's explicit
+    methods -- 'RK45' (the default), 'RK23', 'DOP853' -- on a GPU tensor the integrator is ode.solve_rk: scipy's
+    algorithm with the fp64 state resident on the device (no per-evaluation host round trip, models/utils.py:181-188).
+    The implicit methods ('Radau', 'BDF', 'LSODA'), or SSDE_HOST_ODE=1, use scipy.integrate.solve_ivp on the host exactly
+    as the reference does.  The cached fused right-hand side is the same for every method."""
 
     def denoise_update_fn(model, x):
         score_fn = get_score_fn(sde, model, train=False, continuous=True)
