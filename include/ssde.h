@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 13  /* (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 13  /* (13, no new version: ssde_upfirdn2d takes kernels of 1..SSDE_FIR_MAX_TAPS taps per axis and negative pads, which crop -- ssde_upfirdn_args.taps is appended behind dst2 (a device array for kernels past 4x4; the structure grows inside the op union, so every op record keeps its size and every earlier field its offset) and ssde_upfirdn_args.flags takes the former pad word (SSDE_FIRF_GENERAL, SSDE_FIRF_TILED); a caller of version 13 zero-fills its records, so it sends flags = 0 and taps = NULL, every launch it could make keeps its kernel and its bits, and plan blobs of version 13 load unchanged, so the number stays -- an older library refuses a kernel past 4x4 by message) (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
@@ -234,19 +234,34 @@ typedef struct ssde_gn_finalize_args {
 /* ---- upfirdn2d (NHWC): zero-insert up, pad, FIR, decimate ------------------
  * replaces op/upfirdn2d.py:145-200 + op/upfirdn2d_kernel.cu:107-207 as used by
  * upsample_2d / downsample_2d / conv_downsample_2d (up_or_down_sampling.py:144-257)
- * and naive_upsample_2d / naive_downsample_2d (:59-69, as 2x2 box kernels). */
+ * and naive_upsample_2d / naive_downsample_2d (:59-69, as 2x2 box kernels).
+ * Kernels of 1..SSDE_FIR_MAX_TAPS taps per axis, square or not.  One that fits 4x4 travels in k; a larger one is read
+ * from the device array taps (k is then ignored).  pad0 / pad1 go in front of / behind both axes; a negative pad crops
+ * (upfirdn2d_native, op/upfirdn2d.py:176-181).  h_out = (h_in * up + pad0 + pad1 - kh) / down + 1 (w alike) must be
+ * positive and is checked before any launch.
+ * Kernels: the 4x4 FIR on channels % 32 == 0 with up, down in {1, 2} (not both 2) and pads >= 0 has its own LDS-tiled
+ * kernel; the same shapes with another kernel of at least 3x3 taps take the LDS-tiled kernel for any tap count where it was
+ * measured to win (the rule and the timings: csrc/resample.hip above ssde_upfirdn2d); everything else takes one lane per
+ * output. */
+#define SSDE_FIR_MAX_TAPS 16
+enum {
+  SSDE_FIRF_GENERAL = 1,   /* one lane per output whatever the shape (tests, A/B timing) */
+  SSDE_FIRF_TILED = 2      /* the any-tap-count LDS-tiled kernel wherever it is legal, also for kernels that fit 4x4 (the 4x4 FIR
+                              with pads >= 0 keeps its own kernel); SSDE_FIRF_GENERAL wins over it */
+};
 typedef struct ssde_upfirdn_args {
   ssde_src src;                  /* p1 must be NULL; prologue allowed */
   int32_t n, h_in, w_in, c;
   int32_t h_out, w_out;
-  int32_t up, down, pad0, pad1;
-  int32_t kh, kw;                /* <= 4 */
-  float k[16];                   /* row-major [kh][kw], UNflipped (the op flips, as upfirdn2d does) */
+  int32_t up, down, pad0, pad1;  /* pads may be negative */
+  int32_t kh, kw;                /* 1..SSDE_FIR_MAX_TAPS */
+  float k[16];                   /* kh, kw <= 4: row-major [kh][kw], UNflipped (the op flips, as upfirdn2d does) */
   float* dst;                    /* [N, h_out, w_out, c] */
   int32_t accumulate;            /* dst += result (gradient accumulation in backward programs) */
-  int32_t _pad0;
+  uint32_t flags;                /* SSDE_FIRF_* */
   float* dst2;                   /* optional second output: the same filter applied to the source WITHOUT its prologue
                                     (a residual block resamples act(GroupNorm(x)) and x, layerspp.py:250-258) */
+  const float* taps;             /* kh > 4 or kw > 4: device array, row-major [kh][kw], UNflipped; read at every launch */
 } ssde_upfirdn_args;
 
 /* ---- single-head self-attention core ----------------------------------------

@@ -27,6 +27,8 @@ GNBWDF_THREE_KERNELS, GNBWDF_DEFER_PARAMS = 1, 2
  OP_ATTN_BWD, OP_PERTURB, OP_DSM_LOSS, OP_SUMSQ_FLAT, OP_ADAM, OP_MEMSET, OP_AXPY, OP_PACK, OP_PROJECT,
  OP_GN_FINALIZE, OP_PF_DRIFT, OP_HUTCH_DIV, OP_COLSUM_FINISH, OP_GN_BWD_FINISH, OP_GN_APPLY, OP_GN_APPLY_BWD) = range(1, 35)
 GNSTATF_ANY_WIDTH = 1
+FIRF_GENERAL, FIRF_TILED = 1, 2      # include/ssde.h: SSDE_FIRF_*
+FIR_MAX_TAPS = 16
 FINISH_JOBS = 16
 COLSUMF_DEFER = 1
 PACK_CONV3, PACK_WINO3, PACK_MATRIX, PACK_VECTOR, PACK_WINO4, PACK_WINO4R, PACK_WINO4P = 1, 2, 3, 4, 5, 6, 7
@@ -116,7 +118,7 @@ class UpfirdnArgs(C.Structure):
                 ("h_out", C.c_int32), ("w_out", C.c_int32),
                 ("up", C.c_int32), ("down", C.c_int32), ("pad0", C.c_int32), ("pad1", C.c_int32),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("k", C.c_float * 16), ("dst", _fp),
-                ("accumulate", C.c_int32), ("_pad0", C.c_int32), ("dst2", _fp)]
+                ("accumulate", C.c_int32), ("flags", C.c_uint32), ("dst2", _fp), ("taps", _fp)]
 
 
 class AttnArgs(C.Structure):

@@ -496,11 +496,9 @@ class TrainEngine(E.UNetEngine):
         # the flipped kernel and these pads
         gp0 = kw - pad0 - 1
         gp1 = f["w_in"] * up - f["w_out"] * down + pad0 - up + 1
-        assert gp0 >= 0 and gp1 >= 0, "negative gradient pads are not lowered"
-        k = np.asarray(f["k"][: kh * kw], dtype=np.float32).reshape(kh, kw)[::-1, ::-1]
-        k16 = [0.0] * 16
-        for i, v in enumerate(k.reshape(-1).tolist()):
-            k16[i] = float(v)
+        assert kh == kw, "the gradient pads of a rectangular kernel differ per axis (one pad pair in ssde_upfirdn_args)"
+        taps = f["taps"].cpu().numpy() if f.get("taps") is not None else np.asarray(f["k"][: kh * kw], dtype=np.float32).reshape(kh, kw)
+        kfields = self.low.fir_kernel_fields(taps[::-1, ::-1])      # a negative gradient pad crops, as in the forward op
         direct = src["pro_mode"] == L.PRO_NONE
         if direct:
             t = self._gentry(src["p0"])
@@ -509,7 +507,7 @@ class TrainEngine(E.UNetEngine):
         else:
             dst, acc = b.buf(n, f["h_in"], f["w_in"], c, name="dP_fir"), 0
         b.add(L.OP_UPFIRDN, dict(src=_src(e[0], c), n=n, h_in=f["h_out"], w_in=f["w_out"], c=c, h_out=f["h_in"], w_out=f["w_in"],
-                                 up=down, down=up, pad0=gp0, pad1=gp1, kh=kh, kw=kw, k=k16, dst=dst, accumulate=acc), E.FC_FIR)
+                                 up=down, down=up, pad0=gp0, pad1=gp1, dst=dst, accumulate=acc, **kfields), E.FC_FIR)
         if not direct:
             self._bwd_prologue(src, dst, n, f["h_in"] * f["w_in"])
 

@@ -110,6 +110,7 @@ class ProgramBuilder:
         self.device = device
         self.specs = []      # (kind, fields, flops_class, flops)
         self.keep = []       # tensors that must outlive the program
+        self.fir_taps = {}   # (kh, kw, bytes) -> kept device tensor of a FIR kernel larger than 4x4 (Lowering.fir_kernel_fields)
 
     def buf(self, *shape, name="", persistent=False):
         return Buf(shape, name, persistent)
@@ -196,7 +197,7 @@ def _fir_pairs(specs):
     out = {}
     if os.environ.get("SSDE_FUSE_FIR", "1") == "0":
         return out
-    same = ("n", "h_in", "w_in", "c", "h_out", "w_out", "up", "down", "pad0", "pad1", "kh", "kw", "k")
+    same = ("n", "h_in", "w_in", "c", "h_out", "w_out", "up", "down", "pad0", "pad1", "kh", "kw", "k")   # and taps, by identity
     for i in range(len(specs) - 1):
         (k0, f0, _, _), (k1, f1, _, _) = specs[i], specs[i + 1]
         if k0 != L.OP_UPFIRDN or k1 != L.OP_UPFIRDN or i in out:
@@ -206,7 +207,7 @@ def _fir_pairs(specs):
             continue
         if s0["pro_mode"] == L.PRO_NONE or s1["pro_mode"] != L.PRO_NONE or f0["dst"] is f1["dst"]:
             continue
-        if f0.get("accumulate") or f1.get("accumulate") or any(f0[k] != f1[k] for k in same):
+        if f0.get("accumulate") or f1.get("accumulate") or any(f0[k] != f1[k] for k in same) or f0.get("taps") is not f1.get("taps"):
             continue
         out[i], out[i + 1] = f1["dst"], None
     return out
@@ -950,12 +951,35 @@ class Lowering:
         w_out = (w_in * up + pad[0] + pad[1] - kw) // down + 1
         dst = self.b.buf(self.n, h_out, w_out, n_ch, name=name)
         self._materialize_stats(src.get("_gn"))
-        k16 = [0.0] * 16
-        for i, v in enumerate(taps.reshape(-1).tolist()):
-            k16[i] = float(v)
         self.b.add(L.OP_UPFIRDN, dict(src=src, n=self.n, h_in=h_in, w_in=w_in, c=n_ch, h_out=h_out, w_out=w_out,
-                                      up=up, down=down, pad0=pad[0], pad1=pad[1], kh=kh, kw=kw, k=k16, dst=dst), FC_FIR)
+                                      up=up, down=down, pad0=pad[0], pad1=pad[1], dst=dst, **self.fir_kernel_fields(taps)), FC_FIR)
         return dst, h_out, w_out
+
+    def fir_kernel_fields(self, taps):
+        """kh / kw / k / taps of an OP_UPFIRDN spec.  A kernel that fits 4x4 travels in the record (k); a larger one is a device
+        tensor the builder keeps alive -- one per distinct kernel, so that _fir_pairs compares it by identity, and a constant
+        region of an exported plan like every other kept table."""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        kh, kw = taps.shape
+        if not (1 <= kh <= L.FIR_MAX_TAPS and 1 <= kw <= L.FIR_MAX_TAPS):
+            raise ValueError("upfirdn2d: a %dx%d kernel (fir_kernel of %d taps); at most %d taps per axis"
+                             % (kh, kw, max(kh, kw), L.FIR_MAX_TAPS))
+        k16, t = [0.0] * 16, None
+        if kh <= 4 and kw <= 4:
+            k16[:kh * kw] = [float(v) for v in taps.reshape(-1).tolist()]
+        else:
+            key = (kh, kw, taps.tobytes())
+            t = self.b.fir_taps.get(key)
+            if t is None:
+                t = self.b.fir_taps[key] = self.b.tensor(torch.from_numpy(taps.copy()).to(self.b.device))
+        return dict(kh=kh, kw=kw, k=k16, taps=t)
+
+
+def fir_pads(n_taps, up=False, conv=1):
+    """(pad0, pad1) of upsample_2d / downsample_2d / conv_downsample_2d for a fir_kernel of n_taps taps and factor 2
+    (models/up_or_down_sampling.py:144-257): p = n_taps - 2 (+ conv - 1 in front of a conv x conv stride-2 convolution)."""
+    p = n_taps - 2 + (conv - 1)
+    return ((p + 1) // 2 + (1 if up else 0), p // 2)
 
 
 # --------------------------------------------------------------------------- the U-Net engine
@@ -1129,7 +1153,7 @@ class UNetEngine:
                 hh, ww = hh // 2, ww // 2
                 if model.progressive_input == "input_skip":
                     taps = fir_taps(fk) if fir else fir_taps([1, 1])
-                    pd = (1, 1) if fir else (0, 0)
+                    pd = fir_pads(taps.shape[0])
                     pyr, _, _ = low.upfirdn(_src(pyr, pyr_c), pyr_c, hh * 2, ww * 2, taps, down=2, pad=pd, name="pyr_down")
                     comb = mods[idx]; idx += 1
                     if comb.method != "sum":
@@ -1142,8 +1166,10 @@ class UNetEngine:
                     down = mods[idx]; idx += 1
                     if not fir:
                         raise NotImplementedError("progressive_input='residual' without FIR is not lowered")
-                    # conv_downsample_2d: FIR with pad (2,2) then stride-2 VALID conv (up_or_down_sampling.py:144-178)
-                    pf, ph, pw = low.upfirdn(_src(pyr, pyr_c), pyr_c, hh * 2, ww * 2, fir_taps(fk), pad=(2, 2), name="pyr_fir")
+                    # conv_downsample_2d: FIR with pad ((p+1)//2, p//2), p = taps - 2 + 3 - 1 -- (2,2) for four taps -- then
+                    # stride-2 VALID conv (up_or_down_sampling.py:144-178)
+                    pf, ph, pw = low.upfirdn(_src(pyr, pyr_c), pyr_c, hh * 2, ww * 2, fir_taps(fk), pad=fir_pads(len(fk), conv=3),
+                                             name="pyr_fir")
                     hn = b.buf(n, hh, ww, cur_c, name="pyr")
                     low.conv(hn, hh, ww, cur_c, main=_src(pf, pyr_c), w_main=self._w3(down.Conv2d_0, cin_pad=pyr_c),
                              h_in=ph, w_in=pw, stride=2, pad=0, bias=self._bias(down.Conv2d_0), resid=h, scale=skip_scale,
@@ -1171,7 +1197,7 @@ class UNetEngine:
                 up_pyr = None
                 if pyramid is not None:
                     taps = fir_taps(fk, gain=4.0) if fir else fir_taps([1, 1], gain=4.0)
-                    pd = (2, 1) if fir else (1, 0)
+                    pd = fir_pads(taps.shape[0], up=True)
                     up_pyr, _, _ = low.upfirdn(_src(pyramid, 4), 4, hh // 2, ww // 2, taps, up=2, pad=pd, name="pyr_up")
                 gn = low.gn_stats(h, cur_c, hh * ww, gn_m)
                 pn = b.buf(n, hh, ww, 4, name="pyramid")
@@ -1298,10 +1324,10 @@ class UNetEngine:
             assert t2 is None
             if m.up:
                 taps = fir_taps(m.fir_kernel, gain=4.0) if m.fir else fir_taps([1, 1], gain=4.0)
-                kw = dict(up=2, pad=(2, 1) if m.fir else (1, 0))
+                kw = dict(up=2, pad=fir_pads(taps.shape[0], up=True))
             else:
                 taps = fir_taps(m.fir_kernel) if m.fir else fir_taps([1, 1])
-                kw = dict(down=2, pad=(1, 1) if m.fir else (0, 0))
+                kw = dict(down=2, pad=fir_pads(taps.shape[0]))
             hr, ho, wo = low.upfirdn(low.src(t, c, hh * ww, pro=L.PRO_GN_SILU, gn=gn0), c, hh, ww, taps, name="res_h_rs", **kw)
             xr, _, _ = low.upfirdn(_src(t, c), c, hh, ww, taps, name="res_x_rs", **kw)
             main0, skip_t, skip_c, skip_t2, skip_c2 = _src(hr, c), xr, c, None, 0

@@ -150,14 +150,19 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
     return dst
 
 
-def upfirdn2d_nhwc(x, kernel, up=1, down=1, pad=(0, 0), pro=L.PRO_NONE, gn=None, dual=False, accumulate_into=None):
-    """dual=True also returns the same filter applied to the source without its prologue (one launch, dst2);
-    accumulate_into: an existing output tensor the result is added to."""
+def upfirdn2d_nhwc(x, kernel, up=1, down=1, pad=(0, 0), pro=L.PRO_NONE, gn=None, dual=False, accumulate_into=None, flags=0):
+    """kernel: [kh][kw] taps, 1..16 per axis; pads may be negative (they crop, as upfirdn2d_native does).
+    dual=True also returns the same filter applied to the source without its prologue (one launch, dst2);
+    accumulate_into: an existing output tensor the result is added to; flags: SSDE_FIRF_* (_lib.FIRF_GENERAL / FIRF_TILED)."""
     _need_cuda(x)
     n, h, w, c = x.shape
     kh, kw = kernel.shape
+    if not (1 <= kh <= L.FIR_MAX_TAPS and 1 <= kw <= L.FIR_MAX_TAPS):
+        raise ValueError("upfirdn2d: a %dx%d kernel; at most %d taps per axis" % (kh, kw, L.FIR_MAX_TAPS))
     h_out = (h * up + pad[0] + pad[1] - kh) // down + 1
     w_out = (w * up + pad[0] + pad[1] - kw) // down + 1
+    if h_out < 1 or w_out < 1:
+        raise ValueError("upfirdn2d: output size %dx%d is not positive" % (h_out, w_out))
     dst = torch.empty(n, h_out, w_out, c, device=x.device) if accumulate_into is None else accumulate_into
     dst2 = torch.empty(n, h_out, w_out, c, device=x.device) if dual else None
     a = L.UpfirdnArgs()
@@ -165,9 +170,14 @@ def upfirdn2d_nhwc(x, kernel, up=1, down=1, pad=(0, 0), pro=L.PRO_NONE, gn=None,
     a.accumulate = int(accumulate_into is not None)
     a.dst2 = _p(dst2) if dual else None
     a.n, a.h_in, a.w_in, a.c, a.h_out, a.w_out = n, h, w, c, h_out, w_out
-    a.up, a.down, a.pad0, a.pad1, a.kh, a.kw = up, down, pad[0], pad[1], kh, kw
-    for i, v in enumerate(np.asarray(kernel.detach().cpu(), dtype=np.float32).reshape(-1).tolist()):
-        a.k[i] = v
+    a.up, a.down, a.pad0, a.pad1, a.kh, a.kw, a.flags = up, down, pad[0], pad[1], kh, kw, flags
+    taps = None
+    if kh <= 4 and kw <= 4:
+        for i, v in enumerate(np.asarray(kernel.detach().cpu(), dtype=np.float32).reshape(-1).tolist()):
+            a.k[i] = v
+    else:                       # past 4x4 the launch reads the taps from device memory
+        taps = kernel.detach().to(x.device, torch.float32).contiguous()
+        a.taps = _p(taps)
     a.dst = _p(dst)
     L.check(L.load().ssde_upfirdn2d(C.byref(a), _stream()), "ssde_upfirdn2d")
     return (dst, dst2) if dual else dst

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .. import hipops
+from .. import _lib as L, hipops
 
 
 def _flip_taps(kernel):
@@ -17,7 +17,8 @@ def _flip_taps(kernel):
 
 class UpFirDn2d(torch.autograd.Function):
     """op/upfirdn2d.py:88-142: forward = ssde_upfirdn2d; backward = the same kernel with up/down swapped, the
-    flipped taps and the gradient pads of :111-116 (and again the forward op for the double backward)."""
+    flipped taps and the gradient pads of :111-116 (and again the forward op for the double backward).  The C ABI has one
+    pad pair for both axes, so the backward of a launch whose two axes need different gradient pads is refused."""
 
     @staticmethod
     def forward(ctx, input, kernel, up, down, pad):
@@ -27,27 +28,32 @@ class UpFirDn2d(torch.autograd.Function):
         x = hipops.to_nhwc(input.contiguous().float(), c_pad=(c + 3) // 4 * 4)
         y = hipops.upfirdn2d_nhwc(x, kernel, up=up, down=down, pad=pad)
         out = hipops.to_nchw(y, c=c)
-        g_pad = (kw - p0 - 1, w * up - out.shape[3] * down + p0 - up + 1)
-        if min(g_pad) < 0:
-            raise NotImplementedError("upfirdn2d backward with negative gradient pads")
-        ctx.cfg = (up, down, pad, g_pad)
+        # gradient pads per axis (op/upfirdn2d.py:111-116); negative ones crop
+        g_pad_y = (kh - p0 - 1, h * up - out.shape[2] * down + p0 - up + 1)
+        g_pad_x = (kw - p0 - 1, w * up - out.shape[3] * down + p0 - up + 1)
+        ctx.cfg = (up, down, g_pad_y, g_pad_x)
         ctx.save_for_backward(kernel)
         return out
 
     @staticmethod
     def backward(ctx, grad_output):
         (kernel,) = ctx.saved_tensors
-        up, down, pad, g_pad = ctx.cfg
-        grad_input = UpFirDn2d.apply(grad_output, _flip_taps(kernel), down, up, g_pad)
+        up, down, g_pad_y, g_pad_x = ctx.cfg
+        if g_pad_y != g_pad_x:
+            # ssde_upfirdn_args has one pad pair for both axes: a rectangular kernel (or a map whose two sides leave different
+            # remainders when decimated) would need one per axis
+            raise NotImplementedError("upfirdn2d backward: the gradient pads differ per axis (%s rows, %s columns)"
+                                      % (g_pad_y, g_pad_x))
+        grad_input = UpFirDn2d.apply(grad_output, _flip_taps(kernel), down, up, g_pad_x)
         return grad_input, None, None, None, None
 
 
 def upfirdn2d(input, kernel, up=1, down=1, pad=(0, 0)):
-    """op/upfirdn2d.py:145-156."""
+    """op/upfirdn2d.py:145-156.  Kernels of up to 16x16 taps, square or not; negative pads crop."""
     if input.device.type == "cpu":
         raise RuntimeError("score_sde_pytorch_amd.op.upfirdn2d runs on the MI355X only (no CPU fallback)")
-    if kernel.dim() != 2 or max(kernel.shape) > 4:
-        raise ValueError("upfirdn2d: kernel must be 2-D, at most 4x4")
+    if kernel.dim() != 2 or max(kernel.shape) > L.FIR_MAX_TAPS:
+        raise ValueError("upfirdn2d: kernel must be 2-D, at most %dx%d" % (L.FIR_MAX_TAPS, L.FIR_MAX_TAPS))
     return UpFirDn2d.apply(input, kernel.to(input.device, torch.float32), up, down, (pad[0], pad[1]))
 
 
