@@ -486,6 +486,9 @@ enum { SSDE_GNBWDF_THREE_KERNELS = 1u,     /* ssde_gn_bwd_reduce with g0 / g1: a
        SSDE_GNBWDF_DEFER_PARAMS = 2u };    /* dgamma / dbeta are NOT written: the per-(sample, slice) channel sums stay in scratch
                                             * ([n * slices][c][2]; slices = 1 on the one-pass path) for a later ssde_gn_bwd_finish */
 
+/* The dropout of `src` (drop_thresh != 0) is honoured in EVERY prologue mode, as in the forward and the weight gradient:
+ * dp is multiplied by the mask of element pix * (c0+c1) + channel of the virtual concat tensor -- in SSDE_PRO_NONE too,
+ * where p0/p1 may still be NULL (the mask needs no x). */
 typedef struct ssde_prologue_bwd_args {
   ssde_src src;            /* forward source (p0/p1 may be NULL for SSDE_PRO_NONE) */
   const float* dp;         /* [N*hw, dp_ld] */

@@ -491,9 +491,16 @@ __global__ __launch_bounds__(256) void prologue_bwd_kernel(const PbParams p, con
           if (pro.drop) du *= ssde_keep(pix * (uint32_t)C + (uint32_t)(ch + k), pro);
           d[k] = rs[u] * (du * gm[k] - A[u] - xh * B[u]);
         }
-      } else if (pro.silu) {
+      } else {
+        if (pro.silu) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) d[k] *= ssde_silu_grad(x[k]);
+          for (int k = 0; k < 4; ++k) d[k] *= ssde_silu_grad(x[k]);
+        }
+        // the mask of the forward (ssde_pro_apply masks in every mode): element index in the virtual concat tensor, no x needed
+        if (pro.drop) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) d[k] *= ssde_keep(pix * (uint32_t)C + (uint32_t)(ch + k), pro);
+        }
       }
       float4 r = make_float4(d[0] * p.scale, d[1] * p.scale, d[2] * p.scale, d[3] * p.scale);
       if (acc) { r.x += old[u].x; r.y += old[u].y; r.z += old[u].z; r.w += old[u].w; }
