@@ -432,13 +432,11 @@ class TrainEngine(E.UNetEngine):
             dst, resid = b.buf(n, h_in, w_in, ctot, name="dP"), None
         gsrc = _src(g, g_ld)
         if ksize == 3:
-            wino = low.wino_ok(h_in, w_in, ctot, g_ld) if stride == 1 else 0
-            pack = {8: E.pack_wino4p_weight, 6: E.pack_wino4r_weight, 4: E.pack_wino4_weight, 2: E.pack_wino_weight}.get(wino, E.pack_conv_weight)
-            wd = self.weights.derived(wpacked, lambda w: pack(w.permute(1, 0, 2, 3).flip(2, 3)),
-                                      {8: "dgrad_wino4p", 6: "dgrad_wino4r", 4: "dgrad_wino4", 2: "dgrad_wino"}.get(wino, "dgrad"))
+            route = low.conv3_route(h_in, w_in, ctot, g_ld) if stride == 1 else E.DIRECT
+            wd = self.weights.derived(wpacked, route)
             if stride == 1:
                 low.conv(dst, h_in, w_in, ctot, main=gsrc, w_main=wd, h_in=ho, w_in=wo, stride=1, pad=1, resid=resid,
-                         resid_post=1, scale=scale, wino=wino)
+                         resid_post=1, scale=scale, route=route)
             else:
                 # transposed strided conv = zero-insertion (upfirdn, up=2, 1x1 kernel) + stride-1 conv with pad 2, cropped
                 # (an end-padded forward, pad_end: the gradient of the padded row / column falls outside the crop to h_in x w_in)
@@ -447,8 +445,7 @@ class TrainEngine(E.UNetEngine):
                 low.conv(dst, h_in, w_in, ctot, main=_src(gz, g_ld), w_main=wd, h_in=hz, w_in=wz, stride=1, pad=2,
                          resid=resid, resid_post=1, scale=scale)
         else:
-            wd = self.weights.derived(wpacked, lambda m: E.pack_matrix(m.t().contiguous()), "dgrad")
-            low.conv(dst, ho, wo, ctot, aux=gsrc, w_aux=wd, resid=resid, resid_post=1, scale=scale)
+            low.conv(dst, ho, wo, ctot, aux=gsrc, w_aux=self.weights.derived(wpacked), resid=resid, resid_post=1, scale=scale)
         if not direct:
             self._bwd_prologue(src, dst, n, h_in * w_in)
 

@@ -443,7 +443,7 @@ int ssde_conv_wino4r_launch(const ssde_conv_args* a, void* stream, int* lds_out)
   SSDE_REQUIRE(36ull * (unsigned long long)p.T * (unsigned)p.Ctot * 4ull < (1ull << 32),
                "conv(winograd 4x4, register-fed): a transformed input of 4 GB or more is not addressable by this kernel");
   // Split the reduction when the launch would leave half of the CUs or more without a workgroup (8x8 maps at batch 256: 128
-  // tiles of 8 images x 64 couts): ssde_conv_wino4r_splits, the rule engine.Lowering.wino_ok mirrors.  (dst is the hand-over
+  // tiles of 8 images x 64 couts): ssde_conv_wino4r_splits, the rule engine.Lowering.conv3_route mirrors.  (dst is the hand-over
   // buffer: not when the residual aliases it)
   const int wgs = ssde_cdiv(p.m_tiles, 8) * 8 * p.n_tiles;
   p.ksplit = a->resid != a->dst ? ssde_conv_wino4r_splits(wgs, p.Ctot, a->c_out, a->flags) : 1;

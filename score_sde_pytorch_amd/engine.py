@@ -23,6 +23,7 @@ groups.  It runs as launches of its own (statistics pass + ssde_gn_apply) and it
 import ctypes as C
 import math
 import os
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -35,7 +36,7 @@ INV_SQRT2 = float(1.0 / np.sqrt(2.0))
 # flops_class tags (echoed by ssde_program_run_timed; bench.py groups by them)
 FC_OTHER, FC_CONV3, FC_CONV1, FC_ATTN, FC_GN, FC_FIR = 0, 1, 2, 3, 4, 5
 
-# Lowering.wino_ok: the smallest batch whose 4x4-map 3x3 convolutions take the position-batched F(4x4,3x3) form (conv_wino4p.hip).
+# Lowering.conv3_route: the smallest batch whose 4x4-map 3x3 convolutions take the position-batched F(4x4,3x3) form (conv_wino4p.hip).
 # Measured against the direct kernel, GroupNorm + SiLU prologue (tools/w4p_bench.py), ms direct -> position-batched:
 #   batch 256:  256->256 0.064 -> 0.039   512->256 0.109 -> 0.055   768->256 0.153 -> 0.072
 #   batch 128:  256->256 0.039 -> 0.035   512->256 0.067 -> 0.042   768->256 0.093 -> 0.051
@@ -384,18 +385,22 @@ _WINO4_G = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6
                          [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], dtype=torch.float64)
 
 
+def _wino4_u(w):
+    """[Cout, Cin, 3, 3] -> U = G g G^T of F(4x4,3x3), formed in fp64, stored in fp32: [roundup(Cout, 64)][roundup(Cin, 4)][36], zero-padded"""
+    cout, cin = w.shape[0], w.shape[1]
+    G = _WINO4_G.to(w.device)
+    u = torch.einsum("ak,ockl,bl->ocab", G, w.detach().to(torch.float64), G).to(torch.float32)     # [Cout, Cin, 6, 6]
+    full = torch.zeros((cout + 63) // 64 * 64, (cin + 3) // 4 * 4, 36, dtype=torch.float32, device=w.device)
+    full[:cout, :cin] = u.reshape(cout, cin, 36)
+    return full
+
+
 def pack_wino4_weight(w):
     """[Cout, Cin, 3, 3] -> Winograd F(4x4,3x3) weights U = G g G^T (formed in fp64, stored in fp32) arranged as the LDS
     image conv_wino4.hip reads: [ceil(Cin/4)][ceil(Cout/64)][8 waves][9][32 couts][4 channels] -- wave (q, h) of a workgroup
     owns the transform positions q + 4 j (j = 0..8) and the cout half h of the 64-cout tile, and its 4.5 KB are contiguous."""
-    cout, cin = w.shape[0], w.shape[1]
-    G = _WINO4_G.to(w.device)
-    u = torch.einsum("ak,ockl,bl->ocab", G, w.detach().to(torch.float64), G).to(torch.float32)     # [Cout, Cin, 6, 6]
-    c4, nt = (cin + 3) // 4, (cout + 63) // 64
-    full = torch.zeros(nt * 64, c4 * 4, 36, dtype=torch.float32, device=w.device)
-    full[:cout, :cin] = u.reshape(cout, cin, 36)
     # [nt, h, cl, c4, e, j, q] -> [c4, nt, q, h, j, cl, e]   (pos = 4 j + q, cout = 64 nt + 32 h + cl)
-    return full.reshape(nt, 2, 32, c4, 4, 9, 4).permute(3, 0, 6, 1, 5, 2, 4).contiguous()
+    return _wino4_u(w).reshape(-1, 2, 32, (w.shape[1] + 3) // 4, 4, 9, 4).permute(3, 0, 6, 1, 5, 2, 4).contiguous()
 
 
 def pack_wino4r_weight(w):
@@ -404,13 +409,8 @@ def pack_wino4r_weight(w):
     [ceil(Cin/4)][ceil(Cout/64)][8 waves][4 positions x [64 lanes][4] | [64 lanes][2]] -- wave w owns transform positions
     4 w .. 4 w + 3 with both 32-cout halves of the tile and half w & 1 of position 32 + (w >> 1); lane (lh, li) holds channels
     2 lh, 2 lh + 1 of couts li and 32 + li (four floats per full position), of cout 32 (w & 1) + li for the half position."""
-    cout, cin = w.shape[0], w.shape[1]
-    G = _WINO4_G.to(w.device)
-    u = torch.einsum("ak,ockl,bl->ocab", G, w.detach().to(torch.float64), G).to(torch.float32)     # [Cout, Cin, 6, 6]
-    c4, nt = (cin + 3) // 4, (cout + 63) // 64
-    full = torch.zeros(nt * 64, c4 * 4, 36, dtype=torch.float32, device=w.device)
-    full[:cout, :cin] = u.reshape(cout, cin, 36)
-    v = full.reshape(nt, 2, 32, c4, 2, 2, 36)                    # [nt, half, li, c4, lh, e2, pos]
+    c4, nt = (w.shape[1] + 3) // 4, (w.shape[0] + 63) // 64
+    v = _wino4_u(w).reshape(nt, 2, 32, c4, 2, 2, 36)             # [nt, half, li, c4, lh, e2, pos]
     # full positions: [c4, nt, wave, i, lh, li, half, e2]  (pos = 4 wave + i)
     fp = v[..., :32].reshape(nt, 2, 32, c4, 2, 2, 8, 4).permute(3, 0, 6, 7, 4, 2, 1, 5).reshape(c4, nt, 8, 4 * 64 * 4)
     # half positions 32 + k: wave = 2 k + half -> [c4, nt, k, half, lh, li, e2]
@@ -421,18 +421,40 @@ def pack_wino4r_weight(w):
 def pack_wino4p_weight(w):
     """[Cout, Cin, 3, 3] -> the F(4x4,3x3) weights U = G g G^T (formed in fp64, stored in fp32) position-major for the 36 GEMMs
     of conv_wino4p.hip (SSDE_TILE_WINOGRAD4P / SSDE_PACK_WINO4P): [36 positions][ceil(Cin/4)][roundup(Cout, 64)][4 channels]."""
-    cout, cin = w.shape[0], w.shape[1]
-    G = _WINO4_G.to(w.device)
-    u = torch.einsum("ak,ockl,bl->ocab", G, w.detach().to(torch.float64), G).to(torch.float32)     # [Cout, Cin, 6, 6]
-    c4, cpad = (cin + 3) // 4, (cout + 63) // 64 * 64
-    full = torch.zeros(cpad, c4 * 4, 36, dtype=torch.float32, device=w.device)
-    full[:cout, :cin] = u.reshape(cout, cin, 36)
-    return full.reshape(cpad, c4, 4, 36).permute(3, 1, 0, 2).contiguous()
+    return _wino4_u(w).unflatten(1, (-1, 4)).permute(3, 1, 0, 2).contiguous()
 
 
 def pack_matrix(w):
     """[Cout, Cin] (nn.Linear / 1x1 conv orientation) -> [ceil(Cin/8)][roundup(Cout,64)][8]."""
     return pack_conv_weight(w.reshape(w.shape[0], w.shape[1], 1, 1))
+
+
+class Conv3Route(NamedTuple):
+    """One kernel route of a stride-1 3x3 convolution: what the host needs to feed it (Lowering.conv3_route chooses among them)."""
+    name: str
+    tile: int            # ssde_conv_args.tile
+    pack_kind: int       # the device re-pack of its weight image (ssde_pack_weights)
+    pack: Callable       # the same packing in torch
+    takes_v: bool        # may own a transformed-input buffer (F4: optional by-product for the weight gradient, F4R: required)
+    needs_ws: bool       # needs the ssde_conv_ws_floats workspace
+
+
+DIRECT = Conv3Route("direct", L.TILE_AUTO, L.PACK_CONV3, pack_conv_weight, False, False)       # conv_mfma.hip
+F2 = Conv3Route("f2", L.TILE_WINOGRAD, L.PACK_WINO3, pack_wino_weight, False, False)            # F(2x2,3x3), conv_wino.hip
+F4 = Conv3Route("f4", L.TILE_WINOGRAD4, L.PACK_WINO4, pack_wino4_weight, True, False)           # fused F(4x4,3x3), conv_wino4.hip
+F4R = Conv3Route("f4r", L.TILE_WINOGRAD4R, L.PACK_WINO4R, pack_wino4r_weight, True, False)      # wino4_xform.hip + conv_wino4r.hip
+F4P = Conv3Route("f4p", L.TILE_WINOGRAD4P, L.PACK_WINO4P, pack_wino4p_weight, False, True)      # position-batched, conv_wino4p.hip
+CONV3_ROUTES = (DIRECT, F2, F4, F4R, F4P)
+
+
+def conv3_route_of_tile(tile):
+    """The route behind an ssde_conv_args.tile value; every other value (the explicit direct tiles TILE_256x64 .. TILE_256x32) is DIRECT."""
+    return next((r for r in CONV3_ROUTES if r.tile == tile), DIRECT)
+
+
+def wino4_v_floats(n, h, w, c):
+    """Floats of the transformed input B^T x B of an F(4x4,3x3) convolution (36 / 16 of the input tensor)."""
+    return 36 * n * (h // 4) * (w // 4) * c
 
 
 class _Entry:
@@ -486,12 +508,9 @@ class WeightStore:
         return self.device.type == "cuda" if isinstance(self.device, torch.device) else str(self.device).startswith("cuda")
 
     # -- typed registrations -------------------------------------------------------------------
-    def conv3(self, param, cin_pad=None, cout_pad=None, wino=False):
-        """[Cout, Cin, 3, 3] conv weight, optionally zero-padded to cin_pad / cout_pad channels; wino (see
-        Lowering.wino_ok): 2 / True = packed for the Winograd F(2x2,3x3) kernel (G g G^T, conv_wino.hip), 4 = for the fused
-        F(4x4,3x3) kernel (conv_wino4.hip), 6 = per lane for the
-        register-fed matrix kernel (conv_wino4r.hip), 8 = position-major for the position-batched GEMMs (conv_wino4p.hip),
-        0 = for the direct one."""
+    def conv3(self, param, cin_pad=None, cout_pad=None, route=DIRECT):
+        """[Cout, Cin, 3, 3] conv weight, optionally zero-padded to cin_pad / cout_pad channels, packed for the kernel of
+        `route` (a row of CONV3_ROUTES, see Lowering.conv3_route)."""
         def logical(w):
             w = w.to(torch.float32)
             if cin_pad and w.shape[1] < cin_pad:
@@ -502,10 +521,8 @@ class WeightStore:
         cout_l, cin_l = max(param.shape[0], cout_pad or 0), max(param.shape[1], cin_pad or 0)
         meta = dict(kind="conv3", sources=[param], logical=logical, dims=(cout_l, cin_l),
                     parts=[dict(param=param, row0=0, rows=param.shape[0], transpose=False)], cin_store=param.shape[1])
-        pack = {8: pack_wino4p_weight, 6: pack_wino4r_weight, 4: pack_wino4_weight}.get(wino, pack_wino_weight if wino else pack_conv_weight)
-        kind = {8: L.PACK_WINO4P, 6: L.PACK_WINO4R, 4: L.PACK_WINO4}.get(wino, L.PACK_WINO3 if wino else L.PACK_CONV3)
-        recipe = [dict(kind=kind, src=param, cout=param.shape[0], cin=param.shape[1], cout_l=cout_l, cin_l=cin_l, flags=0, n="dst")]
-        return self.add([param], lambda w: pack(logical(w)), meta, recipe)
+        recipe = [dict(kind=route.pack_kind, src=param, cout=param.shape[0], cin=param.shape[1], cout_l=cout_l, cin_l=cin_l, flags=0, n="dst")]
+        return self.add([param], lambda w: route.pack(logical(w)), meta, recipe)
 
     def matrix(self, parts, cin_pad=None):
         """Rows-concatenated [Cout_i, Cin] matrices; parts = [(param, transpose)], transpose for NIN's [in, out]."""
@@ -552,20 +569,20 @@ class WeightStore:
             recipe = [dict(kind=L.PACK_VECTOR, src=d["param"], r_off=d["off"], n="src") for d in desc]
         return self.add(params, fn, dict(kind="vector", mode=mode, sources=list(params), parts=desc), recipe)
 
-    def derived(self, packed, fn, tag):
-        """The input-gradient packing of an existing entry's logical weight: fn(logical) -> packed, with tag
-        'dgrad' (direct conv / matrix), 'dgrad_wino', 'dgrad_wino4', 'dgrad_wino4r' or 'dgrad_wino4p'."""
+    def derived(self, packed, route=None):
+        """The input-gradient packing of an existing entry's logical weight: a 3x3 weight with in / out swapped and the taps
+        rotated by 180 degrees, packed for the kernel of `route`; a matrix (route=None) transposed."""
         meta = self.meta[id(packed)]
-        key = (id(packed), tag)
+        key = (id(packed), route)
         if key not in self.meta:
             cout_l, cin_l = meta["dims"]
             if meta["kind"] == "conv3":
                 p_ = meta["sources"][0]
-                kind = {"dgrad_wino": L.PACK_WINO3, "dgrad_wino4": L.PACK_WINO4, "dgrad_wino4r": L.PACK_WINO4R,
-                        "dgrad_wino4p": L.PACK_WINO4P}.get(tag, L.PACK_CONV3)
-                recipe = [dict(kind=kind, src=p_, cout=p_.shape[0], cin=p_.shape[1],
+                fn = lambda w: route.pack(w.permute(1, 0, 2, 3).flip(2, 3))  # noqa: E731
+                recipe = [dict(kind=route.pack_kind, src=p_, cout=p_.shape[0], cin=p_.shape[1],
                                cout_l=cin_l, cin_l=cout_l, flags=1, n="dst")]
             else:
+                fn = lambda m: pack_matrix(m.t().contiguous())  # noqa: E731
                 # D = M^T: part rows become column ranges; a transposed (NIN) part is read straight, a plain one swapped
                 recipe = [dict(kind=L.PACK_MATRIX, src=d["param"], cout=d["param"].shape[0], cin=int(np.prod(d["param"].shape[1:])),
                                cout_l=cin_l, cin_l=0, flags=int(not d["transpose"]), r_off=0, c_off=d["row0"], n="src")
@@ -794,19 +811,16 @@ class Lowering:
             self.b.add(L.OP_GN_FINALIZE, fin, FC_GN)
 
     def conv(self, dst, h_out, w_out, c_out, main=None, w_main=None, h_in=0, w_in=0, stride=1, pad=1,
-             aux=None, w_aux=None, bias=None, chan_add=None, chan_add_ld=0, resid=None, scale=1.0, tile=L.TILE_AUTO,
-             resid_post=0, wino=False, stats=False, pad_end=0):
-        """wino (2 / True, 4, 6 or 8): w_main is Winograd-packed (see wino_ok); a fused 1x1 source then runs as a second launch.
+             aux=None, w_aux=None, bias=None, chan_add=None, chan_add_ld=0, resid=None, scale=1.0, resid_post=0, route=None,
+             stats=False, pad_end=0):
+        """route (a row of CONV3_ROUTES; None: DIRECT): w_main is packed for it; a Winograd route runs a fused 1x1 source as a second launch.
         pad_end: zero rows / columns after the last input row / column on top of pad (the one-sided F.pad(x, (0, 1, 0, 1)) of
         DDPM's Downsample, models/layers.py:608-611); direct kernel only.
         stats=True: dst feeds a GroupNorm later -- when the launch plan allows it (ssde_conv_gn_slices) the epilogue
         also writes the tensor's partial statistics and gn_stats() turns into a finalize of a few thousand floats."""
-        split_tmp = None
-        if wino:
-            assert main is not None and stride == 1 and pad == 1 and pad_end == 0 and (h_in, w_in) == (h_out, w_out)
-            tile = {8: L.TILE_WINOGRAD4P, 6: L.TILE_WINOGRAD4R, 4: L.TILE_WINOGRAD4}.get(wino, L.TILE_WINOGRAD)
-            if aux is not None:
-                split_tmp = self.b.buf(self.n, h_out, w_out, c_out, name="wino_tmp")
+        route = route or DIRECT
+        assert route is DIRECT or (main is not None and stride == 1 and pad == 1 and pad_end == 0 and (h_in, w_in) == (h_out, w_out))
+        split_tmp = self.b.buf(self.n, h_out, w_out, c_out, name="wino_tmp") if route is not DIRECT and aux is not None else None
         px = self.n * h_out * w_out
         flops = 0.0
         if main is not None:
@@ -816,21 +830,20 @@ class Lowering:
         fields = dict(
             main=main if main is not None else _NOSRC, aux=aux if aux is not None else _NOSRC,
             w_main=w_main, w_aux=w_aux, n=self.n, h_in=h_in, w_in=w_in, h_out=h_out, w_out=w_out, c_out=c_out,
-            ksize=3 if main is not None else 0, stride=stride, pad=pad, pad_end=pad_end, tile=tile, bias=bias, chan_add=chan_add,
+            ksize=3 if main is not None else 0, stride=stride, pad=pad, pad_end=pad_end, tile=route.tile, bias=bias, chan_add=chan_add,
             chan_add_ld=chan_add_ld, resid_post=resid_post, resid=resid, out_scale=float(scale), dst=dst, gn_part=None,
             wino_v=None, _split_tmp=split_tmp)
-        if wino in (4, 6):
+        if route.takes_v:
             # the transformed input B^T pro(x) B in HBM (2.25x the input): the two-kernel form (wino4_xform.hip + conv_wino4r.hip) cannot do without
             # it; in a training forward the one-kernel form leaves it behind as a by-product when the layer's weight gradient
             # takes the F(4x4,3x3) route (ssde_conv_args.wino_v -> ssde_wgrad_args.v_pre, backward.TrainEngine._bwd_branch:
             # alive until that weight gradient has been enqueued)
-            ctot = main["c0"] + main["c1"]
-            v_floats = 36 * self.n * (h_out // 4) * (w_out // 4) * ctot
+            v_floats = wino4_v_floats(self.n, h_out, w_out, main["c0"] + main["c1"])
             takes = getattr(self, "emit_wino_v", False) and v_floats * 4 < 2 ** 32 and self._wgrad_takes_wino4(fields)
-            if tile == L.TILE_WINOGRAD4R or takes:
+            if route is F4R or takes:
                 fields["wino_v"] = self.b.buf(v_floats, name="wino_v")
                 fields["_v_for_wgrad"] = bool(takes)
-        if wino == 8:
+        if route.needs_ws:
             # the position-batched form's workspace: V, then the products of its reduction shares
             need = int(L.load().ssde_conv_ws_floats(C.byref(self._query_args(fields, last=False))))
             if need <= 0:
@@ -841,8 +854,7 @@ class Lowering:
         if aux is not None:
             self._materialize_stats(aux.get("_gn"))
         if main is not None:
-            in_pass = tile == L.TILE_WINOGRAD4R and h_in * w_in >= 64
-            self._materialize_stats(main.get("_gn"), fields if in_pass else None)
+            self._materialize_stats(main.get("_gn"), fields if route is F4R and h_in * w_in >= 64 else None)
         if stats and isinstance(dst, Buf):
             slices = self._gn_slices(fields)
             if slices > 0:
@@ -863,8 +875,7 @@ class Lowering:
         4.75 -- so: wherever F(4x4,3x3) runs and the kernel's shape limits allow.  In a training program the pass's output is
         also the F(4x4,3x3) weight gradient's input (v_pre).
         SSDE_WINO4_TWO=0 keeps every F(4x4,3x3) layer on the one fused kernel (the reference of the bit-identity tests)."""
-        return os.environ.get("SSDE_WINO4_TWO", "2") != "0" and 36 * self.n * (h // 4) * (w // 4) * c_in * 4 < 2 ** 32 \
-            and c_in % 8 == 0
+        return os.environ.get("SSDE_WINO4_TWO", "2") != "0" and wino4_v_floats(self.n, h, w, c_in) * 4 < 2 ** 32 and c_in % 8 == 0
 
     def _wgrad_takes_wino4(self, f):
         """Would ssde_conv_wgrad run the weight gradient of this forward conv on the F(4x4,3x3) path?  (shape-only query with
@@ -885,65 +896,57 @@ class Lowering:
         a.flags = L.wgrad_route_flags()
         return bool(L.load().ssde_wgrad_wants_winograd4(C.byref(a)))
 
-    def wino_ok(self, h, w, c_out, c_in, aux=False):
-        """Which 3x3 / stride 1 kernel a layer gets: 0 = direct, 2 = Winograd F(2x2,3x3), 4 = F(4x4,3x3) in one fused kernel
-        (conv_wino4.hip), 6 = F(4x4,3x3) as a transform pass + the register-fed matrix kernel (conv_wino4r.hip; _wino4_two_kernels
-        decides between 4 and 6), 8 = F(4x4,3x3) as position-batched GEMMs on the 4x4 maps (conv_wino4p.hip).  aux: the layer
-        also has a fused 1x1 source.
-        Winograd pays when the matrix pipe is the bound: enough channels to fill the 64-cout tile, and enough workgroups
-        to cover the 256 CUs (F(2x2,3x3): 64 tiles x 64 couts per workgroup -- measured x1.2-1.5 over the direct kernel
-        from 8x8 up at batch 256, x0.5 at 4x4 where only 64 workgroups exist).  F(4x4,3x3) does 1.78x less matrix work
-        again and is 15-23 % faster than F(2x2,3x3) from 16x16 maps up (profiles/r2_wino4_v3_interleaved.txt); its
-        workgroups cover 32 tiles = 512 pixels, so 8x8 maps at batch 256 give 128 of them: there the register-fed matrix kernel
-        splits its reduction over two workgroups per tile (four at batch 128) and wins from 256 input channels up (round 5, see
-        below); with fewer channels, and on 4x4 maps, F(2x2,3x3) / the direct kernel stay.
-        Rounding: ~5x coarser than the direct form, 2.5e-6 .. 1.3e-5 on the whole network against the 1e-4 the parity
-        tests allow (tools/experiments/wino43_error_budget.py).
-        SSDE_WINOGRAD: 0 = direct (bitwise fmaf-chain) kernel everywhere, 1 = this heuristic (default), 2 = F(2x2,3x3)
-        wherever it is legal, 3 = the heuristic without F(4x4,3x3), 4 = F(4x4,3x3) wherever it is legal."""
+    def conv3_route(self, h, w, c_out, c_in, aux=False):
+        """Which kernel a 3x3 / stride 1 layer gets: a row of CONV3_ROUTES.  aux: the layer also has a fused 1x1 source.  Winograd pays when
+        the matrix pipe is the bound: enough channels to fill the 64-cout tile, and enough workgroups to cover the 256 CUs.  Rounding:
+        ~5x coarser than the direct form, 2.5e-6 .. 1.3e-5 on the whole network against the 1e-4 the parity tests allow
+        (tools/experiments/wino43_error_budget.py).  SSDE_WINOGRAD: 0 = direct (bitwise fmaf-chain) kernel everywhere, 1 = this heuristic
+        (default), 2 = F(2x2,3x3) wherever it is legal, 3 = the heuristic without F(4x4,3x3), 4 = F(4x4,3x3) wherever it is legal."""
         mode = os.environ.get("SSDE_WINOGRAD", "1")
         if mode == "0":
-            return 0
-        # 8 = the 4x4 maps, one F(4x4,3x3) tile per image: transform pass + 36 position-batched GEMMs + output pass
+            return DIRECT
+        # F4P -- the 4x4 maps, one F(4x4,3x3) tile per image: transform pass + 36 position-batched GEMMs + output pass
         # (conv_wino4p.hip), whose parallelism comes from the transform positions rather than from the tiles.  Not where the
         # layer also has a fused 1x1 source (aux: the Conv_2 skip of a residual block): the direct kernel runs it as more of the
         # same reduction, the Winograd forms as a second launch, and at batch 256 that 1x1 GEMM alone (0.058 ms for 512 -> 256)
         # costs more than the position-batched form saves (direct 0.079 ms against 0.044 + 0.058, tools/op_times.py)
         if mode == "1" and h == 4 and w == 4 and not aux and c_in % 32 == 0 and c_out % 64 == 0 and self.n >= W4P_MIN_BATCH:
-            return 8
+            return F4P
         legal2 = h % 2 == 0 and w % 2 == 0 and h >= 8 and w >= 8 and c_out >= 32 and c_in >= 8 and c_in % 8 == 0
         legal4 = h % 4 == 0 and w % 4 == 0 and h >= 8 and w >= 8 and c_out >= 32 and c_in >= 8 and c_in % 4 == 0
-        four = lambda: 6 if self._wino4_two_kernels(h, w, c_out, c_in) else 4  # noqa: E731
+        two = lambda: self._wino4_two_kernels(h, w, c_out, c_in)  # noqa: E731  (F4R rather than F4)
         if mode == "4" and legal4:
-            return four()
+            return F4R if two() else F4
         if mode == "2" or mode == "4":
-            return 2 if legal2 else 0
+            return F2 if legal2 else DIRECT
         n_tiles = -(-c_out // 64)
-        # (one workgroup per CU: F(4x4,3x3) workgroups own a whole CU's LDS and registers)
+        # F4 / F4R -- 1.78x less matrix work than F(2x2,3x3) and 15-23 % faster from 16x16 maps up (profiles/
+        # r2_wino4_v3_interleaved.txt).  A workgroup covers 32 tiles = 512 pixels and owns a whole CU's LDS and registers: it wins
+        # from one workgroup per CU (256; tools/heuristic_sweep.py, profiles/r2_heuristic_sweep.txt)
         if mode != "3" and legal4 and h >= 16 and w >= 16 and -(-(self.n * h * w) // 512) * n_tiles >= self.cus:
-            return four()
-        # Fewer tiles than that (8x8 maps at batch 256: 128 tiles of 8 images x 64 couts): the fused kernel's split reduction
-        # (conv_wino4.hip) is 17-40 % faster than its unsplit form but only level with F(2x2,3x3) there
-        # (profiles/r3_wino4_split_reduction_ab.txt), so the lowering does not take it.
-        # The register-fed matrix kernel splits its reduction too (conv_wino4r.hip, ssde_conv_wino4r_splits -- the same rule
-        # here): its channel stage is ~2450 cycles against the fused kernel's ~4600, so where the shares fill exactly one round of
-        # workgroups, transform pass + split matrix kernel beat F(2x2,3x3).  TWO shares -- the 8x8 maps at batch 256: 128 tiles ->
-        # 256 workgroups: 256->256 0.077 against 0.109 ms, 512->256 0.112 against 0.193 (profiles/r5_wino4r_split_8x8.txt); with 128
-        # input channels (16 stages per share) the hand-over costs what the split saves and F(2x2,3x3) stays.
-        # SSDE_CONV_KSPLIT=0 (the library's SSDE_CONVF_NO_KSPLIT) switches every split off.
-        if mode != "3" and legal4 and c_in % 16 == 0 and c_in >= 256 and c_out % 4 == 0 \
-                and os.environ.get("SSDE_CONV_KSPLIT", "1") != "0":
+            return F4R if two() else F4
+        # Fewer workgroups than that (8x8 maps at batch 256: 128 tiles of 8 images x 64 couts).  The fused kernel's split reduction
+        # (conv_wino4.hip) is 17-40 % faster than its unsplit form but only level with F(2x2,3x3) there (profiles/
+        # r3_wino4_split_reduction_ab.txt), so the lowering does not take it.  F4R -- the register-fed matrix kernel splits its
+        # reduction too (conv_wino4r.hip, ssde_conv_wino4r_splits -- the same rule here): its channel stage is ~2450 cycles against
+        # the fused kernel's ~4600, so where the shares fill exactly one round of workgroups, transform pass + split matrix kernel
+        # beat F(2x2,3x3) from 256 input channels up; with 128 (16 stages per share) the hand-over costs what the split saves and
+        # F(2x2,3x3) stays.  SSDE_CONV_KSPLIT=0 (the library's SSDE_CONVF_NO_KSPLIT) switches every split off.
+        if mode != "3" and legal4 and c_in % 16 == 0 and c_in >= 256 and c_out % 4 == 0 and os.environ.get("SSDE_CONV_KSPLIT", "1") != "0":
             wgs4 = -(-(-(-(self.n * h * w) // 512)) // 8) * 8 * n_tiles
-            if self.cus // 2 < wgs4 * 2 <= self.cus and self._wino4_two_kernels(h, w, c_out, c_in):
-                return 6
-            # (four shares filling one round -- the 8x8 maps at batch 128, the training step: 256->256 0.102 -> 0.063 ms, 512->256 0.184 -> 0.082,
-            #  step 0.0548 -> 0.0530 s, profiles/r5_wino4r_split_8x8_batch128.txt, r5_wino4r_split4_train_ab.txt)
-            if c_in % 32 == 0 and self.cus // 2 < wgs4 * 4 <= self.cus and self._wino4_two_kernels(h, w, c_out, c_in):
-                return 6
-        # tools/heuristic_sweep.py (profiles/r2_heuristic_sweep.txt): F(4x4,3x3) wins from one of its workgroups per CU (256),
-        # F(2x2,3x3) over the direct kernel from half a workgroup per CU (128; by 2-6 %; at 64 the direct kernel is 1.5x
-        # faster).  tools/batch_sweep.py: the sampler at batch 16 / 64 / 256 under this rule (profiles/r4_batch_sweep.txt)
-        return 2 if legal2 and -(-(self.n * h * w) // 256) * n_tiles >= self.cus // 2 else 0
+            # two shares -- the 8x8 maps at batch 256, 128 tiles -> 256 workgroups: 256->256 0.077 against 0.109 ms, 512->256 0.112
+            # against 0.193 (profiles/r5_wino4r_split_8x8.txt)
+            if self.cus // 2 < wgs4 * 2 <= self.cus and two():
+                return F4R
+            # four shares -- the 8x8 maps at batch 128, the training step: 256->256 0.102 -> 0.063 ms, 512->256 0.184 -> 0.082,
+            # step 0.0548 -> 0.0530 s (profiles/r5_wino4r_split_8x8_batch128.txt, r5_wino4r_split4_train_ab.txt)
+            if c_in % 32 == 0 and self.cus // 2 < wgs4 * 4 <= self.cus and two():
+                return F4R
+        # F2 -- 64 tiles x 64 couts per workgroup: x1.2-1.5 over the direct kernel from 8x8 up at batch 256, x0.5 at 4x4 where only
+        # 64 workgroups exist; it wins from half a workgroup per CU (128; by 2-6 %; at 64 the direct kernel is 1.5x faster,
+        # profiles/r2_heuristic_sweep.txt).  tools/batch_sweep.py: the sampler at batch 16 / 64 / 256 under this rule
+        # (profiles/r4_batch_sweep.txt)
+        return F2 if legal2 and -(-(self.n * h * w) // 256) * n_tiles >= self.cus // 2 else DIRECT
 
     def upfirdn(self, src, n_ch, h_in, w_in, taps, up=1, down=1, pad=(0, 0), name="fir"):
         kh, kw = taps.shape
@@ -1275,9 +1278,9 @@ class UNetEngine:
                 h, hh, ww = low.upfirdn(_src(h, cur_c), cur_c, hh, ww, fir_taps([1, 1], gain=4.0), up=2, pad=(1, 0), name="up")
                 if up.with_conv:
                     hn = b.buf(n, hh, ww, cur_c, name="up_conv")
-                    wino = low.wino_ok(hh, ww, cur_c, cur_c)
-                    low.conv(hn, hh, ww, cur_c, main=_src(h, cur_c), w_main=self._w3(up.Conv_0, wino=wino), h_in=hh, w_in=ww,
-                             bias=self._bias(up.Conv_0), wino=wino, stats=True)
+                    route = low.conv3_route(hh, ww, cur_c, cur_c)
+                    low.conv(hn, hh, ww, cur_c, main=_src(h, cur_c), w_main=self._w3(up.Conv_0, route=route), h_in=hh, w_in=ww,
+                             bias=self._bias(up.Conv_0), route=route, stats=True)
                     h = hn
         assert not hs
 
@@ -1288,8 +1291,8 @@ class UNetEngine:
         return o, hh, ww
 
     # -- packed parameter helpers
-    def _w3(self, m, cin_pad=None, cout_pad=None, wino=False):
-        return self.weights.conv3(m.weight, cin_pad, cout_pad, wino=wino)
+    def _w3(self, m, cin_pad=None, cout_pad=None, route=DIRECT):
+        return self.weights.conv3(m.weight, cin_pad, cout_pad, route=route)
 
     def _w1(self, m, cin_pad=None):
         return self.weights.matrix([(m.weight, False)], cin_pad=cin_pad)
@@ -1336,11 +1339,11 @@ class UNetEngine:
             main0 = low.src(t, c, hh * ww, t2, c2, pro=L.PRO_GN_SILU, gn=gn0)
             skip_t, skip_c, skip_t2, skip_c2 = t, c, t2, c2
         h1 = b.buf(n, hh, ww, cout, name="res_h1")
-        wino0 = low.wino_ok(hh, ww, cout, main0["c0"] + main0["c1"])
+        route0 = low.conv3_route(hh, ww, cout, main0["c0"] + main0["c1"])
         w_short, b_short = self._shortcut(m)
-        wino1 = low.wino_ok(hh, ww, cout, cout, aux=w_short is not None)
-        low.conv(h1, hh, ww, cout, main=main0, w_main=self._w3(m.Conv_0, wino=wino0), h_in=hh, w_in=ww, bias=self._bias(m.Conv_0),
-                 chan_add=chan_add, chan_add_ld=ld, wino=wino0, stats=True)
+        route1 = low.conv3_route(hh, ww, cout, cout, aux=w_short is not None)
+        low.conv(h1, hh, ww, cout, main=main0, w_main=self._w3(m.Conv_0, route=route0), h_in=hh, w_in=ww, bias=self._bias(m.Conv_0),
+                 chan_add=chan_add, chan_add_ld=ld, route=route0, stats=True)
         gn1 = low.gn_stats(h1, cout, hh * ww, m.GroupNorm_1)
         out = b.buf(n, hh, ww, cout, name="res_out")
         self._n_res += 1
@@ -1348,13 +1351,13 @@ class UNetEngine:
         main1 = low.src(h1, cout, hh * ww, pro=L.PRO_GN_SILU, gn=gn1, drop=drop)
         if w_short is not None:
             bsum = self.weights.vector([m.Conv_1.bias, b_short], mode="sum")
-            low.conv(out, hh, ww, cout, main=main1, w_main=self._w3(m.Conv_1, wino=wino1), h_in=hh, w_in=ww,
-                     aux=low.src(skip_t, skip_c, hh * ww, skip_t2, skip_c2), w_aux=w_short, bias=bsum, scale=scale, wino=wino1,
+            low.conv(out, hh, ww, cout, main=main1, w_main=self._w3(m.Conv_1, route=route1), h_in=hh, w_in=ww,
+                     aux=low.src(skip_t, skip_c, hh * ww, skip_t2, skip_c2), w_aux=w_short, bias=bsum, scale=scale, route=route1,
                      stats=True)
         else:
             assert skip_t2 is None
-            low.conv(out, hh, ww, cout, main=main1, w_main=self._w3(m.Conv_1, wino=wino1), h_in=hh, w_in=ww,
-                     bias=self._bias(m.Conv_1), resid=skip_t, scale=scale, wino=wino1, stats=True)
+            low.conv(out, hh, ww, cout, main=main1, w_main=self._w3(m.Conv_1, route=route1), h_in=hh, w_in=ww,
+                     bias=self._bias(m.Conv_1), resid=skip_t, scale=scale, route=route1, stats=True)
         return out, cout
 
     # -- AttnBlockpp (layerspp.py:75-91) and AttnBlock (layers.py:568-581: the same without the rescale)

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import pack_conv_weight, pack_matrix, pack_wino_weight, pack_wino4_weight, pack_wino4r_weight, pack_wino4p_weight
+from .engine import F4R, conv3_route_of_tile, pack_conv_weight, pack_matrix, wino4_v_floats  # noqa: F401  (pack_conv_weight: callers' use)
 
 
 def _stream():
@@ -108,6 +108,7 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
     _need_cuda(x, aux, resid)
     a = L.ConvArgs()
     keep = []
+    route = conv3_route_of_tile(tile)
     if x is not None:
         n, h_in, w_in = x.shape[0], x.shape[1], x.shape[2]
         c_out = weight.shape[0]
@@ -116,11 +117,9 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
         if out_hw is not None:      # top-left crop of the full result (transposed strided convolutions)
             h_out, w_out = out_hw
         _fill_src(a.main, x, x2, pro, gn)
-        packer = {L.TILE_WINOGRAD: pack_wino_weight, L.TILE_WINOGRAD4: pack_wino4_weight,
-                  L.TILE_WINOGRAD4R: pack_wino4r_weight, L.TILE_WINOGRAD4P: pack_wino4p_weight}.get(tile, pack_conv_weight)
-        wp = packer(weight.to(x.device)); keep.append(wp)
-        if tile == L.TILE_WINOGRAD4R:      # the two-kernel form needs the transformed-input buffer
-            wv = torch.empty(36 * n * (h_in // 4) * (w_in // 4) * (x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)), device=x.device)
+        wp = route.pack(weight.to(x.device)); keep.append(wp)
+        if route is F4R:      # the two-kernel form needs the transformed-input buffer
+            wv = torch.empty(wino4_v_floats(n, h_in, w_in, x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)), device=x.device)
             keep.append(wv)
             a.wino_v = _p(wv)
         a.w_main, a.ksize, a.stride, a.pad, a.h_in, a.w_in = _p(wp), 3, stride, pad, h_in, w_in
@@ -141,7 +140,7 @@ def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_N
         a.chan_add, a.chan_add_ld = _p(chan_add), chan_add.shape[-1]
     a.resid, a.out_scale, a.dst = _p(resid), scale, _p(dst)
     a.flags = L.conv_route_flags() if flags is None else flags
-    if tile == L.TILE_WINOGRAD4P:          # the position-batched form's workspace
+    if route.needs_ws:          # the position-batched form's workspace
         need = int(L.load().ssde_conv_ws_floats(C.byref(a)))
         L.check(min(need, 0), "ssde_conv_ws_floats")
         ws = torch.empty(need, device=dev); keep.append(ws)

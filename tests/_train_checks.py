@@ -857,6 +857,34 @@ def check_device_repack(dev, kind="ncsnpp", need_kind=None):
         assert flags == {0, 1}, flags
 
 
+def check_route_repack(dev):
+    """Every row of engine.CONV3_ROUTES feeds both halves of a weight entry -- the torch packer and the device re-pack kind
+    (ssde_pack_weights), forward image and input-gradient image -- so both must give the same image for every row: after an
+    optimizer step the device re-pack is compared with the row's torch packer on the updated weight.  (96, 40) and (36, 12):
+    ragged 64-cout tiles, ragged channel octets / quads, in both orientations.  The recipe and the 1e-6 are those of
+    test_wino4p_gpu's re-pack test (both sides form the same few-term sums of weights of magnitude ~1 in fp32 or better)."""
+    from score_sde_pytorch_amd import engine as E
+    dev = torch.device(dev)
+    for route in E.CONV3_ROUTES:
+        for cout, cin in ((96, 40), (36, 12)):
+            g = torch.Generator().manual_seed(3)
+            w = torch.nn.Parameter((torch.randn(cout, cin, 3, 3, generator=g) / 70).to(dev))
+            ws = E.WeightStore(dev)
+            fwd = ws.conv3(w, route=route)
+            bwd = ws.derived(fwd, route)
+            ws.refresh()
+            opt = torch.optim.SGD([w], lr=0.5)
+            w.grad = torch.randn(w.shape, generator=g).to(dev)
+            opt.step()
+            fwd.fill_(7.0)
+            bwd.fill_(7.0)
+            ws.refresh(on_device=True)                     # a stale source: the device re-pack
+            e_fwd = float((fwd - route.pack(w.detach())).abs().max())
+            e_bwd = float((bwd - route.pack(w.detach().permute(1, 0, 2, 3).flip(2, 3))).abs().max())
+            print("route %-6s %3d <- %3d: forward image %.3g, input-gradient image %.3g" % (route.name, cout, cin, e_fwd, e_bwd))
+            assert e_fwd < 1e-6 and e_bwd < 1e-6, (route.name, cout, cin, e_fwd, e_bwd)
+
+
 def check_op_package(dev):
     """score_sde_pytorch_amd.op: upfirdn2d / fused_leaky_relu (NCHW, autograd) vs the oracle's upfirdn2d_native
     restatement and F.leaky_relu, forward and gradients."""

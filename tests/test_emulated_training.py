@@ -132,6 +132,10 @@ def test_device_weight_repack_of_the_per_lane_f4x4_image(monkeypatch):
     T.check_device_repack("cpu", "ffhq", need_kind=6)
 
 
+def test_device_weight_repack_of_every_conv3_route():
+    T.check_route_repack("cpu")
+
+
 def test_op_package(monkeypatch):
     import score_sde_pytorch_amd.op as op
     # the package refuses CPU tensors; under the emulator host memory is the device

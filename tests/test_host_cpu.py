@@ -207,6 +207,46 @@ def test_every_f4x4_layer_runs_as_two_kernels(monkeypatch):
     assert not [c for c in convs(engine.UNetEngine(model, 256, 32, 32, torch.device("cpu"))) if c[0] == L.TILE_WINOGRAD4R]
 
 
+def test_conv3_route_decisions_match_the_recorded_grid(monkeypatch):
+    """engine.Lowering.conv3_route over tests/golden/conv3_routes.json (tools/record_conv3_routes.py: the decisions recorded
+    before the routes got their table): every switch combination, batch and layer shape of the grid gets the same kernel."""
+    import itertools
+    import json
+    from score_sde_pytorch_amd import engine
+    with open(os.path.join(_util.ROOT, "tests", "golden", "conv3_routes.json")) as f:
+        rec = json.load(f)
+    ax, tiles = rec["axes"], rec["tiles"]
+    switches = ("SSDE_WINOGRAD", "SSDE_CONV_KSPLIT", "SSDE_WINO4_TWO", "SSDE_NUM_CUS")
+    points = list(itertools.product(ax["hw"], ax["c_out"], ax["c_in"], ax["aux"]))
+    assert len(rec["routes"]) == int(np.prod([len(ax[k]) for k in switches + ("batch",)])) == 200 and len(points) == 288
+    seen, bad = {}, []
+    for combo in itertools.product(*[ax[k] for k in switches]):
+        for k, v in zip(switches, combo):
+            monkeypatch.setenv(k, v)
+        for n in ax["batch"]:
+            key = "/".join(combo + (str(n),))
+            low = engine.Lowering(engine.ProgramBuilder(torch.device("cpu")), None, n)
+            got = [low.conv3_route(hw, hw, c_out, c_in, aux=aux).tile for hw, c_out, c_in, aux in points]
+            want = [tiles[int(d)] for d in rec["routes"][key]]
+            bad += [(key, p, g, w) for p, g, w in zip(points, got, want) if g != w]
+            if combo[0] == "1":
+                for t in got:
+                    seen[t] = seen.get(t, 0) + 1
+    assert not bad, (len(bad), bad[:5])
+    # the grid exercises every route under the heuristic
+    assert sorted(seen) == sorted(r.tile for r in engine.CONV3_ROUTES) and min(seen.values()) >= 50, seen
+
+
+def test_conv3_route_table_names_every_tile():
+    from score_sde_pytorch_amd import engine as E, _lib as L
+    assert [r.name for r in E.CONV3_ROUTES] == ["direct", "f2", "f4", "f4r", "f4p"]
+    assert [r.tile for r in E.CONV3_ROUTES[1:]] == [L.TILE_WINOGRAD, L.TILE_WINOGRAD4, L.TILE_WINOGRAD4R, L.TILE_WINOGRAD4P]
+    assert tuple(r.tile for r in E.CONV3_ROUTES[2:]) == L.TILES_WINOGRAD4
+    assert all(E.conv3_route_of_tile(r.tile) is r for r in E.CONV3_ROUTES)
+    assert all(E.conv3_route_of_tile(t) is E.DIRECT for t in (L.TILE_256x64, L.TILE_128x64, L.TILE_64x64, L.TILE_256x32))
+    assert E.wino4_v_floats(256, 16, 16, 128) == 36 * 256 * 16 * 128
+
+
 def test_weight_packing_layout():
     from score_sde_pytorch_amd.engine import pack_conv_weight, pack_matrix
     w = torch.arange(5 * 3 * 3 * 3, dtype=torch.float32).reshape(5, 3, 3, 3)

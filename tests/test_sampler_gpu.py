@@ -33,7 +33,7 @@ def _setup(n_steps_sde=10, batch=8):
     return cfg, model, sde, sampler
 
 
-# kernel modes of the 3x3 convolutions (engine.Lowering.wino_ok): "2" = Winograd F(2x2,3x3) wherever legal (conftest's
+# kernel modes of the 3x3 convolutions (engine.Lowering.conv3_route): "2" = Winograd F(2x2,3x3) wherever legal (conftest's
 # default), "4" = F(4x4,3x3) wherever legal -- the kernel that carries 60 % of the benchmarked PC iteration and rounds ~5x
 # coarser -- and "0" = the direct (bitwise fmaf-chain) kernel
 WINO_MODES = ["2", "4", "0"]

@@ -121,6 +121,10 @@ def test_device_weight_repack_of_the_per_lane_f4x4_image(monkeypatch):
     T.check_device_repack("cuda", "ffhq", need_kind=6)
 
 
+def test_device_weight_repack_of_every_conv3_route():
+    T.check_route_repack("cuda")
+
+
 def test_op_package():
     T.check_op_package("cuda")
 

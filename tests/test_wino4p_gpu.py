@@ -35,9 +35,9 @@ def test_device_repack_matches_host_pack_after_an_optimizer_step():
     g = torch.Generator().manual_seed(3)
     w = torch.nn.Parameter((torch.randn(256, 512, 3, 3, generator=g) / 70).to(dev))
     ws = E.WeightStore(dev)
-    fwd = ws.conv3(w, wino=8)
+    fwd = ws.conv3(w, route=E.F4P)
     dgrad = lambda t: E.pack_wino4p_weight(t.permute(1, 0, 2, 3).flip(2, 3))  # noqa: E731
-    bwd = ws.derived(fwd, dgrad, "dgrad_wino4p")
+    bwd = ws.derived(fwd, E.F4P)
     ws.refresh()
     opt = torch.optim.SGD([w], lr=0.5)
     w.grad = torch.randn(w.shape, generator=g).to(dev)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The CIFAR-10 PC sampler at batch 16 / 64 / 256 under the production kernel heuristic (engine.Lowering.wino_ok, thresholds
+"""The CIFAR-10 PC sampler at batch 16 / 64 / 256 under the production kernel heuristic (engine.Lowering.conv3_route, thresholds
 derived from the device's CU count): ms per PC iteration, images/s, and which 3x3 kernel the 93 launches of one evaluation
 got -- against the same batch with every 3x3 layer forced to the direct kernel (SSDE_WINOGRAD=0) and to F(2x2,3x3) wherever
 legal (SSDE_WINOGRAD=2).  reference: sampling.py:390-409 takes any `shape`.  GPU only; development tool."""

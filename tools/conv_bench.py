@@ -11,7 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from score_sde_pytorch_amd import hipops as ops, _lib as L  # noqa: E402
-from score_sde_pytorch_amd.engine import pack_conv_weight, pack_wino_weight, pack_wino4_weight, pack_wino4r_weight, pack_wino4p_weight  # noqa: E402
+from score_sde_pytorch_amd.engine import F4R, conv3_route_of_tile, wino4_v_floats  # noqa: E402
 
 
 def time_conv(n, cin, cout, h, tile, gn=False, reps=5, resid=False, flags=0):
@@ -25,8 +25,8 @@ def time_conv(n, cin, cout, h, tile, gn=False, reps=5, resid=False, flags=0):
         mean, rstd = ops.groupnorm_stats(x, G, 1e-6)
         gnt = (mean, rstd, torch.ones(cin, device=dev), torch.zeros(cin, device=dev), G)
     ops._fill_src(a.main, x, None, {0: L.PRO_NONE, 1: L.PRO_GN_SILU, 2: L.PRO_GN, 3: L.PRO_SILU}[int(gn)], gnt)
-    wp = {L.TILE_WINOGRAD: pack_wino_weight, L.TILE_WINOGRAD4: pack_wino4_weight, L.TILE_WINOGRAD4R: pack_wino4r_weight,
-          L.TILE_WINOGRAD4P: pack_wino4p_weight}.get(tile, pack_conv_weight)(w)
+    route = conv3_route_of_tile(tile)
+    wp = route.pack(w)
     dst = torch.empty(n, h, h, cout, device=dev)
     if resid:
         rs = torch.randn(n, h, h, cout, device=dev)
@@ -34,11 +34,11 @@ def time_conv(n, cin, cout, h, tile, gn=False, reps=5, resid=False, flags=0):
     a.w_main, a.ksize, a.stride, a.pad, a.h_in, a.w_in = wp.data_ptr(), 3, 1, 1, h, h
     a.n, a.h_out, a.w_out, a.c_out, a.out_scale, a.dst, a.tile = n, h, h, cout, 1.0, dst.data_ptr(), tile
     a.flags = L.conv_route_flags() | flags
-    if tile == L.TILE_WINOGRAD4R or os.environ.get("CONV_BENCH_EMIT_V"):      # the transformed-input buffer (36 / 16 of the tensor)
-        vbuf = torch.empty(36 * n * (h // 4) * (h // 4) * cin, device=dev)
+    if route is F4R or os.environ.get("CONV_BENCH_EMIT_V"):      # the transformed-input buffer (36 / 16 of the tensor)
+        vbuf = torch.empty(wino4_v_floats(n, h, h, cin), device=dev)
         a.wino_v = vbuf.data_ptr()
     lib = L.load()
-    if tile == L.TILE_WINOGRAD4P:                     # the position-batched form's workspace
+    if route.needs_ws:                                # the position-batched form's workspace
         wsbuf = torch.empty(lib.ssde_conv_ws_floats(C.byref(a)), device=dev)
         a.wino_ws, a.wino_ws_floats = wsbuf.data_ptr(), wsbuf.numel()
     st = ops._stream()

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from score_sde_pytorch_amd import hipops as ops, _lib as L  # noqa: E402
-from score_sde_pytorch_amd.engine import pack_conv_weight, pack_wino_weight, pack_wino4_weight, pack_matrix  # noqa: E402
+from score_sde_pytorch_amd.engine import conv3_route_of_tile, pack_matrix  # noqa: E402
 
 
 def power_reader():
@@ -79,7 +79,7 @@ def conv_launcher(n, cin, cout, h, tile, gn=1):
     mean, rstd = ops.groupnorm_stats(x, G, 1e-6)
     keep = [x, w, mean, rstd, torch.ones(cin, device="cuda"), torch.zeros(cin, device="cuda")]
     ops._fill_src(a.main, x, None, L.PRO_GN_SILU, (mean, rstd, keep[4], keep[5], G))
-    wp = {L.TILE_WINOGRAD: pack_wino_weight, L.TILE_WINOGRAD4: pack_wino4_weight}.get(tile, pack_conv_weight)(w)
+    wp = conv3_route_of_tile(tile).pack(w)
     dst = torch.empty(n, h, h, cout, device="cuda")
     keep += [wp, dst]
     a.w_main, a.ksize, a.stride, a.pad, a.h_in, a.w_in = wp.data_ptr(), 3, 1, 1, h, h

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Which 3x3 kernel wins where (GPU only): direct / F(2x2,3x3) / F(4x4,3x3) at the small-batch shapes of the FFHQ-256 and
-training configurations, to set the thresholds of engine.Lowering.wino_ok."""
+training configurations, to set the thresholds of engine.Lowering.conv3_route."""
 import os
 import sys
 

@@ -17,7 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from score_sde_pytorch_amd import hipops as ops, _lib as L  # noqa: E402
-from score_sde_pytorch_amd.engine import pack_wino4r_weight  # noqa: E402
+from score_sde_pytorch_amd.engine import F4R, wino4_v_floats  # noqa: E402
 
 
 def run(n, cin, cout, h, chunks, reps=6, check=None):
@@ -29,10 +29,10 @@ def run(n, cin, cout, h, chunks, reps=6, check=None):
     G = min(cin // 4, 32)
     mean, rstd = ops.groupnorm_stats(x, G, 1e-6)
     gamma, beta = torch.ones(cin, device=dev), torch.zeros(cin, device=dev)
-    wp = pack_wino4r_weight(w)
+    wp = F4R.pack(w)
     dst = torch.empty(n, h, h, cout, device=dev)
     nc = n // chunks
-    vbuf = torch.empty(36 * nc * (h // 4) * (h // 4) * cin, device=dev)
+    vbuf = torch.empty(wino4_v_floats(nc, h, h, cin), device=dev)
     args = []
     for c in range(chunks):
         a = L.ConvArgs()
@@ -40,7 +40,7 @@ def run(n, cin, cout, h, chunks, reps=6, check=None):
         ops._fill_src(a.main, x[i0:i0 + nc], None, L.PRO_GN_SILU, (mean[i0:i0 + nc], rstd[i0:i0 + nc], gamma, beta, G))
         a.resid = rs[i0:i0 + nc].data_ptr()
         a.w_main, a.ksize, a.stride, a.pad, a.h_in, a.w_in = wp.data_ptr(), 3, 1, 1, h, h
-        a.n, a.h_out, a.w_out, a.c_out, a.out_scale, a.tile = nc, h, h, cout, 1.0, L.TILE_WINOGRAD4R
+        a.n, a.h_out, a.w_out, a.c_out, a.out_scale, a.tile = nc, h, h, cout, 1.0, F4R.tile
         a.dst = dst[i0:i0 + nc].data_ptr()
         a.flags = L.conv_route_flags()
         a.wino_v = vbuf.data_ptr()
@@ -74,6 +74,6 @@ if __name__ == "__main__":
             if ref is None:
                 ref = dst.clone()
             same = bool(torch.equal(ref, dst))
-            vmb = 36 * (n // chunks) * (h // 4) ** 2 * cin * 4 / 1e6
+            vmb = wino4_v_floats(n // chunks, h, h, cin) * 4 / 1e6
             line.append("%d chunk%s (V window %.0f MB) %.4f ms%s" % (chunks, "s" if chunks > 1 else "", vmb, ms, "" if same else " MISMATCH"))
         print("%d->%d@%d n=%d | " % (cin, cout, h, n) + " | ".join(line), flush=True)
