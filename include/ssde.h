@@ -625,7 +625,8 @@ int ssde_gn_finalize(const ssde_gn_finalize_args* a, void* stream);
 int ssde_gn_apply(const ssde_gn_apply_args* a, void* stream);
 int ssde_gn_apply_bwd(const ssde_gn_apply_bwd_args* a, void* stream);
 /* slices per image of the GroupNorm partials this launch would write (plan only, no device access); 0 = this
- * launch cannot produce them (a workgroup tile would span several images, or c_out % 4 != 0) */
+ * launch cannot produce them (a workgroup tile would span several images, or c_out % 4 != 0), or cannot run at all
+ * (ssde_conv_lds_bytes says why) */
 int ssde_conv_gn_slices(const ssde_conv_args* a);
 /* floats of ssde_conv_args.wino_ws this launch needs (plan only, no device access): 0 = its route takes no workspace, < 0 = invalid */
 int64_t ssde_conv_ws_floats(const ssde_conv_args* a);

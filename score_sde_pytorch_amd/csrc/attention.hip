@@ -979,19 +979,6 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_kv_kernel(const float* __
   store_acc(dk, out + C, C3, valid, cp, C, scale);
 }
 
-// Launch of a kernel whose dynamic LDS exceeds the default limit.  The limit is raised at the first launch of each instantiation
-// (one flag each), which the engines make outside any stream capture; idempotent: a lost race only sets the attribute twice.
-template <typename K, typename... Args>
-int launch_lds(K kfn, std::atomic<bool>* done, dim3 grid, dim3 block, int bytes, hipStream_t stream, Args... args) {
-  if (!*done) {
-    SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    *done = true;
-  }
-  hipLaunchKernelGGL(kfn, grid, block, bytes, stream, args...);
-  SSDE_LAUNCH_CHECK();
-  return SSDE_OK;
-}
-
 // what both entry points ask of a launch's sizes
 int check_shape(const char* what, int n, int l, int c) {
   SSDE_REQUIRE(n > 0 && l > 0 && l <= SSDE_ATTN_L_MAX, "%s: token count %d outside 1..%d", what, l, SSDE_ATTN_L_MAX);
@@ -1023,22 +1010,19 @@ extern "C" int ssde_attention(const ssde_attn_args* a, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(ssde_cdiv(a->l, kQB), a->n);
   if (route == SSDE_ATTN_ROUTE_STREAM) {
-    static std::atomic<bool> set[2];
-    if (a->c <= 256) return launch_lds(attn_stream_kernel<1>, &set[0], grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
-    return launch_lds(attn_stream_kernel<2>, &set[1], grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
+    if (a->c <= 256) return ssde_launch_lds<attn_stream_kernel<1>>("attention", grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
+    return ssde_launch_lds<attn_stream_kernel<2>>("attention", grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
   }
   if (route == SSDE_ATTN_ROUTE_X6) {
-    static std::atomic<bool> set[4];
     const dim3 grid_x6(ssde_cdiv(a->n, 8) * 8 * 4);
     switch (a->c) {
-      case 64: return launch_lds(attn_x6_kernel<4>, &set[0], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
-      case 128: return launch_lds(attn_x6_kernel<8>, &set[1], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
-      case 192: return launch_lds(attn_x6_kernel<12>, &set[2], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
-      default: return launch_lds(attn_x6_kernel<16>, &set[3], grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
+      case 64: return ssde_launch_lds<attn_x6_kernel<4>>("attention", grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
+      case 128: return ssde_launch_lds<attn_x6_kernel<8>>("attention", grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
+      case 192: return ssde_launch_lds<attn_x6_kernel<12>>("attention", grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
+      default: return ssde_launch_lds<attn_x6_kernel<16>>("attention", grid_x6, x6::kT, x6::kLds, st, a->qkv, a->dst, a->n, a->scale);
     }
   }
-  static std::atomic<bool> set{false};
-  return launch_lds(attn_kernel, &set, grid, 256, kAttnLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
+  return ssde_launch_lds<attn_kernel>("attention", grid, 256, kAttnLdsFloats * 4, st, a->qkv, a->dst, a->n, a->l, a->c, a->scale);
 }
 
 extern "C" int ssde_attention_bwd(const ssde_attn_bwd_args* a, void* stream) {
@@ -1050,17 +1034,15 @@ extern "C" int ssde_attention_bwd(const ssde_attn_bwd_args* a, void* stream) {
   if (a->l > kLMax) {   // (no flag field: the backward routes by the token count alone)
     SSDE_REQUIRE(a->c <= kStreamCMax, "attention_bwd: the streaming kernels (more than %d tokens) take at most %d channels (got %d)", kLMax,
                  kStreamCMax, a->c);
-    static std::atomic<bool> set_s{false}, set_sq[2], set_skv{false};
-    if (int rc = launch_lds(attn_stream_stats_kernel, &set_s, grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->o, a->d_o, a->stats, a->n, a->l,
+    if (int rc = ssde_launch_lds<attn_stream_stats_kernel>("attention_bwd", grid, 256, kStreamLdsFloats * 4, st, a->qkv, a->o, a->d_o, a->stats, a->n, a->l,
                             a->c, a->scale))
       return rc;
-    if (int rc = a->c <= 256 ? launch_lds(attn_stream_bwd_q_kernel<1>, &set_sq[0], grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale)
-                             : launch_lds(attn_stream_bwd_q_kernel<2>, &set_sq[1], grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale))
+    if (int rc = a->c <= 256 ? ssde_launch_lds<attn_stream_bwd_q_kernel<1>>("attention_bwd", grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale)
+                             : ssde_launch_lds<attn_stream_bwd_q_kernel<2>>("attention_bwd", grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale))
       return rc;
-    return launch_lds(attn_stream_bwd_kv_kernel, &set_skv, dim3(grid.x, grid.y, ssde_cdiv(a->c, 256)), 256, lds, st, a->qkv, a->d_o, a->dqkv,
+    return ssde_launch_lds<attn_stream_bwd_kv_kernel>("attention_bwd", dim3(grid.x, grid.y, ssde_cdiv(a->c, 256)), 256, lds, st, a->qkv, a->d_o, a->dqkv,
                       a->stats, a->n, a->l, a->c, a->scale);
   }
-  static std::atomic<bool> set_q{false}, set_kv{false};
-  if (int rc = launch_lds(attn_bwd_q_kernel, &set_q, grid, 256, lds, st, a->qkv, a->o, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale)) return rc;
-  return launch_lds(attn_bwd_kv_kernel, &set_kv, grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
+  if (int rc = ssde_launch_lds<attn_bwd_q_kernel>("attention_bwd", grid, 256, lds, st, a->qkv, a->o, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale)) return rc;
+  return ssde_launch_lds<attn_bwd_kv_kernel>("attention_bwd", grid, 256, lds, st, a->qkv, a->d_o, a->dqkv, a->stats, a->n, a->l, a->c, a->scale);
 }

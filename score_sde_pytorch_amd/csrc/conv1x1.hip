@@ -837,40 +837,34 @@ __global__ __launch_bounds__(kThreads, 2) void gemm1x1_pipe_kernel(const GemmPar
   if (pd.valid) finish_tile(old);
 }
 
-}  // namespace
-
-// Used by ssde_conv2d for 1x1-only launches it judges large enough (conv_mfma.hip); shapes it does not take stay on the
-// general kernel.
-bool ssde_conv1x1_wants(const ssde_conv_args* a) {
-  if (a->ksize != 0 || a->aux.p0 == nullptr || a->tile != SSDE_TILE_AUTO) return false;
-  const long long M = (long long)a->n * a->h_out * a->w_out;
-  return a->c_out >= 96 && M >= 128 && M < (1ll << 31);
-}
-
-int ssde_conv1x1_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
-  const ssde_src& s = a->aux;
-  SSDE_REQUIRE(s.c0 % 4 == 0 && s.c1 % 4 == 0, "conv1x1: channels must be multiples of 4 (got %d,%d)", s.c0, s.c1);
-  SSDE_REQUIRE(s.c1 == 0 || (s.p1 != nullptr && s.c0 % 32 == 0), "conv1x1: concat boundary must be a multiple of 32");
-  const bool gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
-  if (gn) {
-    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0 && ((s.c0 + s.c1) / s.gn_groups) % 4 == 0,
-                 "conv1x1: GroupNorm needs channels-per-group %% 4 == 0");
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "conv1x1: GroupNorm pointers missing");
-  }
-  SSDE_REQUIRE(a->w_aux && a->dst, "conv1x1: null weights / destination");
+// which kernel runs a launch, and with what: decided without touching a device
+struct GemmPlan {
   GemmParams p;
+  bool gn, x6, pipe;       // GroupNorm prologue; the bf16 split; the persistent, software-pipelined form
+  int xbm, xpf, xbn;       // shape of the split kernel (see there): rows per workgroup, load-ahead depth, output channels per workgroup
+  int grid;
+};
+
+int gemm_plan(const ssde_conv_args* a, GemmPlan* g, ssde_conv_plan* pl) {
+  const ssde_src& s = a->aux;
+  if (int rc = ssde_src_check(s, "conv1x1", "", 32, SSDE_SRC_GN)) return rc;
+  g->gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
+  SSDE_REQUIRE(a->w_aux && a->dst, "conv1x1: null weights / destination");
+  GemmParams& p = g->p;
   p.src = s; p.wpk = a->w_aux;
   p.M = a->n * a->h_out * a->w_out; p.HW = a->h_out * a->w_out; p.K = s.c0 + s.c1;
   p.Cout = a->c_out; p.CoutPad = ssde_cdiv(a->c_out, 64) * 64;
   p.m_tiles = ssde_cdiv(p.M, BM); p.n_tiles = ssde_cdiv(a->c_out, BN);
-  p.bias = a->bias; p.chan_add = a->chan_add; p.chan_add_ld = a->chan_add_ld;
-  p.resid = a->resid; p.resid_post = a->resid_post; p.scale = a->out_scale; p.dst = a->dst;
-  p.gn_part = a->gn_part;
+  ssde_fill_epilogue(p, a);
+  // GroupNorm partials: the kernels store 64-row half tiles of linear pixel rows, 4 waves each: part of one image, or whole images
+  // of at least one epilogue trip (8 rows) each
   const bool gn_ok = a->c_out % 4 == 0 && (p.HW % 64 == 0 || (p.HW >= 8 && p.HW < 64 && 64 % p.HW == 0));
   SSDE_REQUIRE(!a->gn_part || gn_ok, "conv1x1: GroupNorm partials need H*W %% 64 == 0 or a power of two in 8..32");
+  pl->gn_slices = !gn_ok ? 0 : p.HW % 64 == 0 ? (p.HW / 64) * 4 : 4;
+  pl->ws_floats = 0;
   p.lHW = ssde_ilog2(p.HW);
   p.gn_entries = p.HW >= 64 ? a->n * (p.HW / 64) : a->n;
-  const bool x6 = (a->flags & SSDE_CONVF_BF16X6) != 0;
+  const bool x6 = g->x6 = (a->flags & SSDE_CONVF_BF16X6) != 0;
   // the persistent, software-pipelined form: when workgroups get more than one tile each (otherwise there is nothing to overlap
   // and the plain kernels' 3-4 workgroups per CU cover each other better than its 2)
   {
@@ -891,26 +885,14 @@ int ssde_conv1x1_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
     //  kernel through the padded count and 0.088 instead of 0.046 ms; 256 -> 768 @8x8 0.062 against 0.052)
     const bool pays = x6 && p.K >= 512 && (long long)p.m_tiles * p.n_tiles > wgs && !wide_first;
     // (round 5: the fp32 instantiation of the pipelined kernel is no longer built -- it lost everywhere)
-    if (pipe_ok && x6 && (pays || (a->flags & SSDE_CONVF_GEMM_PIPE))) {
-      const int lds = 2 * (x6 ? X6<128>::kStageBytes : kStage * 4) + 4 * kSlabFloats * 4;
-      if (lds_out) { *lds_out = lds; return SSDE_OK; }
-      const dim3 grid(total < wgs ? total : wgs);
-      auto go = [&](auto kfn, std::atomic<bool>& attr_set) {
-        if (!attr_set) {
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-          attr_set = true;
-        }
-        hipLaunchKernelGGL(kfn, grid, dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-        return true;
-      };
-      static std::atomic<bool> pset[2];
-      const bool ok = gn ? go(gemm1x1_pipe_kernel<true, true>, pset[0]) : go(gemm1x1_pipe_kernel<false, true>, pset[1]);
-      SSDE_REQUIRE(ok, "conv1x1: hipFuncSetAttribute failed");
-      SSDE_LAUNCH_CHECK();
+    g->pipe = pipe_ok && x6 && (pays || (a->flags & SSDE_CONVF_GEMM_PIPE));
+    if (g->pipe) {
+      pl->lds_bytes = 2 * X6<128>::kStageBytes + 4 * kSlabFloats * 4;
+      g->grid = total < wgs ? total : wgs;
       return SSDE_OK;
     }
   }
-  // shape of the split kernel (see there): rows per workgroup and load-ahead depth; A/B-selectable per call
+  // shape of the split kernel; A/B-selectable per call
   int xbm = 128, xpf = 1, xbn = BN;
   if (x6) {
     if (a->flags & SSDE_CONVF_X6_BM64) xbm = 64;
@@ -926,29 +908,45 @@ int ssde_conv1x1_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
     p.m_tiles = ssde_cdiv(p.M, xbm);
     p.n_tiles = ssde_cdiv(a->c_out, xbn);
   }
+  g->xbm = xbm; g->xpf = xpf; g->xbn = xbn;
   const int lds_ops = x6 ? 2 * (xbn == 256 ? X6<128, 256>::kStageBytes : xbm == 64 ? X6<64>::kStageBytes : X6<128>::kStageBytes) : 2 * kStage * 4;
   const int lds_epi = 64 * (xbn + 4) * 4;
-  const int lds = lds_ops > lds_epi ? lds_ops : lds_epi;
-  if (lds_out) { *lds_out = lds; return SSDE_OK; }
-  const dim3 grid(ssde_cdiv(p.m_tiles, 8) * 8 * p.n_tiles);
-  auto go = [&](auto kfn, std::atomic<bool>& attr_set) {
-    if (!attr_set) {                            // once per instantiation, before any stream capture
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return false;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, grid, dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-    return true;
-  };
-  static std::atomic<bool> set[12];
-  bool ok;
-  if (!x6) ok = gn ? go(gemm1x1_kernel<true>, set[0]) : go(gemm1x1_kernel<false>, set[1]);
-  else if (xbn == 256) ok = gn ? go(gemm1x1_bf16x6_kernel<true, 128, 1, 256>, set[10]) : go(gemm1x1_bf16x6_kernel<false, 128, 1, 256>, set[11]);
-  else if (xbm == 128 && xpf == 1) ok = gn ? go(gemm1x1_bf16x6_kernel<true, 128, 1>, set[2]) : go(gemm1x1_bf16x6_kernel<false, 128, 1>, set[3]);
-  else if (xbm == 128) ok = gn ? go(gemm1x1_bf16x6_kernel<true, 128, 2>, set[4]) : go(gemm1x1_bf16x6_kernel<false, 128, 2>, set[5]);
-  else if (xpf == 1) ok = gn ? go(gemm1x1_bf16x6_kernel<true, 64, 1>, set[6]) : go(gemm1x1_bf16x6_kernel<false, 64, 1>, set[7]);
-  else ok = gn ? go(gemm1x1_bf16x6_kernel<true, 64, 2>, set[8]) : go(gemm1x1_bf16x6_kernel<false, 64, 2>, set[9]);
-  SSDE_REQUIRE(ok, "conv1x1: hipFuncSetAttribute failed");
-  SSDE_LAUNCH_CHECK();
+  pl->lds_bytes = lds_ops > lds_epi ? lds_ops : lds_epi;
+  g->grid = ssde_cdiv(p.m_tiles, 8) * 8 * p.n_tiles;
   return SSDE_OK;
+}
+
+template <auto Kfn>
+int gemm_go(const GemmPlan& g, int lds, hipStream_t st) {
+  return ssde_launch_lds<Kfn>("conv1x1", dim3(g.grid), dim3(kThreads), lds, st, g.p);
+}
+
+}  // namespace
+
+// Wanted by ssde_conv2d: 1x1-only launches it judges large enough (conv_mfma.hip's table); shapes it does not take stay on the
+// general kernel.
+bool ssde_conv1x1_wants(const ssde_conv_args* a) {
+  if (a->ksize != 0 || a->aux.p0 == nullptr || a->tile != SSDE_TILE_AUTO) return false;
+  const long long M = (long long)a->n * a->h_out * a->w_out;
+  return a->c_out >= 96 && M >= 128 && M < (1ll << 31);
+}
+
+int ssde_conv1x1_plan(const ssde_conv_args* a, ssde_conv_plan* pl) {
+  GemmPlan g;
+  return gemm_plan(a, &g, pl);
+}
+
+int ssde_conv1x1_launch(const ssde_conv_args* a, hipStream_t st) {
+  GemmPlan g;
+  ssde_conv_plan pl;
+  if (int rc = gemm_plan(a, &g, &pl)) return rc;
+  const int lds = pl.lds_bytes;
+  const bool gn = g.gn;
+  if (g.pipe) return gn ? gemm_go<gemm1x1_pipe_kernel<true, true>>(g, lds, st) : gemm_go<gemm1x1_pipe_kernel<false, true>>(g, lds, st);
+  if (!g.x6) return gn ? gemm_go<gemm1x1_kernel<true>>(g, lds, st) : gemm_go<gemm1x1_kernel<false>>(g, lds, st);
+  if (g.xbn == 256) return gn ? gemm_go<gemm1x1_bf16x6_kernel<true, 128, 1, 256>>(g, lds, st) : gemm_go<gemm1x1_bf16x6_kernel<false, 128, 1, 256>>(g, lds, st);
+  if (g.xbm == 128 && g.xpf == 1) return gn ? gemm_go<gemm1x1_bf16x6_kernel<true, 128, 1>>(g, lds, st) : gemm_go<gemm1x1_bf16x6_kernel<false, 128, 1>>(g, lds, st);
+  if (g.xbm == 128) return gn ? gemm_go<gemm1x1_bf16x6_kernel<true, 128, 2>>(g, lds, st) : gemm_go<gemm1x1_bf16x6_kernel<false, 128, 2>>(g, lds, st);
+  if (g.xpf == 1) return gn ? gemm_go<gemm1x1_bf16x6_kernel<true, 64, 1>>(g, lds, st) : gemm_go<gemm1x1_bf16x6_kernel<false, 64, 1>>(g, lds, st);
+  return gn ? gemm_go<gemm1x1_bf16x6_kernel<true, 64, 2>>(g, lds, st) : gemm_go<gemm1x1_bf16x6_kernel<false, 64, 2>>(g, lds, st);
 }

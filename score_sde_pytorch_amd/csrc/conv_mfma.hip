@@ -390,27 +390,12 @@ struct ConvPlan {
   int gn_slices;           // slices per image of the GroupNorm partials (0: a tile spans several images)
 };
 
-int src_check(const ssde_src& s, const char* what) {
-  SSDE_REQUIRE(s.p0 != nullptr && s.c0 > 0, "conv: %s source missing", what);
-  SSDE_REQUIRE(s.c0 % 4 == 0 && s.c1 % 4 == 0, "conv: %s channels must be multiples of 4 (got %d,%d)", what, s.c0, s.c1);
-  SSDE_REQUIRE(s.c1 == 0 || s.p1 != nullptr, "conv: %s second tensor missing", what);
-  SSDE_REQUIRE(s.c1 == 0 || s.c0 % 32 == 0, "conv: %s concat boundary must be a multiple of 32", what);
-  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) {
-    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0 && ((s.c0 + s.c1) / s.gn_groups) % 4 == 0,
-                 "conv: %s GroupNorm needs channels-per-group %% 4 == 0", what);
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "conv: %s GroupNorm pointers missing", what);
-  }
-  return SSDE_OK;
-}
-
-int pow2_floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
-
 // tile geometry: TW x TH output pixels (powers of two; the output itself may be any size, edge tiles are
 // bounds-checked) of IMGS images
 int halo_px(int bm, int w_out, int h_out, int stride, int ks, int* lTW, int* lTH) {
-  int tw = pow2_floor(w_out < 16 ? w_out : 16);
+  int tw = ssde_pow2_floor(w_out < 16 ? w_out : 16);
   int th = bm / tw; if (th > h_out) th = h_out;
-  th = pow2_floor(th);
+  th = ssde_pow2_floor(th);
   *lTW = ssde_ilog2(tw); *lTH = ssde_ilog2(th);
   const int imgs = bm / (tw * th);
   return imgs * ((th - 1) * stride + ks) * ((tw - 1) * stride + ks);
@@ -424,7 +409,7 @@ int make_plan(const ssde_conv_args* a, ConvPlan* pl) {
   SSDE_REQUIRE(a->ksize == 0 || a->ksize == 3, "conv: ksize must be 0 or 3 (1x1 goes through aux)");
   SSDE_REQUIRE(a->n > 0 && a->h_out > 0 && a->w_out > 0 && a->c_out > 0, "conv: bad output shape");
   if (pl->has3) {
-    if (int rc = src_check(a->main, "main")) return rc;
+    if (int rc = ssde_src_check(a->main, "conv", "main ", 32, SSDE_SRC_NEEDS_C0 | SSDE_SRC_GN)) return rc;
     SSDE_REQUIRE(a->w_main, "conv: w_main missing");
     SSDE_REQUIRE(a->stride == 1 || a->stride == 2, "conv: stride must be 1 or 2");
     SSDE_REQUIRE(a->pad_end == 0 || a->pad_end == 1, "conv: pad_end must be 0 or 1 (got %d)", a->pad_end);
@@ -438,7 +423,7 @@ int make_plan(const ssde_conv_args* a, ConvPlan* pl) {
                  a->stride, a->pad, a->pad_end);
   }
   if (pl->has1) {
-    if (int rc = src_check(a->aux, "aux")) return rc;
+    if (int rc = ssde_src_check(a->aux, "conv", "aux ", 32, SSDE_SRC_NEEDS_C0 | SSDE_SRC_GN)) return rc;
     SSDE_REQUIRE(a->w_aux, "conv: w_aux missing");
   }
   const int M = a->n * a->h_out * a->w_out;
@@ -454,8 +439,6 @@ int make_plan(const ssde_conv_args* a, ConvPlan* pl) {
     if (a->w_out * a->h_out * a->n < kTiles[tile].bm && tile != SSDE_TILE_256x32) tile = SSDE_TILE_64x64;
   }
   SSDE_REQUIRE(tile >= 1 && tile <= 4, "conv: bad tile id %d", tile);
-  (void)SSDE_TILE_WINOGRAD4;
-  (void)SSDE_TILE_WINOGRAD;
   int lTW = 0, lTH = 0;
   pl->bkc = 8;
   const bool deep_ok = !(a->flags & SSDE_CONVF_BKC8);     // (the flag: 8-channel stages everywhere -- A/B runs, tests)
@@ -485,9 +468,7 @@ int make_plan(const ssde_conv_args* a, ConvPlan* pl) {
   g.tiles_per_img = g.tiles_x * ssde_cdiv(a->h_out, th);
   g.m_tiles = ssde_cdiv(a->n, imgs) * g.tiles_per_img;
   g.n_tiles = ssde_cdiv(a->c_out, bn);
-  kp.bias = a->bias; kp.chan_add = a->chan_add; kp.chan_add_ld = a->chan_add_ld;
-  kp.resid = a->resid; kp.resid_post = a->resid_post; kp.scale = a->out_scale; kp.dst = a->dst;
-  kp.gn_part = a->gn_part;
+  ssde_fill_epilogue(kp, a);
   // part of one image per tile, or whole images of at least one epilogue trip (kThreads / (bn / 4) rows) each
   const bool gn_ok = a->c_out % 4 == 0 && (imgs == 1 || (g.tiles_per_img == 1 && tw * th >= kThreads / (bn / 4)));
   pl->gn_slices = gn_ok ? g.tiles_per_img * (kThreads / 64) : 0;
@@ -524,23 +505,57 @@ int launch_cfg(ConvPlan& pl, hipStream_t st) {
     pl.kp.sync = ssde_conv_sync_slots(pl.kp.g.m_tiles * pl.kp.g.n_tiles);
     SSDE_REQUIRE(pl.kp.sync, "conv: no hand-over slots for a split reduction");
   }
-#define SSDE_CONV_LAUNCH(H3, H1)                                                                     \
-  do {                                                                                               \
-    auto kfn = conv_mfma_kernel<WM, WN, TM, TN, H3, H1, BKC3>;                                       \
-    static std::atomic<bool> attr_set{false}; /* once per instantiation, before any stream capture */            \
-    if (!attr_set) {                                                                                 \
-      SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                         \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));   \
-      attr_set = true;                                                                               \
-    }                                                                                                \
-    hipLaunchKernelGGL(kfn, grid, block, pl.lds_bytes, st, pl.kp);                                   \
-  } while (0)
-  if (pl.has3 && pl.has1) SSDE_CONV_LAUNCH(true, true);
-  else if (pl.has3) SSDE_CONV_LAUNCH(true, false);
-  else SSDE_CONV_LAUNCH(false, true);
-#undef SSDE_CONV_LAUNCH
-  SSDE_LAUNCH_CHECK();
+  if (pl.has3 && pl.has1) return ssde_launch_lds<conv_mfma_kernel<WM, WN, TM, TN, true, true, BKC3>>("conv", grid, block, pl.lds_bytes, st, pl.kp);
+  if (pl.has3) return ssde_launch_lds<conv_mfma_kernel<WM, WN, TM, TN, true, false, BKC3>>("conv", grid, block, pl.lds_bytes, st, pl.kp);
+  return ssde_launch_lds<conv_mfma_kernel<WM, WN, TM, TN, false, true, BKC3>>("conv", grid, block, pl.lds_bytes, st, pl.kp);
+}
+
+// the direct kernel's row of the route table
+int direct_plan(const ssde_conv_args* a, ssde_conv_plan* out) {
+  ConvPlan pl;
+  if (int rc = make_plan(a, &pl)) return rc;
+  *out = ssde_conv_plan{pl.lds_bytes, pl.gn_slices, 0};
   return SSDE_OK;
+}
+
+int direct_launch(const ssde_conv_args* a, hipStream_t st) {
+  ConvPlan pl;
+  if (int rc = make_plan(a, &pl)) return rc;
+  switch (pl.tile) {
+    case SSDE_TILE_256x64: return launch_cfg<4, 1, 2, 2>(pl, st);
+    case SSDE_TILE_128x64: return launch_cfg<4, 1, 1, 2>(pl, st);
+    case SSDE_TILE_64x64:  return pl.bkc == 8 ? launch_cfg<2, 2, 1, 1>(pl, st) : launch_cfg<2, 2, 1, 1, SSDE_CONV_BKC64>(pl, st);
+    case SSDE_TILE_256x32: return launch_cfg<4, 1, 2, 1>(pl, st);
+  }
+  ssde_set_error("conv: unreachable tile %d", pl.tile);
+  return SSDE_EINVAL;
+}
+
+// The routes of ssde_conv2d, asked in this order.  The Winograd kernels are chosen by the caller (tile); they tile the output of a
+// 3x3 / stride 1 / pad 1 convolution and know no end padding.  A 1x1-only launch that is large enough goes to the GEMM kernel, an
+// image head (at most 4 output channels) to its own kernel, everything else to the direct kernel of this file.
+template <int TILE> bool wants_tile(const ssde_conv_args* a) { return a->tile == TILE; }
+const ssde_conv_route kRoutes[] = {
+    {"f2", wants_tile<SSDE_TILE_WINOGRAD>, ssde_conv_wino_plan, ssde_conv_wino_launch, false},
+    {"f4", wants_tile<SSDE_TILE_WINOGRAD4>, ssde_conv_wino4_plan, ssde_conv_wino4_launch, false},
+    {"f4r", wants_tile<SSDE_TILE_WINOGRAD4R>, ssde_conv_wino4r_plan, ssde_conv_wino4r_launch, false},
+    {"f4p", wants_tile<SSDE_TILE_WINOGRAD4P>, ssde_conv_wino4p_plan, ssde_conv_wino4p_launch, false},
+    {"1x1", [](const ssde_conv_args* a) { return a->dst && ssde_conv1x1_wants(a); }, ssde_conv1x1_plan, ssde_conv1x1_launch, true},
+    {"small", [](const ssde_conv_args* a) { return a->dst && ssde_conv_small_wants(a); }, ssde_conv_small_plan, ssde_conv_small_launch, true},
+    {"direct", [](const ssde_conv_args*) { return true; }, direct_plan, direct_launch, true},
+};
+
+// The route of a launch.  nullptr (error set): end padding on a route that knows none -- refused here, before any of the route's
+// own checks.  Null arguments go to the direct kernel's row, which reports them.
+const ssde_conv_route* route_of(const ssde_conv_args* a) {
+  const ssde_conv_route* r = kRoutes + sizeof(kRoutes) / sizeof(kRoutes[0]) - 1;
+  if (!a) return r;
+  for (r = kRoutes; !r->wants(a); ++r) {}        // (the last row wants everything)
+  if (a->pad_end != 0 && !r->takes_pad_end) {
+    ssde_set_error("conv: pad_end %d with Winograd tile %d (end padding runs on the direct kernel only)", a->pad_end, a->tile);
+    return nullptr;
+  }
+  return r;
 }
 
 }  // namespace
@@ -564,28 +579,10 @@ unsigned* ssde_conv_sync_slots(int need) {
   return base + 2 * (size_t)at;
 }
 
-// the Winograd kernels have their own launchers: launch (lds_out == NULL), LDS query, or GroupNorm-slice query (stream == 1)
-typedef int (*ssde_wino_launcher)(const ssde_conv_args*, void*, int*);
-static ssde_wino_launcher wino_launcher(int tile) {
-  switch (tile) {
-    case SSDE_TILE_WINOGRAD: return ssde_conv_wino_launch;
-    case SSDE_TILE_WINOGRAD4: return ssde_conv_wino4_launch;
-    case SSDE_TILE_WINOGRAD4R: return ssde_conv_wino4r_launch;
-    case SSDE_TILE_WINOGRAD4P: return ssde_conv_wino4p_launch;
-    default: return nullptr;
-  }
-}
-
-// The Winograd kernels tile the output of a 3x3 / stride 1 / pad 1 convolution and know no end padding: a launch that names
-// one of their tiles with pad_end != 0 is refused here, before any of their launchers or plan queries sees it.
-static int wino_pad_end_ok(const ssde_conv_args* a) {
-  SSDE_REQUIRE(!a || a->pad_end == 0 || wino_launcher(a->tile) == nullptr,
-               "conv: pad_end %d with Winograd tile %d (end padding runs on the direct kernel only)", a->pad_end, a->tile);
-  return SSDE_OK;
-}
-
 extern "C" int ssde_conv2d(const ssde_conv_args* a, void* stream) {
-  if (int rc = wino_pad_end_ok(a)) return rc;
+  const ssde_conv_route* r = route_of(a);
+  if (!r) return SSDE_EINVAL;
+  // what belongs to the call rather than to its route
   if (a && a->gn_in_part0 && !ssde_wino4_xform_merges_gn(a)) {
     // the statistics of main are still partials and this route has no kernel that merges them for itself: the finalize launch
     // of ABI 3-9, issued here in front of the kernel
@@ -598,81 +595,39 @@ extern "C" int ssde_conv2d(const ssde_conv_args* a, void* stream) {
     f.mean = const_cast<float*>(s.gn_mean); f.rstd = const_cast<float*>(s.gn_rstd);
     if (int rc = ssde_gn_finalize(&f, stream)) return rc;
   }
-  if (a) {
-    if (ssde_wino_launcher fn = wino_launcher(a->tile)) {
-      // the two-kernel forms: the input-transform pass into wino_v first, unless the caller says wino_v already holds it
-      if (a->tile == SSDE_TILE_WINOGRAD4R && !(a->flags & SSDE_CONVF_V_GIVEN)) {
-        // (the matrix kernel's launcher validates the arguments -- aux source, kernel size / stride / pad, map and channel limits,
-        //  V < 4 GB --: ask it in its plan-only form first, so that an invalid call enqueues nothing)
-        int lds = 0;
-        if (int rc = fn(a, nullptr, &lds)) return rc;
-        if (int rc = ssde_wino4_xform_vq_launch(a, stream)) return rc;
-      }
-      return fn(a, stream, nullptr);
-    }
+  if (a && a->tile == SSDE_TILE_WINOGRAD4R && !(a->flags & SSDE_CONVF_V_GIVEN)) {
+    // the two-kernel form: the input-transform pass into wino_v first, unless the caller says wino_v already holds it.  The matrix
+    // kernel's route validates the arguments -- aux source, kernel size / stride / pad, map and channel limits --: its plan first,
+    // so that an invalid call enqueues nothing
+    ssde_conv_plan pl;
+    if (int rc = r->plan(a, &pl)) return rc;
+    if (int rc = ssde_wino4_xform_vq_launch(a, stream)) return rc;
   }
-  if (a && a->dst && ssde_conv1x1_wants(a)) return ssde_conv1x1_launch(a, stream, nullptr);   // 1x1-only: GEMM kernel (conv1x1.hip)
-  if (a && a->dst && ssde_conv_small_wants(a)) return ssde_conv_small_launch(a, stream, nullptr);   // image heads (conv_small.hip)
-  ConvPlan pl;
-  if (int rc = make_plan(a, &pl)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (pl.tile) {
-    case SSDE_TILE_256x64: return launch_cfg<4, 1, 2, 2>(pl, st);
-    case SSDE_TILE_128x64: return launch_cfg<4, 1, 1, 2>(pl, st);
-    case SSDE_TILE_64x64:  return pl.bkc == 8 ? launch_cfg<2, 2, 1, 1>(pl, st) : launch_cfg<2, 2, 1, 1, SSDE_CONV_BKC64>(pl, st);
-    case SSDE_TILE_256x32: return launch_cfg<4, 1, 2, 1>(pl, st);
-  }
-  ssde_set_error("conv: unreachable tile %d", pl.tile);
-  return SSDE_EINVAL;
+  return r->launch(a, static_cast<hipStream_t>(stream));
 }
 
+// The plan queries: the route's plan, without a device.
 extern "C" int ssde_conv_gn_slices(const ssde_conv_args* a) {
   if (!a || a->c_out % 4 != 0) return 0;
-  if (wino_pad_end_ok(a)) return 0;
   ssde_conv_args q = *a;
-  q.gn_part = nullptr;
-  if (ssde_wino_launcher fn = wino_launcher(q.tile)) {
-    int s = 0;
-    if (fn(&q, reinterpret_cast<void*>(1), &s)) return 0;     // plan-only query form
-    return s;
-  }
-  if (q.dst && ssde_conv1x1_wants(&q)) {
-    // the GEMM kernel stores 64-row half tiles of linear pixel rows, 4 waves each: part of one image, or whole images
-    // of at least one epilogue trip (8 rows) each
-    const int hw = q.h_out * q.w_out;
-    if (hw % 64 == 0) return (hw / 64) * 4;
-    return (hw >= 8 && hw < 64 && 64 % hw == 0) ? 4 : 0;
-  }
-  if (q.dst && ssde_conv_small_wants(&q)) return 0;             // (the image heads are not normalised by anybody)
-  ConvPlan pl;
-  if (make_plan(&q, &pl)) return 0;
-  return pl.gn_slices;
+  q.gn_part = nullptr;                           // "could this launch write partials?", not "does its gn_part fit?"
+  const ssde_conv_route* r = route_of(&q);
+  ssde_conv_plan pl;
+  return r && r->plan(&q, &pl) == SSDE_OK ? pl.gn_slices : 0;
 }
 
 extern "C" int64_t ssde_conv_ws_floats(const ssde_conv_args* a) {
-  if (int rc = wino_pad_end_ok(a)) return rc;
-  if (a && a->tile == SSDE_TILE_WINOGRAD4P) return ssde_conv_wino4p_ws_floats(a);
-  return 0;
+  const ssde_conv_route* r = route_of(a);
+  if (!r) return SSDE_EINVAL;
+  // (only the route with a workspace refuses here: for the others the answer is 0 whatever ssde_conv_lds_bytes says of the launch)
+  ssde_conv_plan pl = {0, 0, 0};
+  const int rc = r->plan(a, &pl);
+  return rc && a && a->tile == SSDE_TILE_WINOGRAD4P ? rc : pl.ws_floats;
 }
 
 extern "C" int ssde_conv_lds_bytes(const ssde_conv_args* a) {
-  if (int rc = wino_pad_end_ok(a)) return rc;
-  if (ssde_wino_launcher fn = a ? wino_launcher(a->tile) : nullptr) {
-    int lds = 0;
-    if (int rc = fn(a, nullptr, &lds)) return rc;
-    return lds;
-  }
-  if (a && a->dst && ssde_conv1x1_wants(a)) {
-    int lds = 0;
-    if (int rc = ssde_conv1x1_launch(a, nullptr, &lds)) return rc;
-    return lds;
-  }
-  if (a && a->dst && ssde_conv_small_wants(a)) {
-    int lds = 0;
-    if (int rc = ssde_conv_small_launch(a, nullptr, &lds)) return rc;
-    return lds;
-  }
-  ConvPlan pl;
-  if (int rc = make_plan(a, &pl)) return rc;
+  const ssde_conv_route* r = route_of(a);
+  ssde_conv_plan pl;
+  if (int rc = r ? r->plan(a, &pl) : SSDE_EINVAL) return rc;
   return pl.lds_bytes;
 }

@@ -209,18 +209,19 @@ bool ssde_conv_small_wants(const ssde_conv_args* a) {
          a->h_in == a->h_out && a->w_in == a->w_out && ctot >= 8 && ctot % 8 == 0 && a->main.c0 % 4 == 0 && a->gn_part == nullptr;
 }
 
-int ssde_conv_small_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
+int ssde_conv_small_plan(const ssde_conv_args* a, ssde_conv_plan* pl) {
   SSDE_REQUIRE(ssde_conv_small_wants(a) && a->dst && a->w_main, "conv(small cout): not a launch for this kernel");
-  if (lds_out) { *lds_out = kLdsBytes; return SSDE_OK; }
+  pl->lds_bytes = kLdsBytes;
+  pl->gn_slices = 0;                             // (the image heads are not normalised by anybody)
+  pl->ws_floats = 0;
+  return SSDE_OK;
+}
+
+int ssde_conv_small_launch(const ssde_conv_args* a, hipStream_t st) {
+  ssde_conv_plan pl;
+  if (int rc = ssde_conv_small_plan(a, &pl)) return rc;
   const ssde_src& s = a->main;
-  SSDE_REQUIRE(s.c1 == 0 || s.p1, "conv(small cout): second source missing");
-  const bool gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
-  if (gn) {
-    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0 && ((s.c0 + s.c1) / s.gn_groups) % 4 == 0,
-                 "conv(small cout): GroupNorm needs channels-per-group %% 4 == 0");
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "conv(small cout): GroupNorm pointers missing");
-  }
-  SSDE_REQUIRE(s.drop_thresh == 0 || s.drop_seed, "conv(small cout): dropout seed pointer missing");
+  if (int rc = ssde_src_check(s, "conv(small cout)", "", 4, SSDE_SRC_GN | SSDE_SRC_SEED)) return rc;
   SSDE_REQUIRE((unsigned long long)a->n * a->h_in * a->w_in * (unsigned)(s.c0 + s.c1) < (1ull << 32), "conv(small cout): tensor too large");
   SmallParams p;
   p.src = s; p.wpk = a->w_main;
@@ -230,13 +231,5 @@ int ssde_conv_small_launch(const ssde_conv_args* a, void* stream, int* lds_out) 
   p.resid = a->resid; p.resid_post = a->resid_post; p.scale = a->out_scale; p.dst = a->dst;
   const long long wgs = (long long)a->n * p.tiles_x * p.tiles_y;
   SSDE_REQUIRE(wgs > 0 && wgs < (1ll << 31), "conv(small cout): bad grid");
-  static std::atomic<bool> attr_set;
-  if (!attr_set) {                              // once, before any stream capture
-    SSDE_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_small_cout_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024) == hipSuccess, "conv(small cout): hipFuncSetAttribute failed");
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(conv_small_cout_kernel, dim3((unsigned)wgs), dim3(kThreads), kLdsBytes, static_cast<hipStream_t>(stream), p);
-  SSDE_LAUNCH_CHECK();
-  return SSDE_OK;
+  return ssde_launch_lds<conv_small_cout_kernel>("conv(small cout)", dim3((unsigned)wgs), dim3(kThreads), pl.lds_bytes, st, p);
 }

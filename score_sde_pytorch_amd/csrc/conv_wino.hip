@@ -479,62 +479,46 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
   SSDE_TR(46);
 }
 
-int pow2_floor(int v) { int q = 1; while (q * 2 <= v) q *= 2; return q; }
-
-}  // namespace
-
-// Launched by ssde_conv2d when a->tile == SSDE_TILE_WINOGRAD (the caller packs w_main for this kernel).
-int ssde_conv_wino_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
+// Everything a launch needs, without touching a device: the parameter block, and the plan the queries report.
+int wino_plan(const ssde_conv_args* a, WinoParams* pp, ssde_conv_plan* pl) {
   SSDE_REQUIRE(a && a->dst && a->main.p0 && a->w_main, "conv(winograd): null args");
   SSDE_REQUIRE(a->ksize == 3 && a->stride == 1 && a->pad == 1, "conv(winograd): needs 3x3, stride 1, pad 1");
   SSDE_REQUIRE(a->aux.p0 == nullptr, "conv(winograd): fused 1x1 source not supported (issue it as a second conv)");
   SSDE_REQUIRE(a->h_in == a->h_out && a->w_in == a->w_out && a->h_out % 2 == 0 && a->w_out % 2 == 0 && a->h_out >= 8 && a->w_out >= 8,
                "conv(winograd): even same-size output of at least 8x8 needed (got %dx%d)", a->h_out, a->w_out);
   const ssde_src& s = a->main;
-  SSDE_REQUIRE(s.c0 > 0 && s.c0 % 4 == 0 && s.c1 % 4 == 0 && (s.c1 == 0 || (s.p1 && s.c0 % 8 == 0)),
-               "conv(winograd): channels must be multiples of 4 (concat boundary of 8)");
-  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) {
-    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0 && ((s.c0 + s.c1) / s.gn_groups) % 4 == 0,
-                 "conv(winograd): GroupNorm needs channels-per-group %% 4 == 0");
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "conv(winograd): GroupNorm pointers missing");
-  }
-  SSDE_REQUIRE(s.drop_thresh == 0 || s.drop_seed, "conv(winograd): dropout seed pointer missing");
-  WinoParams p;
+  if (int rc = ssde_src_check(s, "conv(winograd)", "", 8, SSDE_SRC_ALL)) return rc;
+  WinoParams& p = *pp;
   p.src = s; p.wpk = a->w_main;
   p.N = a->n; p.H = a->h_out; p.W = a->w_out; p.Cout = a->c_out;
-  const int twt = pow2_floor((a->w_out / 2) < 8 ? (a->w_out / 2) : 8);
-  int tht = 64 / twt; if (tht > a->h_out / 2) tht = a->h_out / 2;
-  tht = pow2_floor(tht);
-  const int imgs = 64 / (twt * tht);
-  p.lTWt = ssde_ilog2(twt); p.lTHt = ssde_ilog2(tht);
-  p.tiles_x = ssde_cdiv(a->w_out, 2 * twt);
-  p.tiles_per_img = p.tiles_x * ssde_cdiv(a->h_out, 2 * tht);
-  p.m_tiles = ssde_cdiv(a->n, imgs) * p.tiles_per_img;
-  p.n_tiles = ssde_cdiv(a->c_out, 64);
-  p.bias = a->bias; p.chan_add = a->chan_add; p.chan_add_ld = a->chan_add_ld;
-  p.resid = a->resid; p.resid_post = a->resid_post; p.scale = a->out_scale; p.dst = a->dst;
-  p.gn_part = a->gn_part;
-  // GroupNorm partials: a tile is part of one image (tiles_per_img slices) or holds `imgs` whole images (1 slice each,
-  // tiles_per_img == 1); 256 / imgs rows per image >= the 32 rows of one epilogue trip
-  const bool gn_ok = a->c_out % 4 == 0 && (imgs == 1 || (p.tiles_per_img == 1 && imgs <= 8));
-  SSDE_REQUIRE(!a->gn_part || gn_ok, "conv(winograd): GroupNorm partials not available for this tiling");
-  if (lds_out && stream == reinterpret_cast<void*>(1)) { *lds_out = gn_ok ? p.tiles_per_img * (kThreads / 64) : 0; return SSDE_OK; }
-  const int halo_px = imgs * (2 * tht + 2) * (2 * twt + 2);
+  const ssde_wino_tiling t = ssde_wino_tiling_fill(p, a, 2, 64);
+  ssde_fill_epilogue(p, a);
+  SSDE_REQUIRE(!a->gn_part || t.gn_ok, "conv(winograd): GroupNorm partials not available for this tiling");
+  pl->gn_slices = t.gn_ok ? p.tiles_per_img * (kThreads / 64) : 0;      // part of one image: a slice per tile and wave
+  const int halo_px = t.imgs * (2 * t.tht + 2) * (2 * t.twt + 2);
   SSDE_REQUIRE(halo_px * 2 <= kMaxRaw * kStagers, "conv(winograd): halo of %d pixels exceeds the staging plan", halo_px);
-  int lds = (4 * kStageFloats + 4 * halo_px * 2) * 4;
-  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) lds += (2 * imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
-  SSDE_REQUIRE(lds <= 160 * 1024, "conv(winograd): %d bytes of LDS", lds);
-  if (lds_out) { *lds_out = lds; return SSDE_OK; }
-  static std::atomic<bool> attr_set{false};   // once, before any stream capture
-  if (!attr_set) {
-    SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  pl->lds_bytes = (4 * kStageFloats + 4 * halo_px * 2) * 4;
+  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) pl->lds_bytes += (2 * t.imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
+  SSDE_REQUIRE(pl->lds_bytes <= 160 * 1024, "conv(winograd): %d bytes of LDS", pl->lds_bytes);
+  pl->ws_floats = 0;
+  return SSDE_OK;
+}
+
+}  // namespace
+
+// The route of a->tile == SSDE_TILE_WINOGRAD (the caller packs w_main for this kernel).
+int ssde_conv_wino_plan(const ssde_conv_args* a, ssde_conv_plan* pl) {
+  WinoParams p;
+  return wino_plan(a, &p, pl);
+}
+
+int ssde_conv_wino_launch(const ssde_conv_args* a, hipStream_t st) {
+  WinoParams p;
+  ssde_conv_plan pl;
+  if (int rc = wino_plan(a, &p, &pl)) return rc;
+  using Both = ssde_lds_kernels<conv_wino_kernel<false>, conv_wino_kernel<true>>;
   const bool gn = a->main.pro_mode == SSDE_PRO_GN || a->main.pro_mode == SSDE_PRO_GN_SILU;
   const dim3 grid(ssde_cdiv(p.m_tiles, 8) * 8 * p.n_tiles);
-  if (gn) hipLaunchKernelGGL(conv_wino_kernel<true>, grid, dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  else hipLaunchKernelGGL(conv_wino_kernel<false>, grid, dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-  SSDE_LAUNCH_CHECK();
-  return SSDE_OK;
+  return gn ? ssde_launch_lds<conv_wino_kernel<true>, Both>("conv(winograd)", grid, dim3(kThreads), pl.lds_bytes, st, p)
+            : ssde_launch_lds<conv_wino_kernel<false>, Both>("conv(winograd)", grid, dim3(kThreads), pl.lds_bytes, st, p);
 }

@@ -740,8 +740,6 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   SSDE_TRR(111);
 }
 
-int pow2_floor(int v) { int q = 1; while (q * 2 <= v) q *= 2; return q; }
-
 }  // namespace
 
 // over how many workgroups per tile (1, 2 or 4) a launch of `wgs` tiles over `ctot` input channels splits its reduction: up
@@ -755,90 +753,79 @@ int ssde_conv_wino4_splits(int wgs, int ctot, int c_out, unsigned flags) {
   return 1;
 }
 
-// stream == (void*)1 with lds_out: plan-only query of the GroupNorm slices per image (conv_mfma.hip, ssde_conv_gn_slices)
-int ssde_conv_wino4_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
+namespace {
+
+// Everything a launch needs, without touching a device: the parameter block (but for the split of the reduction, which takes
+// hand-over slots), and the plan the queries report.
+int wino4_plan(const ssde_conv_args* a, Wino4Params* pp, ssde_conv_plan* pl) {
   SSDE_REQUIRE(a && a->dst && a->main.p0 && a->w_main, "conv(winograd 4x4): null args");
   SSDE_REQUIRE(a->ksize == 3 && a->stride == 1 && a->pad == 1, "conv(winograd 4x4): needs 3x3, stride 1, pad 1");
   SSDE_REQUIRE(a->aux.p0 == nullptr, "conv(winograd 4x4): fused 1x1 source not supported (issue it as a second conv)");
   SSDE_REQUIRE(a->h_in == a->h_out && a->w_in == a->w_out && a->h_out % 4 == 0 && a->w_out % 4 == 0 && a->h_out >= 8 && a->w_out >= 8,
                "conv(winograd 4x4): same-size output, multiples of 4, at least 8x8 (got %dx%d)", a->h_out, a->w_out);
   const ssde_src& s = a->main;
-  SSDE_REQUIRE(s.c0 > 0 && s.c0 % 4 == 0 && s.c1 % 4 == 0 && (s.c1 == 0 || s.p1), "conv(winograd 4x4): channels must be multiples of 4");
-  const bool gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
-  if (gn) {
-    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0 && ((s.c0 + s.c1) / s.gn_groups) % 4 == 0,
-                 "conv(winograd 4x4): GroupNorm needs channels-per-group %% 4 == 0");
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "conv(winograd 4x4): GroupNorm pointers missing");
-  }
-  SSDE_REQUIRE(s.drop_thresh == 0 || s.drop_seed, "conv(winograd 4x4): dropout seed pointer missing");
+  if (int rc = ssde_src_check(s, "conv(winograd 4x4)", "", 4, SSDE_SRC_ALL)) return rc;
   // the halo loads address a source as scalar base + 32-bit byte offset
   SSDE_REQUIRE((unsigned long long)a->n * a->h_in * a->w_in * (unsigned)(s.c0 > s.c1 ? s.c0 : s.c1) * 4ull < (1ull << 32),
                "conv(winograd 4x4): a source of 4 GB or more is not addressable by this kernel");
-  Wino4Params p;
+  Wino4Params& p = *pp;
   p.src = s; p.wpk = a->w_main;
   p.N = a->n; p.H = a->h_out; p.W = a->w_out; p.Cout = a->c_out;
-  const int twt = pow2_floor((a->w_out / 4) < 8 ? (a->w_out / 4) : 8);
-  int tht = kTiles / twt; if (tht > a->h_out / 4) tht = a->h_out / 4;
-  tht = pow2_floor(tht);
-  const int imgs = kTiles / (twt * tht);
-  p.lTWt = ssde_ilog2(twt); p.lTHt = ssde_ilog2(tht);
-  p.tiles_x = ssde_cdiv(a->w_out, 4 * twt);
-  p.tiles_per_img = p.tiles_x * ssde_cdiv(a->h_out, 4 * tht);
-  p.m_tiles = ssde_cdiv(a->n, imgs) * p.tiles_per_img;
-  p.n_tiles = ssde_cdiv(a->c_out, 64);
-  p.bias = a->bias; p.chan_add = a->chan_add; p.chan_add_ld = a->chan_add_ld;
-  p.resid = a->resid; p.resid_post = a->resid_post; p.scale = a->out_scale; p.dst = a->dst;
-  p.gn_part = a->gn_part;
+  const ssde_wino_tiling t = ssde_wino_tiling_fill(p, a, 4, kTiles);
+  ssde_fill_epilogue(p, a);
   p.wino_v = a->wino_v; p.tiles_h = a->h_out / 4; p.tiles_w = a->w_out / 4; p.T = a->n * p.tiles_h * p.tiles_w;
   SSDE_REQUIRE(!a->wino_v || 36ull * (unsigned long long)p.T * (unsigned)(s.c0 + s.c1) * 4ull < (1ull << 32),
                "conv(winograd 4x4): a transformed-input by-product of 4 GB or more is not addressable by this kernel");
   // GroupNorm partials: a workgroup tile is part of one image (two epilogue rounds: 2 x tiles_per_img slices of 8 wave
   // entries) or holds `imgs` >= 2 whole images (imgs / 2 per round; 512 / imgs rows per image >= the 32 rows of one
   // epilogue trip)
-  const bool gn_ok = a->c_out % 4 == 0 && (imgs == 1 || (p.tiles_per_img == 1 && imgs <= 8));
-  SSDE_REQUIRE(!a->gn_part || gn_ok, "conv(winograd 4x4): GroupNorm partials not available for this tiling");
-  if (lds_out && stream == reinterpret_cast<void*>(1)) {
-    *lds_out = gn_ok ? (imgs == 1 ? 2 * p.tiles_per_img : 1) * (kEpiThreads / 64) : 0;
-    return SSDE_OK;
-  }
-  const int halo_px = imgs * (4 * tht + 2) * (4 * twt + 2);
+  SSDE_REQUIRE(!a->gn_part || t.gn_ok, "conv(winograd 4x4): GroupNorm partials not available for this tiling");
+  pl->gn_slices = t.gn_ok ? (t.imgs == 1 ? 2 * p.tiles_per_img : 1) * (kEpiThreads / 64) : 0;
+  const int halo_px = t.imgs * (4 * t.tht + 2) * (4 * t.twt + 2);
   SSDE_REQUIRE(halo_px <= kMaxRaw * kThreads, "conv(winograd 4x4): halo of %d pixels exceeds the staging plan", halo_px);
   int lds = (2 * kVFloats + 2 * kUFloats + 2 * 2 * 2 * halo_px) * 4;
-  if (gn) lds += (2 * imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
+  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) lds += (2 * t.imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
   const int lds_epi = kPos * 16 * kLdm * 4;
   if (lds < lds_epi) lds = lds_epi;
   p.ticket_off = lds / 4;
   lds += 16;
   SSDE_REQUIRE(lds <= 160 * 1024, "conv(winograd 4x4): %d bytes of LDS", lds);
-  if (lds_out) { *lds_out = lds; return SSDE_OK; }
+  pl->lds_bytes = lds;
+  pl->ws_floats = 0;
+  return SSDE_OK;
+}
+
+// the instantiation of a launch: GroupNorm prologue, shares of the reduction, V written as a by-product
+template <bool kGn, bool kV>
+int wino4_launch_as(const Wino4Params& p, dim3 grid, int lds, hipStream_t st) {
+  constexpr const char* kRoute = "conv(winograd 4x4)";
+  switch (p.ksplit) {
+    case 4: return ssde_launch_lds<conv_wino4_kernel<kGn, 4, kV>>(kRoute, grid, dim3(kThreads), lds, st, p);
+    case 2: return ssde_launch_lds<conv_wino4_kernel<kGn, 2, kV>>(kRoute, grid, dim3(kThreads), lds, st, p);
+    default: return ssde_launch_lds<conv_wino4_kernel<kGn, 1, kV>>(kRoute, grid, dim3(kThreads), lds, st, p);
+  }
+}
+
+}  // namespace
+
+// The route of a->tile == SSDE_TILE_WINOGRAD4.
+int ssde_conv_wino4_plan(const ssde_conv_args* a, ssde_conv_plan* pl) {
+  Wino4Params p;
+  return wino4_plan(a, &p, pl);
+}
+
+int ssde_conv_wino4_launch(const ssde_conv_args* a, hipStream_t st) {
+  Wino4Params p;
+  ssde_conv_plan pl;
+  if (int rc = wino4_plan(a, &p, &pl)) return rc;
   // Split the reduction when the launch would leave half of the CUs or more without a workgroup (8x8 maps at batch 256:
   // 128 tiles of 8 images x 64 couts)
   const int wgs = ssde_cdiv(p.m_tiles, 8) * 8 * p.n_tiles;
-  p.ksplit = a->resid != a->dst ? ssde_conv_wino4_splits(wgs, s.c0 + s.c1, a->c_out, a->flags) : 1;
+  p.ksplit = a->resid != a->dst ? ssde_conv_wino4_splits(wgs, p.src.c0 + p.src.c1, a->c_out, a->flags) : 1;
   p.sync = p.ksplit > 1 ? ssde_conv_sync_slots(p.m_tiles * p.n_tiles) : nullptr;
   if (!p.sync) p.ksplit = 1;
   const dim3 grid(wgs * p.ksplit);
-  auto go = [&](auto kfn, std::atomic<bool>& attr_set) {
-    if (!attr_set) {                            // once per instantiation, before any stream capture
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return false;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, grid, dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-    return true;
-  };
-  static std::atomic<bool> set[2][3], setv[2][3];
-  const int si = p.ksplit == 4 ? 2 : p.ksplit == 2 ? 1 : 0;
-  const bool ok = a->wino_v
-      ? (gn ? (si == 2 ? go(conv_wino4_kernel<true, 4, true>, setv[1][2]) : si == 1 ? go(conv_wino4_kernel<true, 2, true>, setv[1][1])
-                                                                                    : go(conv_wino4_kernel<true, 1, true>, setv[1][0]))
-            : (si == 2 ? go(conv_wino4_kernel<false, 4, true>, setv[0][2]) : si == 1 ? go(conv_wino4_kernel<false, 2, true>, setv[0][1])
-                                                                                     : go(conv_wino4_kernel<false, 1, true>, setv[0][0])))
-      : (gn ? (si == 2 ? go(conv_wino4_kernel<true, 4>, set[1][2]) : si == 1 ? go(conv_wino4_kernel<true, 2>, set[1][1])
-                                                                            : go(conv_wino4_kernel<true, 1>, set[1][0]))
-            : (si == 2 ? go(conv_wino4_kernel<false, 4>, set[0][2]) : si == 1 ? go(conv_wino4_kernel<false, 2>, set[0][1])
-                                                                             : go(conv_wino4_kernel<false, 1>, set[0][0])));
-  SSDE_REQUIRE(ok, "conv(winograd 4x4): hipFuncSetAttribute failed");
-  SSDE_LAUNCH_CHECK();
-  return SSDE_OK;
+  const bool gn = p.src.pro_mode == SSDE_PRO_GN || p.src.pro_mode == SSDE_PRO_GN_SILU;
+  if (a->wino_v) return gn ? wino4_launch_as<true, true>(p, grid, pl.lds_bytes, st) : wino4_launch_as<false, true>(p, grid, pl.lds_bytes, st);
+  return gn ? wino4_launch_as<true, false>(p, grid, pl.lds_bytes, st) : wino4_launch_as<false, false>(p, grid, pl.lds_bytes, st);
 }

@@ -215,15 +215,15 @@ int w4p_splits(int waves1, int Q, unsigned flags) {
   return ks;
 }
 
-int w4p_shape(const ssde_conv_args* a, W4pShape* s) {
+// the shape of a launch and the plan the queries report, without touching a device
+int w4p_shape(const ssde_conv_args* a, W4pShape* s, ssde_conv_plan* pl) {
   SSDE_REQUIRE(a && a->main.p0 && a->w_main && a->dst, "conv(winograd 4x4, position-batched): null args");
   SSDE_REQUIRE(a->ksize == 3 && a->stride == 1 && a->pad == 1, "conv(winograd 4x4, position-batched): needs 3x3, stride 1, pad 1");
   SSDE_REQUIRE(a->aux.p0 == nullptr, "conv(winograd 4x4, position-batched): fused 1x1 source not supported (issue it as a second conv)");
   SSDE_REQUIRE(a->n > 0 && a->h_in == a->h_out && a->w_in == a->w_out && a->h_out % 4 == 0 && a->w_out % 4 == 0 && a->h_out > 0 && a->w_out > 0,
                "conv(winograd 4x4, position-batched): same-size output, multiples of 4 (got %dx%d)", a->h_out, a->w_out);
   const ssde_src& src = a->main;
-  SSDE_REQUIRE(src.c0 > 0 && src.c0 % 4 == 0 && src.c1 % 4 == 0 && (src.c1 == 0 || src.p1),
-               "conv(winograd 4x4, position-batched): channels must be multiples of 4");
+  if (int rc = ssde_src_check(src, "conv(winograd 4x4, position-batched)", "", 4, SSDE_SRC_NEEDS_C0)) return rc;   // (the prologue: wino4_xform.hip)
   const int ctot = src.c0 + src.c1;
   SSDE_REQUIRE(ctot % (8 * kKC) == 0, "conv(winograd 4x4, position-batched): input channels must be a multiple of %d (got %d)", 8 * kKC, ctot);
   SSDE_REQUIRE(a->c_out > 0 && a->c_out % 4 == 0, "conv(winograd 4x4, position-batched): output channels must be a multiple of 4");
@@ -235,30 +235,25 @@ int w4p_shape(const ssde_conv_args* a, W4pShape* s) {
   s->ks = w4p_splits(36 * ssde_cdiv(s->T, kBM) * (s->Np / kBN), s->Q, a->flags);
   s->v_floats = (int64_t)36 * s->T * ctot;
   s->slab_floats = (int64_t)36 * s->T * s->Np;
+  pl->lds_bytes = 16 * kOutLdt * 4;
+  pl->gn_slices = (a->h_out / 4) * (a->w_out / 4);          // one slice per tile (c_out % 4 == 0 on this route)
+  pl->ws_floats = s->v_floats + s->ks * s->slab_floats;
   return SSDE_OK;
 }
 
 }  // namespace
 
-// floats of ssde_conv_args.wino_ws a launch of this route needs: V, then the slabs of the shares (< 0: invalid arguments)
-int64_t ssde_conv_wino4p_ws_floats(const ssde_conv_args* a) {
+// The route of a->tile == SSDE_TILE_WINOGRAD4P.  Its workspace (ssde_conv_args.wino_ws) holds V, then the slabs of the shares.
+int ssde_conv_wino4p_plan(const ssde_conv_args* a, ssde_conv_plan* pl) {
   W4pShape s;
-  if (int rc = w4p_shape(a, &s)) return rc;
-  return s.v_floats + s.ks * s.slab_floats;
+  return w4p_shape(a, &s, pl);
 }
 
-// launch (lds_out == NULL), LDS query, or GroupNorm-slice query (stream == 1): conv_mfma.hip's wino_launcher forms.  Everything
-// is validated before the first launch is enqueued.
-int ssde_conv_wino4p_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
+// Everything is validated before the first launch is enqueued.
+int ssde_conv_wino4p_launch(const ssde_conv_args* a, hipStream_t st) {
   W4pShape s;
-  if (int rc = w4p_shape(a, &s)) return rc;
-  const int per_img = (a->h_out / 4) * (a->w_out / 4);
-  if (lds_out && stream == reinterpret_cast<void*>(1)) {
-    *lds_out = per_img;                          // one slice per tile (c_out % 4 == 0 on this route)
-    return SSDE_OK;
-  }
-  const int lds = 16 * kOutLdt * 4;
-  if (lds_out) { *lds_out = lds; return SSDE_OK; }
+  ssde_conv_plan pl;
+  if (int rc = w4p_shape(a, &s, &pl)) return rc;
   // a workspace sized for fewer shares (a plan exported on a device with fewer CUs) takes fewer shares
   while (s.ks > 1 && a->wino_ws_floats < s.v_floats + s.ks * s.slab_floats) s.ks /= 2;
   SSDE_REQUIRE(a->wino_ws && a->wino_ws_floats >= s.v_floats + s.ks * s.slab_floats,
@@ -268,17 +263,16 @@ int ssde_conv_wino4p_launch(const ssde_conv_args* a, void* stream, int* lds_out)
   float* m = a->wino_ws + s.v_floats;
   ssde_conv_args x = *a;                         // the transform pass writes V into the workspace (wino_v is not this route's)
   x.wino_v = v;
-  if (int rc = ssde_wino4_xform_vq_launch(&x, stream)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = ssde_wino4_xform_vq_launch(&x, st)) return rc;
   const Wino4pGemmParams g{v, a->w_main, m, s.T, s.Q, s.Np, ssde_cdiv(s.T, kBM), s.Np / kBN, s.ks, s.Q / s.ks};
   const int waves = 36 * g.m_tiles * g.n_tiles * s.ks;
   hipLaunchKernelGGL(wino4p_gemm_kernel, dim3(ssde_cdiv(waves, kGemmWaves)), dim3(64 * kGemmWaves), 0, st, g);
   SSDE_LAUNCH_CHECK();
   Wino4pOutParams o;
   o.m = m; o.T = s.T; o.Np = s.Np; o.ks = s.ks;
-  o.H = a->h_out; o.W = a->w_out; o.tiles_w = a->w_out / 4; o.per_img = per_img;
+  o.H = a->h_out; o.W = a->w_out; o.tiles_w = a->w_out / 4; o.per_img = pl.gn_slices;
   o.e = SsdeEpi{a->bias, a->chan_add, a->chan_add_ld, a->resid, a->resid_post, a->out_scale, a->dst, a->c_out, a->gn_part};
-  hipLaunchKernelGGL(wino4p_out_kernel, dim3(s.T, s.Np / kBN), dim3(64), lds, st, o);
+  hipLaunchKernelGGL(wino4p_out_kernel, dim3(s.T, s.Np / kBN), dim3(64), pl.lds_bytes, st, o);
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
 }

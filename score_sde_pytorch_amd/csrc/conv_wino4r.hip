@@ -384,8 +384,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino4r_kernel(const Wino4rPa
   SSDE_RT(5);
 }
 
-int pow2_floor(int v) { int q = 1; while (q * 2 <= v) q *= 2; return q; }
-
 }  // namespace
 
 // over how many workgroups per tile (1, 2 or 4) a launch of `wgs` tiles over `ctot` input channels splits its reduction: the
@@ -403,42 +401,48 @@ int ssde_conv_wino4r_splits(int wgs, int ctot, int c_out, unsigned flags) {
   return 1;
 }
 
-// stream == (void*)1 with lds_out: plan-only query of the GroupNorm slices per image (conv_mfma.hip, ssde_conv_gn_slices)
-int ssde_conv_wino4r_launch(const ssde_conv_args* a, void* stream, int* lds_out) {
+namespace {
+
+// Everything a launch needs, without touching a device: the parameter block (but for the split of the reduction, which takes
+// hand-over slots), and the plan the queries report.  The source's prologue is the transform pass's business (wino4_xform.hip).
+int wino4r_plan(const ssde_conv_args* a, Wino4rParams* pp, ssde_conv_plan* pl) {
   SSDE_REQUIRE(a && a->dst && a->main.p0 && a->w_main, "conv(winograd 4x4, register-fed): null args");
   SSDE_REQUIRE(a->ksize == 3 && a->stride == 1 && a->pad == 1, "conv(winograd 4x4, register-fed): needs 3x3, stride 1, pad 1");
   SSDE_REQUIRE(a->aux.p0 == nullptr, "conv(winograd 4x4, register-fed): fused 1x1 source not supported (issue it as a second conv)");
   SSDE_REQUIRE(a->h_in == a->h_out && a->w_in == a->w_out && a->h_out % 4 == 0 && a->w_out % 4 == 0 && a->h_out >= 8 && a->w_out >= 8,
                "conv(winograd 4x4, register-fed): same-size output, multiples of 4, at least 8x8 (got %dx%d)", a->h_out, a->w_out);
   const ssde_src& s = a->main;
-  SSDE_REQUIRE(s.c0 > 0 && s.c0 % 4 == 0 && s.c1 % 4 == 0 && (s.c1 == 0 || s.p1), "conv(winograd 4x4, register-fed): channels must be multiples of 4");
+  if (int rc = ssde_src_check(s, "conv(winograd 4x4, register-fed)", "", 4, SSDE_SRC_NEEDS_C0)) return rc;
   SSDE_REQUIRE((s.c0 + s.c1) % 8 == 0, "conv(winograd 4x4, register-fed): input channels must be a multiple of 8 (the stage loop runs in pairs)");
-  Wino4rParams p;
+  Wino4rParams& p = *pp;
   p.v = a->wino_v; p.wpk = a->w_main;
   p.N = a->n; p.H = a->h_out; p.W = a->w_out; p.Cout = a->c_out; p.Ctot = s.c0 + s.c1;
-  const int twt = pow2_floor((a->w_out / 4) < 8 ? (a->w_out / 4) : 8);
-  int tht = kTiles / twt; if (tht > a->h_out / 4) tht = a->h_out / 4;
-  tht = pow2_floor(tht);
-  const int imgs = kTiles / (twt * tht);
-  p.lTWt = ssde_ilog2(twt); p.lTHt = ssde_ilog2(tht);
-  p.tiles_x = ssde_cdiv(a->w_out, 4 * twt);
-  p.tiles_per_img = p.tiles_x * ssde_cdiv(a->h_out, 4 * tht);
-  p.m_tiles = ssde_cdiv(a->n, imgs) * p.tiles_per_img;
-  p.n_tiles = ssde_cdiv(a->c_out, kBN);
-  p.bias = a->bias; p.chan_add = a->chan_add; p.chan_add_ld = a->chan_add_ld;
-  p.resid = a->resid; p.resid_post = a->resid_post; p.scale = a->out_scale; p.dst = a->dst;
-  p.gn_part = a->gn_part;
+  static_assert(kBN == 64, "ssde_wino_tiling_fill: 64 output channels per workgroup");
+  const ssde_wino_tiling t = ssde_wino_tiling_fill(p, a, 4, kTiles);
+  ssde_fill_epilogue(p, a);
   p.tiles_h = a->h_out / 4; p.tiles_w = a->w_out / 4; p.T = a->n * p.tiles_h * p.tiles_w;
-  const bool gn_ok = a->c_out % 4 == 0 && (imgs == 1 || (p.tiles_per_img == 1 && imgs <= 8));
-  SSDE_REQUIRE(!a->gn_part || gn_ok, "conv(winograd 4x4, register-fed): GroupNorm partials not available for this tiling");
-  if (lds_out && stream == reinterpret_cast<void*>(1)) {
-    *lds_out = gn_ok ? (imgs == 1 ? 2 * p.tiles_per_img : 1) * (kThreads / 64) : 0;
-    return SSDE_OK;
-  }
+  SSDE_REQUIRE(!a->gn_part || t.gn_ok, "conv(winograd 4x4, register-fed): GroupNorm partials not available for this tiling");
+  pl->gn_slices = t.gn_ok ? (t.imgs == 1 ? 2 * p.tiles_per_img : 1) * (kThreads / 64) : 0;
   p.ticket_off = kLds / 4;
-  const int lds = kLds + 16;
-  SSDE_REQUIRE(lds <= 160 * 1024, "conv(winograd 4x4, register-fed): %d bytes of LDS", lds);
-  if (lds_out) { *lds_out = lds; return SSDE_OK; }
+  pl->lds_bytes = kLds + 16;
+  static_assert(kLds + 16 <= 160 * 1024, "LDS of a CU");
+  pl->ws_floats = 0;
+  return SSDE_OK;
+}
+
+}  // namespace
+
+// The route of a->tile == SSDE_TILE_WINOGRAD4R: the matrix kernel; ssde_conv2d issues the transform pass in front of it.
+int ssde_conv_wino4r_plan(const ssde_conv_args* a, ssde_conv_plan* pl) {
+  Wino4rParams p;
+  return wino4r_plan(a, &p, pl);
+}
+
+int ssde_conv_wino4r_launch(const ssde_conv_args* a, hipStream_t st) {
+  constexpr const char* kRoute = "conv(winograd 4x4, register-fed)";
+  Wino4rParams p;
+  ssde_conv_plan pl;
+  if (int rc = wino4r_plan(a, &p, &pl)) return rc;
   SSDE_REQUIRE(a->wino_v, "conv(winograd 4x4, register-fed): the transformed-input buffer (ssde_conv_args.wino_v) is missing");
   SSDE_REQUIRE(36ull * (unsigned long long)p.T * (unsigned)p.Ctot * 4ull < (1ull << 32),
                "conv(winograd 4x4, register-fed): a transformed input of 4 GB or more is not addressable by this kernel");
@@ -450,19 +454,9 @@ int ssde_conv_wino4r_launch(const ssde_conv_args* a, void* stream, int* lds_out)
   p.sync = p.ksplit > 1 ? ssde_conv_sync_slots(p.m_tiles * p.n_tiles) : nullptr;
   if (!p.sync) p.ksplit = 1;
   const dim3 grid(wgs * p.ksplit);
-  auto go = [&](auto kfn, std::atomic<bool>& attr_set) {
-    if (!attr_set) {                            // once per instantiation, before any stream capture
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return false;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, grid, dim3(kThreads), lds, static_cast<hipStream_t>(stream), p);
-    return true;
-  };
-  static std::atomic<bool> set[3];
-  const bool ok = p.ksplit == 4 ? go(conv_wino4r_kernel<4>, set[2]) : p.ksplit == 2 ? go(conv_wino4r_kernel<2>, set[1])
-                : go(conv_wino4r_kernel<1>, set[0]);
-  SSDE_REQUIRE(ok, "conv(winograd 4x4, register-fed): hipFuncSetAttribute failed");
-  SSDE_LAUNCH_CHECK();
-  return SSDE_OK;
+  switch (p.ksplit) {
+    case 4: return ssde_launch_lds<conv_wino4r_kernel<4>>(kRoute, grid, dim3(kThreads), pl.lds_bytes, st, p);
+    case 2: return ssde_launch_lds<conv_wino4r_kernel<2>>(kRoute, grid, dim3(kThreads), pl.lds_bytes, st, p);
+    default: return ssde_launch_lds<conv_wino4r_kernel<1>>(kRoute, grid, dim3(kThreads), pl.lds_bytes, st, p);
+  }
 }

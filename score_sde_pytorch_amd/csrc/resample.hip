@@ -406,19 +406,11 @@ extern "C" int ssde_upfirdn2d(const ssde_upfirdn_args* a, void* stream) {
     p.dst = a->dst; p.dst2 = a->dst2; p.accumulate = a->accumulate;
     const int lds = (p.ih * p.iw * kFirCh + a->kh * a->kw) * 4;
     SSDE_REQUIRE(lds <= 160 * 1024, "upfirdn2d: %d bytes of LDS", lds);
-    static std::atomic<bool> attr_set{false};   // once, before any stream capture
-    if (!attr_set) {
-      SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(upfirdn_wide_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(upfirdn_wide_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(upfirdn_wide_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set = true;
-    }
+    using Wide = ssde_lds_kernels<upfirdn_wide_kernel<2, 1>, upfirdn_wide_kernel<1, 2>, upfirdn_wide_kernel<1, 1>>;
     const dim3 grid((unsigned)((size_t)a->n * p.tiles_y * p.tiles_x * p.cchunks));
-    if (a->up == 2) hipLaunchKernelGGL((upfirdn_wide_kernel<2, 1>), grid, dim3(256), lds, st, p);
-    else if (a->down == 2) hipLaunchKernelGGL((upfirdn_wide_kernel<1, 2>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((upfirdn_wide_kernel<1, 1>), grid, dim3(256), lds, st, p);
-    SSDE_LAUNCH_CHECK();
-    return SSDE_OK;
+    if (a->up == 2) return ssde_launch_lds<upfirdn_wide_kernel<2, 1>, Wide>("upfirdn2d", grid, dim3(256), lds, st, p);
+    if (a->down == 2) return ssde_launch_lds<upfirdn_wide_kernel<1, 2>, Wide>("upfirdn2d", grid, dim3(256), lds, st, p);
+    return ssde_launch_lds<upfirdn_wide_kernel<1, 1>, Wide>("upfirdn2d", grid, dim3(256), lds, st, p);
   }
   FirParams p;
   p.src = a->src;

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <atomic>
+#include <initializer_list>
 #include "../../include/ssde.h"
 
 #define SSDE_OK 0
@@ -13,21 +14,40 @@
 #define SSDE_EHIP (-5)
 
 void ssde_set_error(const char* fmt, ...);
-// conv_wino.hip: launch (lds_out == NULL) or plan-only (returns the LDS bytes through lds_out)
-int ssde_conv_wino_launch(const ssde_conv_args* a, void* stream, int* lds_out);
-int ssde_conv_wino4_launch(const ssde_conv_args* a, void* stream, int* lds_out);   // conv_wino4.hip, same forms
-bool ssde_wino4_xform_merges_gn(const ssde_conv_args* a);                               // wino4_xform.hip: the pass merges the source's GroupNorm partials itself (gn_in_part0)
-int ssde_wino4_xform_vq_launch(const ssde_conv_args* a, void* stream);              // wino4_xform.hip: V = B^T pro(x) B into a->wino_v
-int ssde_conv_wino4r_launch(const ssde_conv_args* a, void* stream, int* lds_out);  // conv_wino4r.hip (two-kernel form, operands from registers)
-int ssde_conv_wino4p_launch(const ssde_conv_args* a, void* stream, int* lds_out);  // conv_wino4p.hip (position-batched GEMMs, the 4x4 maps)
-int64_t ssde_conv_wino4p_ws_floats(const ssde_conv_args* a);                       // conv_wino4p.hip: its workspace (ssde_conv_args.wino_ws)
-bool ssde_conv1x1_wants(const ssde_conv_args* a);                                    // conv1x1.hip
-int ssde_conv1x1_launch(const ssde_conv_args* a, void* stream, int* lds_out);
+// ---- the routes of ssde_conv2d --------------------------------------------------------------------------------------
+// What a launch needs, answered without enqueuing anything or touching a device: the dynamic LDS of its (last) kernel, the slices
+// per image of the GroupNorm partials its epilogue can write (0: none for this tiling), the floats of ssde_conv_args.wino_ws.
+struct ssde_conv_plan { int lds_bytes; int gn_slices; int64_t ws_floats; };
+// One row of the table in conv_mfma.hip, which ssde_conv2d and the three plan queries (ssde_conv_lds_bytes, ssde_conv_gn_slices,
+// ssde_conv_ws_floats) walk in order: the first route that wants a launch gets it.
+struct ssde_conv_route {
+  const char* name;
+  bool (*wants)(const ssde_conv_args*);                   // does ssde_conv2d hand this launch to the route?
+  int  (*plan)(const ssde_conv_args*, ssde_conv_plan*);   // validates, enqueues nothing, touches no device
+  int  (*launch)(const ssde_conv_args*, hipStream_t);     // plans again, then the launch-only checks, then enqueues
+  bool takes_pad_end;                                     // false: ssde_conv_args.pad_end != 0 is refused in front of the route
+};
+// A route's launch() repeats its plan() and adds the checks of what only a launch has to bring: the transformed-input buffer,
+// the workspace, the source pointers the kernel dereferences, the hand-over slots of a split reduction.
+int ssde_conv_wino_plan(const ssde_conv_args* a, ssde_conv_plan* pl);               // conv_wino.hip: F(2x2,3x3)
+int ssde_conv_wino_launch(const ssde_conv_args* a, hipStream_t st);
+int ssde_conv_wino4_plan(const ssde_conv_args* a, ssde_conv_plan* pl);              // conv_wino4.hip: F(4x4,3x3), one kernel
+int ssde_conv_wino4_launch(const ssde_conv_args* a, hipStream_t st);
+int ssde_conv_wino4r_plan(const ssde_conv_args* a, ssde_conv_plan* pl);             // conv_wino4r.hip: the matrix kernel of the two-kernel form
+int ssde_conv_wino4r_launch(const ssde_conv_args* a, hipStream_t st);              //   (operands from registers; ssde_conv2d issues the transform pass)
+int ssde_conv_wino4p_plan(const ssde_conv_args* a, ssde_conv_plan* pl);             // conv_wino4p.hip: position-batched GEMMs, the 4x4 maps
+int ssde_conv_wino4p_launch(const ssde_conv_args* a, hipStream_t st);
+bool ssde_conv1x1_wants(const ssde_conv_args* a);                                    // conv1x1.hip: 1x1-only launches large enough for the GEMM
+int ssde_conv1x1_plan(const ssde_conv_args* a, ssde_conv_plan* pl);
+int ssde_conv1x1_launch(const ssde_conv_args* a, hipStream_t st);
+bool ssde_conv_small_wants(const ssde_conv_args* a);                                 // conv_small.hip (image heads: at most 4 couts)
+int ssde_conv_small_plan(const ssde_conv_args* a, ssde_conv_plan* pl);
+int ssde_conv_small_launch(const ssde_conv_args* a, hipStream_t st);
+bool ssde_wino4_xform_merges_gn(const ssde_conv_args* a);                            // wino4_xform.hip: the pass merges the source's GroupNorm partials itself (gn_in_part0)
+int ssde_wino4_xform_vq_launch(const ssde_conv_args* a, void* stream);               // wino4_xform.hip: V = B^T pro(x) B into a->wino_v
 unsigned* ssde_conv_sync_slots(int need);                                            // conv_mfma.hip
-int ssde_conv_wino4_splits(int wgs, int ctot, int c_out, unsigned flags);                         // conv_wino4.hip
-int ssde_conv_wino4r_splits(int wgs, int ctot, int c_out, unsigned flags);                        // conv_wino4r.hip
-bool ssde_conv_small_wants(const ssde_conv_args* a);                                             // conv_small.hip (image heads: at most 4 couts)
-int ssde_conv_small_launch(const ssde_conv_args* a, void* stream, int* lds_out);
+int ssde_conv_wino4_splits(int wgs, int ctot, int c_out, unsigned flags);            // conv_wino4.hip
+int ssde_conv_wino4r_splits(int wgs, int ctot, int c_out, unsigned flags);           // conv_wino4r.hip
 bool ssde_wgrad_wino_wants(const ssde_wgrad_args* a);                                // wgrad_wino.hip
 int64_t ssde_wgrad_wino_scratch_floats(const ssde_wgrad_args* a);
 int ssde_wgrad_wino_launch(const ssde_wgrad_args* a, void* stream);
@@ -58,6 +78,85 @@ int ssde_num_cus();                                                             
 static inline int ssde_ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static inline int ssde_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool ssde_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+static inline int ssde_pow2_floor(int v) { int q = 1; while (q * 2 <= v) q *= 2; return q; }
+
+// ---- host helpers of the launchers ----------------------------------------------------------------------------------
+// What every kernel that stages an ssde_src asks of it.  `route` prefixes the message ("conv(winograd 4x4)"), `what` names the
+// source where a launch has two ("main ", "aux ", else "").  boundary: c0 of a channel concatenation must be a multiple of it (4 =
+// nothing beyond the channel multiple).  The flags switch on the checks that some launchers leave to a kernel in front of theirs.
+enum { SSDE_SRC_NEEDS_C0 = 1, SSDE_SRC_GN = 2, SSDE_SRC_SEED = 4, SSDE_SRC_ALL = 7 };
+static inline int ssde_src_check(const ssde_src& s, const char* route, const char* what, int boundary, int checks) {
+  SSDE_REQUIRE(!(checks & SSDE_SRC_NEEDS_C0) || (s.p0 != nullptr && s.c0 > 0), "%s: %ssource missing", route, what);
+  SSDE_REQUIRE(s.c0 % 4 == 0 && s.c1 % 4 == 0, "%s: %schannels must be multiples of 4 (got %d,%d)", route, what, s.c0, s.c1);
+  SSDE_REQUIRE(s.c1 == 0 || s.p1 != nullptr, "%s: %ssecond tensor missing", route, what);
+  SSDE_REQUIRE(s.c1 == 0 || s.c0 % boundary == 0, "%s: %sconcat boundary must be a multiple of %d", route, what, boundary);
+  if ((checks & SSDE_SRC_GN) && (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU)) {
+    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0 && ((s.c0 + s.c1) / s.gn_groups) % 4 == 0,
+                 "%s: %sGroupNorm needs channels-per-group %% 4 == 0", route, what);
+    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "%s: %sGroupNorm pointers missing", route, what);
+  }
+  SSDE_REQUIRE(!(checks & SSDE_SRC_SEED) || s.drop_thresh == 0 || s.drop_seed, "%s: %sdropout seed pointer missing", route, what);
+  return SSDE_OK;
+}
+
+// Tiling of the Winograd kernels (conv_wino, conv_wino4, conv_wino4r): a workgroup owns `tiles` output tiles of edge x edge
+// pixels, twt x tht of them (powers of two, at most 8 wide) of each of `imgs` images.  Fills the tiling fields of the kernel's
+// parameter block.  gn_ok: the epilogue can write GroupNorm partials -- a workgroup's tiles are part of one image, or at most 8
+// whole images (then the rows of an image are at least one epilogue trip).
+struct ssde_wino_tiling { int twt, tht, imgs; bool gn_ok; };
+template <class P>
+static inline ssde_wino_tiling ssde_wino_tiling_fill(P& p, const ssde_conv_args* a, int edge, int tiles) {
+  ssde_wino_tiling t;
+  t.twt = ssde_pow2_floor((a->w_out / edge) < 8 ? (a->w_out / edge) : 8);
+  t.tht = tiles / t.twt; if (t.tht > a->h_out / edge) t.tht = a->h_out / edge;
+  t.tht = ssde_pow2_floor(t.tht);
+  t.imgs = tiles / (t.twt * t.tht);
+  p.lTWt = ssde_ilog2(t.twt); p.lTHt = ssde_ilog2(t.tht);
+  p.tiles_x = ssde_cdiv(a->w_out, edge * t.twt);
+  p.tiles_per_img = p.tiles_x * ssde_cdiv(a->h_out, edge * t.tht);
+  p.m_tiles = ssde_cdiv(a->n, t.imgs) * p.tiles_per_img;
+  p.n_tiles = ssde_cdiv(a->c_out, 64);
+  t.gn_ok = a->c_out % 4 == 0 && (t.imgs == 1 || (p.tiles_per_img == 1 && t.imgs <= 8));
+  return t;
+}
+
+// the epilogue fields of a kernel's parameter block
+template <class P>
+static inline void ssde_fill_epilogue(P& p, const ssde_conv_args* a) {
+  p.bias = a->bias; p.chan_add = a->chan_add; p.chan_add_ld = a->chan_add_ld;
+  p.resid = a->resid; p.resid_post = a->resid_post; p.scale = a->out_scale; p.dst = a->dst;
+  p.gn_part = a->gn_part;
+}
+
+// Launch of a kernel whose dynamic LDS may exceed the 64 KB a kernel gets unasked (up to the 160 KB of a CU).  The limit is raised
+// once per kernel, at the first launch, which the engines make outside any stream capture; the flag is keyed on the kernel's
+// ADDRESS (several instantiations share one function type).  Group: a launcher that picks among a few instantiations names them
+// all, ssde_lds_kernels<k0, k1, ...>, and its first launch raises the limit of every one (so that no later pick is a first).
+// Idempotent: a lost race only sets the attribute twice.
+template <auto... Kfns>
+struct ssde_lds_kernels {
+  static int opt_in(const char* route) {
+    static std::atomic<bool> done{false};
+    if (!done) {
+      for (const void* k : {reinterpret_cast<const void*>(Kfns)...}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) {
+          ssde_set_error("%s: hipFuncSetAttribute failed: %s", route, hipGetErrorString(e));
+          return SSDE_EHIP;
+        }
+      }
+      done = true;
+    }
+    return SSDE_OK;
+  }
+};
+template <auto Kfn, class Group = ssde_lds_kernels<Kfn>, class... Args>
+static inline int ssde_launch_lds(const char* route, dim3 grid, dim3 block, int lds_bytes, hipStream_t st, const Args&... args) {
+  if (int rc = Group::opt_in(route)) return rc;
+  hipLaunchKernelGGL(Kfn, grid, block, lds_bytes, st, args...);
+  SSDE_LAUNCH_CHECK();
+  return SSDE_OK;
+}
 
 // Every LDS byte is carved from the dynamic region: a static __shared__ precedes the dynamic region
 // unpadded and can knock its base off 16-byte alignment (cdna_hip_programming.md Guideline 17).  The

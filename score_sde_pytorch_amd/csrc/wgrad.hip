@@ -399,15 +399,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgParams p) {
 template <int KS, int CO_B, int CI_B>
 int launch(const WgParams& p, int lds_bytes, hipStream_t st) {
   constexpr int BCO = 2 * CO_B * 32, BCI = 2 * CI_B * 32;
-  auto kfn = wgrad_kernel<KS, CO_B, CI_B>;
-  static std::atomic<bool> attr_set{false};   // once per instantiation, before any stream capture
-  if (!attr_set) {
-    SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
   const int ntiles = p.co_tiles * p.ci_tiles;
-  hipLaunchKernelGGL(kfn, dim3(ssde_cdiv(p.splits, 8) * 8 * ntiles), dim3(kThreads), lds_bytes, st, p);
-  SSDE_LAUNCH_CHECK();
+  if (int rc = ssde_launch_lds<wgrad_kernel<KS, CO_B, CI_B>>("wgrad", dim3(ssde_cdiv(p.splits, 8) * 8 * ntiles), dim3(kThreads), lds_bytes, st, p)) return rc;
   if (p.splits > 1) {
     const size_t total = (size_t)KS * KS * BCO * BCI * ntiles;
     size_t blocks = (total + 255) / 256;
@@ -417,8 +410,6 @@ int launch(const WgParams& p, int lds_bytes, hipStream_t st) {
   }
   return SSDE_OK;
 }
-
-int pow2_floor(int v) { int q = 1; while (q * 2 <= v) q *= 2; return q; }
 
 struct WgPlan { WgParams p; int lds; int64_t slab_floats; int pref_splits; };
 
@@ -460,9 +451,9 @@ int make_plan(const ssde_wgrad_args* a, WgPlan* pl) {
   if (a->ksize == 1) px = 64;
   else if (a->stride == 2) px = 32;
   else px = hw >= 128 ? 128 : 64;
-  const int tw = pow2_floor(a->w_out < 16 ? a->w_out : 16);
+  const int tw = ssde_pow2_floor(a->w_out < 16 ? a->w_out : 16);
   int th = px / tw; if (th > a->h_out) th = a->h_out;
-  th = pow2_floor(th);
+  th = ssde_pow2_floor(th);
   const int imgs = px / (tw * th);
   p.lTW = ssde_ilog2(tw); p.lTH = ssde_ilog2(th); p.lPX = ssde_ilog2(px);
   p.tiles_x = ssde_cdiv(a->w_out, tw);

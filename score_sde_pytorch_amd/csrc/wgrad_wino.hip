@@ -413,18 +413,13 @@ int ssde_wgrad_wino_launch(const ssde_wgrad_args* a, void* stream) {
   }
   SSDE_REQUIRE(a->scratch, "wgrad(winograd): scratch missing");
   constexpr int lds = (4 * kStageFloats + kRawX + kRawG) * 4;
-  static std::atomic<bool> attr_set{false};   // once, before any stream capture
-  if (!attr_set) {
-    SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_wino_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_wino_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  using Both = ssde_lds_kernels<wgrad_wino_kernel<false>, wgrad_wino_kernel<true>>;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int ntiles = p.co_tiles * p.ci_tiles;
   const dim3 grid(ssde_cdiv(p.splits * ntiles, 8) * 8);
-  if (gn) hipLaunchKernelGGL(wgrad_wino_kernel<true>, grid, dim3(kThreads), lds, st, p);
-  else hipLaunchKernelGGL(wgrad_wino_kernel<false>, grid, dim3(kThreads), lds, st, p);
-  SSDE_LAUNCH_CHECK();
+  if (int rc = gn ? ssde_launch_lds<wgrad_wino_kernel<true>, Both>("wgrad(winograd)", grid, dim3(kThreads), lds, st, p)
+                  : ssde_launch_lds<wgrad_wino_kernel<false>, Both>("wgrad(winograd)", grid, dim3(kThreads), lds, st, p))
+    return rc;
   int blocks = ntiles * 16;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(wgrad_wino_reduce_kernel, dim3(blocks), dim3(256), 0, st, p);
