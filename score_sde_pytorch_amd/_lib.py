@@ -380,6 +380,25 @@ def wgrad_route_flags(env=None):
     return f
 
 
+# the geometry of a weight-gradient launch: with the source's channels and prologue, all that the library's host queries read
+WGRAD_GEOMETRY = ("g_ld", "g_off", "n", "h_in", "w_in", "h_out", "w_out", "c_out", "ksize", "stride", "pad", "pad_end",
+                  "cin_store", "transpose_out")
+
+
+def wgrad_shape_args(src, flags=None, **geometry):
+    """The shape-only ssde_wgrad_args that ssde_wgrad_scratch_floats and ssde_wgrad_wants_winograd4 take (no pointer is looked
+    at).  src: a mapping with c0, c1, pro_mode, gn_groups; geometry: every name of WGRAD_GEOMETRY, none defaulted -- a field a
+    caller forgets would reach the library as 0; flags: SSDE_WGRADF_* (None: the A/B variables of the environment)."""
+    if sorted(geometry) != sorted(WGRAD_GEOMETRY):
+        raise TypeError("wgrad_shape_args: geometry must name exactly %s" % (WGRAD_GEOMETRY,))
+    a = WgradArgs()
+    a.src.c0, a.src.c1, a.src.pro_mode, a.src.gn_groups = src["c0"], src["c1"], src["pro_mode"], src["gn_groups"]
+    for k in WGRAD_GEOMETRY:
+        setattr(a, k, int(geometry[k]))
+    a.flags = wgrad_route_flags() if flags is None else flags
+    return a
+
+
 def gn_bwd_route_flags(env=None):
     e = os.environ if env is None else env
     return GNBWDF_THREE_KERNELS if e.get("SSDE_GN_BWD_FUSED", "1") == "0" else 0

@@ -452,14 +452,7 @@ class TrainEngine(E.UNetEngine):
     @staticmethod
     def _wgrad_scratch(fields):
         """Ask the library how much slab scratch its preferred pixel split of this launch needs (shape-only query)."""
-        a = L.WgradArgs()
-        for k in ("g_ld", "g_off", "n", "h_in", "w_in", "h_out", "w_out", "c_out", "ksize", "stride", "pad", "cin_store",
-                  "transpose_out"):
-            setattr(a, k, fields[k])
-        a.pad_end = fields.get("pad_end", 0)
-        s = fields["src"]
-        a.src.c0, a.src.c1, a.src.pro_mode, a.src.gn_groups = s["c0"], s["c1"], s["pro_mode"], s["gn_groups"]
-        a.flags = fields.get("flags", L.wgrad_route_flags())
+        a = L.wgrad_shape_args(fields["src"], fields.get("flags"), **{k: fields[k] for k in L.WGRAD_GEOMETRY})
         r = int(L.load().ssde_wgrad_scratch_floats(C.byref(a)))
         if r < 0:
             L.check(r, "ssde_wgrad_scratch_floats")

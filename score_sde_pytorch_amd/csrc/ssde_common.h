@@ -48,12 +48,25 @@ int ssde_wino4_xform_vq_launch(const ssde_conv_args* a, void* stream);          
 unsigned* ssde_conv_sync_slots(int need);                                            // conv_mfma.hip
 int ssde_conv_wino4_splits(int wgs, int ctot, int c_out, unsigned flags);            // conv_wino4.hip
 int ssde_conv_wino4r_splits(int wgs, int ctot, int c_out, unsigned flags);           // conv_wino4r.hip
-bool ssde_wgrad_wino_wants(const ssde_wgrad_args* a);                                // wgrad_wino.hip
-int64_t ssde_wgrad_wino_scratch_floats(const ssde_wgrad_args* a);
-int ssde_wgrad_wino_launch(const ssde_wgrad_args* a, void* stream);
-bool ssde_wgrad_wino4_wants(const ssde_wgrad_args* a);                               // wgrad_wino4.hip (asked first)
-int64_t ssde_wgrad_wino4_scratch_floats(const ssde_wgrad_args* a);
-int ssde_wgrad_wino4_launch(const ssde_wgrad_args* a, void* stream);
+// ---- the routes of ssde_conv_wgrad ----------------------------------------------------------------------------------
+// What a launch needs, answered without enqueuing anything or touching a device: its scratch is fixed_floats (operands it parks
+// there) + split_floats per split of the reduction over pixels; scratch_floats is that sum for the split the route prefers (0:
+// none needed), splits the count this launch asks for (ssde_wgrad_args.splits, else the preferred one).
+struct ssde_wgrad_plan { int64_t scratch_floats, fixed_floats, split_floats; int splits; };
+// One row of the table in wgrad.hip, which ssde_conv_wgrad, ssde_wgrad_scratch_floats and ssde_wgrad_wants_winograd4 walk in
+// order, behind the checks of what EVERY route asks of the arguments (wgrad_args_check): the first route that wants a launch gets it.
+struct ssde_wgrad_route {
+  const char* name;
+  bool (*wants)(const ssde_wgrad_args*);                    // only what selects the route
+  int  (*plan)(const ssde_wgrad_args*, ssde_wgrad_plan*);   // validates, enqueues nothing, touches no device
+  int  (*launch)(const ssde_wgrad_args*, hipStream_t);      // plans again, then the checks of what only a launch brings -- the
+};                                                          // tensors, the scratch (to which it fits the split) --, then enqueues
+bool ssde_wgrad_wino4_wants(const ssde_wgrad_args* a);                               // wgrad_wino4.hip: F(4x4,3x3)
+int ssde_wgrad_wino4_plan(const ssde_wgrad_args* a, ssde_wgrad_plan* pl);
+int ssde_wgrad_wino4_launch(const ssde_wgrad_args* a, hipStream_t st);
+bool ssde_wgrad_wino_wants(const ssde_wgrad_args* a);                                // wgrad_wino.hip: F(2x2,3x3)
+int ssde_wgrad_wino_plan(const ssde_wgrad_args* a, ssde_wgrad_plan* pl);
+int ssde_wgrad_wino_launch(const ssde_wgrad_args* a, hipStream_t st);
 
 #define SSDE_REQUIRE(cond, ...)            \
   do {                                     \
@@ -97,6 +110,23 @@ static inline int ssde_src_check(const ssde_src& s, const char* route, const cha
   }
   SSDE_REQUIRE(!(checks & SSDE_SRC_SEED) || s.drop_thresh == 0 || s.drop_seed, "%s: %sdropout seed pointer missing", route, what);
   return SSDE_OK;
+}
+
+// ---- host helpers of the weight-gradient routes ---------------------------------------------------------------------
+// SSDE_WGRADF_* -> the Winograd forms a launch may take: 0 = none (_DIRECT), 2 = F(2x2,3x3) wherever legal (_F2), 44 = F(4x4,3x3)
+// wherever legal (_F4_FORCE, tests), 4 = F(4x4,3x3) where it is legal and pays, F(2x2,3x3) for the rest (no flag)
+static inline int ssde_wgrad_mode(const ssde_wgrad_args* a) {
+  return (a->flags & SSDE_WGRADF_DIRECT) ? 0 : (a->flags & SSDE_WGRADF_F2) ? 2 : (a->flags & SSDE_WGRADF_F4_FORCE) ? 44 : 4;
+}
+// What only a launch brings: the tensors every kernel dereferences
+static inline int ssde_wgrad_tensors_check(const ssde_wgrad_args* a, const char* route) {
+  SSDE_REQUIRE(a->g && a->dw, "%s: null tensors", route);
+  return ssde_src_check(a->src, route, "", 4, SSDE_SRC_ALL);
+}
+// Fewer, longer workgroups when scratch is short: the splits that fit (all that the plan asks for when they do; 0: not even one)
+static inline int ssde_wgrad_fit_splits(const ssde_wgrad_args* a, const ssde_wgrad_plan& pl) {
+  if (a->scratch_floats >= pl.fixed_floats + pl.split_floats * pl.splits) return pl.splits;
+  return a->scratch_floats < pl.fixed_floats ? 0 : (int)((a->scratch_floats - pl.fixed_floats) / pl.split_floats);
 }
 
 // Tiling of the Winograd kernels (conv_wino, conv_wino4, conv_wino4r): a workgroup owns `tiles` output tiles of edge x edge

@@ -19,6 +19,7 @@
 // conflict-free ds_read_b32 of 32 consecutive floats and the halo is re-used by all 9 taps.
 // dw is written in the REFERENCE layout (OIHW, or [in][out] for NIN with transpose_out).
 #include "ssde_common.h"
+#include <algorithm>
 #include <cstdlib>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -396,29 +397,117 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgParams p) {
   }
 }
 
-template <int KS, int CO_B, int CI_B>
-int launch(const WgParams& p, int lds_bytes, hipStream_t st) {
-  constexpr int BCO = 2 * CO_B * 32, BCI = 2 * CI_B * 32;
-  const int ntiles = p.co_tiles * p.ci_tiles;
-  if (int rc = ssde_launch_lds<wgrad_kernel<KS, CO_B, CI_B>>("wgrad", dim3(ssde_cdiv(p.splits, 8) * 8 * ntiles), dim3(kThreads), lds_bytes, st, p)) return rc;
-  if (p.splits > 1) {
-    const size_t total = (size_t)KS * KS * BCO * BCI * ntiles;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((wgrad_reduce_kernel<KS * KS, BCO, BCI>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    SSDE_LAUNCH_CHECK();
-  }
+// hipcc puts kernels into the code object in the order of their first mention: named here, whatever order the host code calls them in
+[[maybe_unused]] constexpr void (*kKernels[])(const WgParams) = {wgrad_kernel<3, 1, 1>, wgrad_reduce_kernel<9, 64, 64>,
+                                                                 wgrad_reduce_kernel<1, 128, 128>, wgrad_kernel<1, 2, 2>};
+
+// ---- host: the fields every kernel of this file reads; a workgroup owns edge x edge (output, input) channels ----
+void fill_params(const ssde_wgrad_args* a, int edge, WgParams& p) {
+  p = WgParams{};
+  p.src = a->src; p.g = a->g; p.g_ld = a->g_ld; p.g_off = a->g_off;
+  p.N = a->n; p.Hin = a->h_in; p.Win = a->w_in; p.Hout = a->h_out; p.Wout = a->w_out;
+  p.Cout = a->c_out; p.Ctot = a->src.c0 + a->src.c1; p.cin_store = a->cin_store;
+  p.stride = a->stride; p.pad = a->pad; p.transpose_out = a->transpose_out; p.scale = a->scale; p.dw = a->dw; p.scratch = a->scratch;
+  p.co_tiles = ssde_cdiv(a->c_out, edge); p.ci_tiles = ssde_cdiv(a->cin_store, edge);
+  p.rows = a->n * a->h_out * a->w_out;
+}
+
+// Both routes run one split without scratch: a short scratch costs them splits, never the launch
+int fit_or_one(const ssde_wgrad_args* a, const ssde_wgrad_plan& pl) { return std::max(1, ssde_wgrad_fit_splits(a, pl)); }
+
+template <int T, int BCO, int BCI>
+int launch_reduce(const WgParams& p, hipStream_t st) {
+  if (p.splits == 1) return SSDE_OK;
+  size_t blocks = ((size_t)T * BCO * BCI * p.co_tiles * p.ci_tiles + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL((wgrad_reduce_kernel<T, BCO, BCI>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+  SSDE_LAUNCH_CHECK();
   return SSDE_OK;
 }
 
-struct WgPlan { WgParams p; int lds; int64_t slab_floats; int pref_splits; };
-
-// 1x1 / NIN / Linear gradients go to wgrad1x1_gemm_kernel (SSDE_WGRADF_1X1_CHUNKED: the chunked kernel)
-bool pipelined_1x1(const ssde_wgrad_args* a) {
-  return a->ksize == 1 && !(a->flags & SSDE_WGRADF_1X1_CHUNKED);
+// ---- route: 1x1 / NIN / Linear gradients on wgrad1x1_gemm_kernel (SSDE_WGRADF_1X1_CHUNKED: left to the chunked kernel) ----
+bool gemm1x1_wants(const ssde_wgrad_args* a) { return a->ksize == 1 && !(a->flags & SSDE_WGRADF_1X1_CHUNKED); }
+int gemm1x1_plan_params(const ssde_wgrad_args* a, WgParams& p, ssde_wgrad_plan* pl) {
+  fill_params(a, 128, p);
+  const int ntiles = p.co_tiles * p.ci_tiles;
+  pl->fixed_floats = 0; pl->split_floats = (int64_t)128 * 128 * ntiles;
+  // ~768 workgroups (3 of the 4 a CU holds: the sweep in profiles/r3_wgrad1x1_ab.txt peaks at 768-1024 for every shape of the
+  // CIFAR network), at least 8 stages of 16 pixels each
+  const int stages = ssde_cdiv(p.rows, kG1BK);
+  int sp = ssde_cdiv(768, ntiles);
+  if (sp > stages / 8) sp = stages / 8;
+  if (sp < 1) sp = 1;
+  pl->scratch_floats = sp > 1 ? pl->split_floats * sp : 0;
+  if (a->splits > 0) sp = a->splits;
+  if (sp > stages) sp = stages;
+  pl->splits = sp;
+  return SSDE_OK;
+}
+int gemm1x1_plan(const ssde_wgrad_args* a, ssde_wgrad_plan* pl) { WgParams p; return gemm1x1_plan_params(a, p, pl); }
+int gemm1x1_launch(const ssde_wgrad_args* a, hipStream_t st) {
+  WgParams p; ssde_wgrad_plan pl;
+  if (int rc = gemm1x1_plan_params(a, p, &pl)) return rc;
+  if (int rc = ssde_wgrad_tensors_check(a, "wgrad")) return rc;
+  p.rows_per_split = ssde_cdiv(ssde_cdiv(p.rows, kG1BK), fit_or_one(a, pl)) * kG1BK;
+  p.splits = ssde_cdiv(p.rows, p.rows_per_split);
+  SSDE_REQUIRE(p.splits == 1 || a->scratch, "wgrad: scratch missing");
+  hipLaunchKernelGGL(wgrad1x1_gemm_kernel, dim3(ssde_cdiv(p.splits, 8) * 8 * p.co_tiles * p.ci_tiles), dim3(kThreads), 2 * kG1Stage * 4, st, p);
+  SSDE_LAUNCH_CHECK();
+  return launch_reduce<1, 128, 128>(p, st);
 }
 
-int make_plan(const ssde_wgrad_args* a, WgPlan* pl) {
+// ---- route: the chunked kernel, 3x3 and 1x1: whatever is left ----
+int chunked_plan_params(const ssde_wgrad_args* a, WgParams& p, int& lds, ssde_wgrad_plan* pl) {
+  const int ks = a->ksize, edge = ks == 3 ? 64 : 128;
+  fill_params(a, edge, p);
+  const int hw = a->h_out * a->w_out;
+  int px;
+  if (ks == 1) px = 64;
+  else if (a->stride == 2) px = 32;
+  else px = hw >= 128 ? 128 : 64;
+  const int tw = ssde_pow2_floor(a->w_out < 16 ? a->w_out : 16);
+  int th = px / tw; if (th > a->h_out) th = a->h_out;
+  th = ssde_pow2_floor(th);
+  const int imgs = px / (tw * th);
+  p.lTW = ssde_ilog2(tw); p.lTH = ssde_ilog2(th); p.lPX = ssde_ilog2(px);
+  p.tiles_x = ssde_cdiv(a->w_out, tw);
+  p.tiles_per_img = p.tiles_x * ssde_cdiv(a->h_out, th);
+  p.chunks = ssde_cdiv(a->n, imgs) * p.tiles_per_img;
+  const int ntiles = p.co_tiles * p.ci_tiles;
+  pl->fixed_floats = 0; pl->split_floats = (int64_t)ks * ks * edge * edge * ntiles;
+  // ~2 workgroups per CU; a split costs one slab write + read, so keep >= 2 chunks per workgroup
+  int splits = ssde_cdiv(512, ntiles);
+  const int max_splits = p.chunks >= 2 ? p.chunks / 2 : 1;
+  if (splits > max_splits) splits = max_splits;
+  if (splits < 1) splits = 1;
+  pl->scratch_floats = splits > 1 ? pl->split_floats * splits : 0;
+  if (a->splits > 0) splits = a->splits;
+  if (splits > p.chunks) splits = p.chunks;
+  pl->splits = splits;
+  const int halo = imgs * ((th - 1) * a->stride + ks) * ((tw - 1) * a->stride + ks);
+  lds = (px * edge + halo * edge) * 4;
+  SSDE_REQUIRE(lds <= 160 * 1024, "wgrad: %d bytes of LDS needed", lds);
+  return SSDE_OK;
+}
+int chunked_plan(const ssde_wgrad_args* a, ssde_wgrad_plan* pl) { WgParams p; int lds; return chunked_plan_params(a, p, lds, pl); }
+template <int KS, int CO_B, int CI_B>
+int chunked_enqueue(const WgParams& p, int lds_bytes, hipStream_t st) {
+  const dim3 grid(ssde_cdiv(p.splits, 8) * 8 * p.co_tiles * p.ci_tiles);
+  if (int rc = ssde_launch_lds<wgrad_kernel<KS, CO_B, CI_B>>("wgrad", grid, dim3(kThreads), lds_bytes, st, p)) return rc;
+  return launch_reduce<KS * KS, 2 * CO_B * 32, 2 * CI_B * 32>(p, st);
+}
+int chunked_launch(const ssde_wgrad_args* a, hipStream_t st) {
+  WgParams p; int lds; ssde_wgrad_plan pl;
+  if (int rc = chunked_plan_params(a, p, lds, &pl)) return rc;
+  if (int rc = ssde_wgrad_tensors_check(a, "wgrad")) return rc;
+  p.chunks_per_split = ssde_cdiv(p.chunks, fit_or_one(a, pl));
+  p.splits = ssde_cdiv(p.chunks, p.chunks_per_split);
+  SSDE_REQUIRE(p.splits == 1 || a->scratch, "wgrad: scratch missing");
+  return a->ksize == 3 ? chunked_enqueue<3, 1, 1>(p, lds, st) : chunked_enqueue<1, 2, 2>(p, lds, st);
+}
+
+// ---- what every route asks of the arguments, checked once in front of the table ----
+int wgrad_args_check(const ssde_wgrad_args* a) {
   SSDE_REQUIRE(a && a->ksize != 0, "wgrad: null args");
   SSDE_REQUIRE(a->ksize == 3 || a->ksize == 1, "wgrad: ksize must be 1 or 3");
   SSDE_REQUIRE(a->stride == 1 || a->stride == 2, "wgrad: stride must be 1 or 2");
@@ -440,103 +529,35 @@ int make_plan(const ssde_wgrad_args* a, WgPlan* pl) {
   }
   if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU)
     SSDE_REQUIRE(s.gn_groups > 0 && Ctot % s.gn_groups == 0 && (Ctot / s.gn_groups) % 4 == 0, "wgrad: GroupNorm channels-per-group %% 4");
-  WgParams& p = pl->p;
-  p.src = s; p.g = a->g; p.g_ld = a->g_ld; p.g_off = a->g_off;
-  p.N = a->n; p.Hin = a->h_in; p.Win = a->w_in; p.Hout = a->h_out; p.Wout = a->w_out;
-  p.Cout = a->c_out; p.Ctot = Ctot; p.cin_store = a->cin_store;
-  p.stride = a->stride; p.pad = a->pad; p.transpose_out = a->transpose_out; p.scale = a->scale; p.dw = a->dw;
-  p.scratch = a->scratch;
-  const int hw = a->h_out * a->w_out;
-  int px;
-  if (a->ksize == 1) px = 64;
-  else if (a->stride == 2) px = 32;
-  else px = hw >= 128 ? 128 : 64;
-  const int tw = ssde_pow2_floor(a->w_out < 16 ? a->w_out : 16);
-  int th = px / tw; if (th > a->h_out) th = a->h_out;
-  th = ssde_pow2_floor(th);
-  const int imgs = px / (tw * th);
-  p.lTW = ssde_ilog2(tw); p.lTH = ssde_ilog2(th); p.lPX = ssde_ilog2(px);
-  p.tiles_x = ssde_cdiv(a->w_out, tw);
-  p.tiles_per_img = p.tiles_x * ssde_cdiv(a->h_out, th);
-  p.chunks = ssde_cdiv(a->n, imgs) * p.tiles_per_img;
-  const int bco = a->ksize == 3 ? 64 : 128, bci = bco;
-  p.co_tiles = ssde_cdiv(a->c_out, bco);
-  p.ci_tiles = ssde_cdiv(a->cin_store, bci);
-  const int ntiles = p.co_tiles * p.ci_tiles;
-  pl->slab_floats = (int64_t)a->ksize * a->ksize * bco * bci * ntiles;
-  // ~2 workgroups per CU; a split costs one slab write + read, so keep >= 2 chunks per workgroup
-  int splits = ssde_cdiv(512, ntiles);
-  const int max_splits = p.chunks >= 2 ? p.chunks / 2 : 1;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  pl->pref_splits = splits;
-  if (a->splits > 0) splits = a->splits;
-  if (splits > p.chunks) splits = p.chunks;
-  if (splits > 1 && a->scratch_floats < pl->slab_floats * splits) {
-    splits = (int)(a->scratch_floats / pl->slab_floats);     // fewer, longer workgroups when scratch is short
-    if (splits < 1) splits = 1;
-  }
-  p.chunks_per_split = ssde_cdiv(p.chunks, splits);
-  p.splits = ssde_cdiv(p.chunks, p.chunks_per_split);
-  p.rows = a->n * hw;
-  p.rows_per_split = 0;
-  if (pipelined_1x1(a)) {
-    // the pipelined GEMM: ~768 workgroups (3 of the 4 a CU holds: the sweep in profiles/r3_wgrad1x1_ab.txt peaks at
-    // 768-1024 for every shape of the CIFAR network), at least 8 stages of 16 pixels each
-    const int stages = ssde_cdiv(p.rows, kG1BK);
-    int sp = ssde_cdiv(768, ntiles);
-    if (sp > stages / 8) sp = stages / 8;
-    if (sp < 1) sp = 1;
-    pl->pref_splits = sp;
-    if (a->splits > 0) sp = a->splits;
-    if (sp > stages) sp = stages;
-    if (sp > 1 && a->scratch_floats < pl->slab_floats * sp) { sp = (int)(a->scratch_floats / pl->slab_floats); if (sp < 1) sp = 1; }
-    p.rows_per_split = ssde_cdiv(stages, sp) * kG1BK;
-    p.splits = ssde_cdiv(p.rows, p.rows_per_split);
-  }
-  const int ks = a->ksize;
-  const int halo = imgs * ((th - 1) * a->stride + ks) * ((tw - 1) * a->stride + ks);
-  pl->lds = (px * bco + halo * bci) * 4;
-  SSDE_REQUIRE(pl->lds <= 160 * 1024, "wgrad: %d bytes of LDS needed", pl->lds);
   return SSDE_OK;
+}
+
+// ---- the table: the first route that wants a launch gets it ----
+const ssde_wgrad_route kRoutes[] = {
+    {"f4", ssde_wgrad_wino4_wants, ssde_wgrad_wino4_plan, ssde_wgrad_wino4_launch},      // wgrad_wino4.hip
+    {"f2", ssde_wgrad_wino_wants, ssde_wgrad_wino_plan, ssde_wgrad_wino_launch},         // wgrad_wino.hip
+    {"1x1", gemm1x1_wants, gemm1x1_plan, gemm1x1_launch},
+    {"direct", [](const ssde_wgrad_args*) { return true; }, chunked_plan, chunked_launch},
+};
+const ssde_wgrad_route* route_of(const ssde_wgrad_args* a) {
+  if (wgrad_args_check(a)) return nullptr;           // (error set)
+  const ssde_wgrad_route* r = kRoutes;
+  while (!r->wants(a)) ++r;                      // (the last row wants everything)
+  return r;
 }
 
 }  // namespace
 
-extern "C" int ssde_wgrad_wants_winograd4(const ssde_wgrad_args* a) { return a && ssde_wgrad_wino4_wants(a) ? 1 : 0; }
+extern "C" int ssde_wgrad_wants_winograd4(const ssde_wgrad_args* a) { return route_of(a) == kRoutes ? 1 : 0; }     // (the first row)
 
 extern "C" int64_t ssde_wgrad_scratch_floats(const ssde_wgrad_args* a) {
-  if (a && ssde_wgrad_wino4_wants(a)) return ssde_wgrad_wino4_scratch_floats(a);    // Winograd F(4x4,3x3): wgrad_wino4.hip
-  if (a && ssde_wgrad_wino_wants(a)) return ssde_wgrad_wino_scratch_floats(a);      // Winograd F(2x2,3x3): wgrad_wino.hip
-  WgPlan pl;
-  if (int rc = make_plan(a, &pl)) return rc;
-  return pl.pref_splits > 1 ? pl.slab_floats * pl.pref_splits : 0;
+  const ssde_wgrad_route* r = route_of(a);
+  ssde_wgrad_plan pl;
+  if (int rc = r ? r->plan(a, &pl) : SSDE_EINVAL) return rc;
+  return pl.scratch_floats;
 }
 
 extern "C" int ssde_conv_wgrad(const ssde_wgrad_args* a, void* stream) {
-  if (a && ssde_wgrad_wino4_wants(a)) return ssde_wgrad_wino4_launch(a, stream);
-  if (a && ssde_wgrad_wino_wants(a)) return ssde_wgrad_wino_launch(a, stream);
-  WgPlan pl;
-  if (int rc = make_plan(a, &pl)) return rc;
-  const ssde_src& s = a->src;
-  SSDE_REQUIRE(a->g && a->dw && s.p0 && (s.c1 == 0 || s.p1), "wgrad: null tensors");
-  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU)
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "wgrad: GroupNorm pointers missing");
-  SSDE_REQUIRE(s.drop_thresh == 0 || s.drop_seed, "wgrad: dropout seed pointer missing");
-  SSDE_REQUIRE(pl.p.splits == 1 || a->scratch, "wgrad: scratch missing");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (a->ksize == 3) return launch<3, 1, 1>(pl.p, pl.lds, st);
-  if (pl.p.rows_per_split > 0) {
-    const int ntiles = pl.p.co_tiles * pl.p.ci_tiles;
-    hipLaunchKernelGGL(wgrad1x1_gemm_kernel, dim3(ssde_cdiv(pl.p.splits, 8) * 8 * ntiles), dim3(kThreads), 2 * kG1Stage * 4, st, pl.p);
-    SSDE_LAUNCH_CHECK();
-    if (pl.p.splits > 1) {
-      size_t blocks = ((size_t)128 * 128 * ntiles + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL((wgrad_reduce_kernel<1, 128, 128>), dim3((unsigned)blocks), dim3(256), 0, st, pl.p);
-      SSDE_LAUNCH_CHECK();
-    }
-    return SSDE_OK;
-  }
-  return launch<1, 2, 2>(pl.p, pl.lds, st);
+  const ssde_wgrad_route* r = route_of(a);
+  return r ? r->launch(a, static_cast<hipStream_t>(stream)) : SSDE_EINVAL;
 }

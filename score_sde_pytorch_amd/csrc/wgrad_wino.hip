@@ -347,74 +347,59 @@ __global__ __launch_bounds__(256) void wgrad_wino_reduce_kernel(const WwParams p
   }
 }
 
-bool winograd_enabled(const ssde_wgrad_args* a) { return !(a->flags & SSDE_WGRADF_DIRECT); }
-
 }  // namespace
 
-// ssde_conv_wgrad / ssde_wgrad_scratch_floats (wgrad.hip) route eligible launches here.
+// ---- route: F(2x2,3x3) wherever it is legal, unless SSDE_WGRADF_DIRECT (asked after F(4x4,3x3), wgrad_wino4.hip) ----
 bool ssde_wgrad_wino_wants(const ssde_wgrad_args* a) {
-  if (!winograd_enabled(a) || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->pad_end != 0 || a->transpose_out) return false;
+  if (ssde_wgrad_mode(a) == 0 || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->pad_end != 0) return false;
   if (a->h_in != a->h_out || a->w_in != a->w_out || a->h_out % 4 != 0 || a->w_out % 8 != 0) return false;
   const ssde_src& s = a->src;
   const int Ctot = s.c0 + s.c1;
   if (a->c_out % 64 != 0 || Ctot % 64 != 0 || a->cin_store != Ctot || (s.c1 > 0 && s.c0 % 64 != 0)) return false;
-  if (a->g_ld % 4 != 0 || a->g_off % 4 != 0) return false;
   return (long long)a->n * a->h_out * a->w_out < (1ll << 30);
 }
 
-static int ww_plan(const ssde_wgrad_args* a, WwParams* p) {
+static void set_splits(WwParams* p, int splits) {
+  if (splits > p->chunks) splits = p->chunks;
+  if (splits < 1) splits = 1;
+  p->chunks_per_split = ssde_cdiv(p->chunks, splits);
+  p->splits = ssde_cdiv(p->chunks, p->chunks_per_split);
+}
+
+static int plan_params(const ssde_wgrad_args* a, WwParams* p, ssde_wgrad_plan* pl) {
   const ssde_src& s = a->src;
   p->src = s; p->g = a->g; p->g_ld = a->g_ld; p->g_off = a->g_off;
   p->N = a->n; p->H = a->h_out; p->W = a->w_out; p->Cout = a->c_out; p->Ctot = s.c0 + s.c1;
   p->cx = a->w_out / 8; p->cy = a->h_out / 4;
   p->chunks = a->n * p->cx * p->cy;
   p->co_tiles = a->c_out / 64; p->ci_tiles = p->Ctot / 64;
+  p->scale = a->scale; p->dw = a->dw; p->scratch = a->scratch;
   const int ntiles = p->co_tiles * p->ci_tiles;
+  pl->fixed_floats = 0; pl->split_floats = (int64_t)ntiles * kSlab;      // (one split writes its slab too: the reduction applies G^T . G)
   // one workgroup fills a CU (155 KB of LDS): aim at ONE round of at most 256 workgroups (257 would take as long as
   // 512), with at least 4 stages each
   int splits = 256 / ntiles;
   const int max_splits = p->chunks >= 4 ? p->chunks / 4 : 1;
   if (splits > max_splits) splits = max_splits;
-  if (a->splits > 0) splits = a->splits;
-  if (splits > p->chunks) splits = p->chunks;
-  if (splits < 1) splits = 1;
-  p->chunks_per_split = ssde_cdiv(p->chunks, splits);
-  p->splits = ssde_cdiv(p->chunks, p->chunks_per_split);
-  p->scale = a->scale; p->dw = a->dw; p->scratch = a->scratch;
+  set_splits(p, splits);
+  pl->scratch_floats = pl->split_floats * p->splits;
+  if (a->splits > 0) set_splits(p, a->splits);
+  pl->splits = p->splits;
   return SSDE_OK;
 }
+int ssde_wgrad_wino_plan(const ssde_wgrad_args* a, ssde_wgrad_plan* pl) { WwParams p; return plan_params(a, &p, pl); }
 
-int64_t ssde_wgrad_wino_scratch_floats(const ssde_wgrad_args* a) {
-  WwParams p;
-  ssde_wgrad_args b = *a;
-  b.splits = 0;
-  ww_plan(&b, &p);
-  return (int64_t)p.splits * p.co_tiles * p.ci_tiles * kSlab;
-}
-
-int ssde_wgrad_wino_launch(const ssde_wgrad_args* a, void* stream) {
-  const ssde_src& s = a->src;
-  SSDE_REQUIRE(a->g && a->dw && s.p0 && (s.c1 == 0 || s.p1), "wgrad(winograd): null tensors");
-  const bool gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
-  if (gn) {
-    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0 && ((s.c0 + s.c1) / s.gn_groups) % 4 == 0,
-                 "wgrad(winograd): GroupNorm channels-per-group %% 4");
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "wgrad(winograd): GroupNorm pointers missing");
-  }
-  SSDE_REQUIRE(s.drop_thresh == 0 || s.drop_seed, "wgrad(winograd): dropout seed pointer missing");
-  WwParams p;
-  ww_plan(a, &p);
-  const int64_t need = (int64_t)p.splits * p.co_tiles * p.ci_tiles * kSlab;
-  if (a->scratch_floats < need) {          // fewer, longer workgroups when scratch is short
-    const int fit = (int)(a->scratch_floats / ((int64_t)p.co_tiles * p.ci_tiles * kSlab));
-    SSDE_REQUIRE(fit >= 1 && a->scratch, "wgrad(winograd): scratch of %lld floats needed at least", (long long)p.co_tiles * p.ci_tiles * kSlab);
-    p.chunks_per_split = ssde_cdiv(p.chunks, fit);
-    p.splits = ssde_cdiv(p.chunks, p.chunks_per_split);
-  }
+int ssde_wgrad_wino_launch(const ssde_wgrad_args* a, hipStream_t st) {
+  WwParams p; ssde_wgrad_plan pl;
+  if (int rc = plan_params(a, &p, &pl)) return rc;
+  if (int rc = ssde_wgrad_tensors_check(a, "wgrad(winograd)")) return rc;
+  const int fit = ssde_wgrad_fit_splits(a, pl);
+  SSDE_REQUIRE(fit >= 1, "wgrad(winograd): scratch of %lld floats needed at least", (long long)pl.split_floats);
   SSDE_REQUIRE(a->scratch, "wgrad(winograd): scratch missing");
+  if (fit < p.splits) set_splits(&p, fit);
+  const bool gn = a->src.pro_mode == SSDE_PRO_GN || a->src.pro_mode == SSDE_PRO_GN_SILU;
   constexpr int lds = (4 * kStageFloats + kRawX + kRawG) * 4;
   using Both = ssde_lds_kernels<wgrad_wino_kernel<false>, wgrad_wino_kernel<true>>;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const int ntiles = p.co_tiles * p.ci_tiles;
   const dim3 grid(ssde_cdiv(p.splits * ntiles, 8) * 8);
   if (int rc = gn ? ssde_launch_lds<wgrad_wino_kernel<true>, Both>("wgrad(winograd)", grid, dim3(kThreads), lds, st, p)
@@ -426,3 +411,4 @@ int ssde_wgrad_wino_launch(const ssde_wgrad_args* a, void* stream) {
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
 }
+

@@ -468,20 +468,43 @@ __global__ __launch_bounds__(256) void wgrad4_reduce_kernel(const W4Params p) {
   }
 }
 
-// ssde_wgrad_args.flags: SSDE_WGRADF_DIRECT = direct kernel everywhere (0), SSDE_WGRADF_F2 = F(2x2,3x3) wherever legal (2),
-// SSDE_WGRADF_F4_FORCE = F(4x4,3x3) wherever legal (44, tests), none = F(4x4,3x3) where it is legal and pays, F(2x2,3x3) for
-// the rest (4)
-int mode(const ssde_wgrad_args* a) {
-  return (a->flags & SSDE_WGRADF_DIRECT) ? 0 : (a->flags & SSDE_WGRADF_F2) ? 2 : (a->flags & SSDE_WGRADF_F4_FORCE) ? 44 : 4;
+}  // namespace
+
+// ---- route: F(4x4,3x3) where it is legal and pays (SSDE_WGRADF_F4_FORCE: wherever it is legal); asked first ----
+bool ssde_wgrad_wino4_wants(const ssde_wgrad_args* a) {
+  const int m = ssde_wgrad_mode(a);
+  if ((m != 4 && m != 44) || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->pad_end != 0) return false;
+  if (a->h_in != a->h_out || a->w_in != a->w_out || a->h_out % 4 != 0 || a->w_out % 4 != 0 || a->h_out < 8 || a->w_out < 8) return false;
+  const int Ctot = a->src.c0 + a->src.c1;
+  if (a->c_out % 32 != 0 || Ctot % 32 != 0 || a->cin_store != Ctot) return false;
+  const long long T = (long long)a->n * (a->h_out / 4) * (a->w_out / 4);
+  // where it pays (profiles/r3_wgrad_wino4_ab.txt, batch 128): from 16x16 maps up when a channel count exceeds 128, 128 -> 128
+  // from 8192 tiles (32x32 maps at batch 128: +3-4 % since the transforms move two channels per thread), and on 8x8 maps from
+  // 512 input channels; the rest stays on the fused F(2x2,3x3) kernel
+  if (m == 4 && !((T >= 1024 && (Ctot > 128 || a->c_out > 128)) || T >= 8192 || (T >= 512 && Ctot >= 512))) return false;
+  return (long long)a->n * a->h_out * a->w_out < (1ll << 30) && T * (Ctot > a->c_out ? Ctot : a->c_out) * kPos < (1ll << 40);
 }
 
-void plan(const ssde_wgrad_args* a, W4Params* p) {
+// the plain split over K: `splits` ranges of whole stages
+static void set_splits(W4Params* p, int splits) {
+  if (splits < 1) splits = 1;
+  p->k_per_split = ssde_cdiv(ssde_cdiv(p->T, splits), BK) * BK;
+  p->splits = ssde_cdiv(p->T, p->k_per_split);
+  p->sk_on = 0;
+}
+
+static int plan_params(const ssde_wgrad_args* a, W4Params* p, ssde_wgrad_plan* pl) {
   const ssde_src& s = a->src;
+  *p = W4Params{};
   p->src = s; p->g = a->g; p->g_ld = a->g_ld; p->g_off = a->g_off;
   p->N = a->n; p->H = a->h_out; p->W = a->w_out; p->Cout = a->c_out; p->Ctot = s.c0 + s.c1;
   p->tx = a->w_out / 4; p->ty = a->h_out / 4;
   p->T = a->n * p->tx * p->ty;
   p->co_tiles = ssde_cdiv(a->c_out, BM); p->ci_tiles = ssde_cdiv(p->Ctot, BN);
+  p->scale = a->scale; p->dw = a->dw;
+  p->xcd_order = !(a->flags & SSDE_WGRADF_NO_XCD_ORDER);
+  pl->fixed_floats = (int64_t)kPos * p->T * (p->Ctot + p->Cout);      // the transformed operands V and Z
+  pl->split_floats = (int64_t)kPos * p->Cout * p->Ctot;
   // four workgroups share a CU: aim at 768 of them, at least 32 stages (512 tiles) each; every
   // split costs a slab of 36 x Cout x Cin floats that the reduction reads back.  (The K loop itself runs near the MFMA bound --
   // 6.4 k cycles per 16-tile stage with three workgroups on the CU, tools/wgrad4_trace.py -- and what a launch loses is
@@ -494,123 +517,62 @@ void plan(const ssde_wgrad_args* a, W4Params* p) {
   int splits = (target + blocks / 2) / blocks;
   const int max_splits = p->T / 512;
   if (splits > max_splits) splits = max_splits;
-  if (a->splits > 0) splits = a->splits;
-  if (splits < 1) splits = 1;
-  p->k_per_split = ssde_cdiv(ssde_cdiv(p->T, splits), BK) * BK;
-  p->splits = ssde_cdiv(p->T, p->k_per_split);
-  p->sk_on = 0; p->sk_per = p->sk_S = p->sk_groups = 0;
-  {
-    if (!(a->flags & SSDE_WGRADF_NO_STREAMK) && a->splits <= 0) {      // (default on; the flag: the plain split, for A/B runs and tests)
-      // three workgroups per CU are what the kernel's registers and LDS keep resident beside each other at full rate
-      const int ntiles = p->co_tiles * p->ci_tiles;
-      const int S = ssde_cdiv(p->T, BK), total = kPos * S;
-      int groups = 3 * ssde_num_cus() / ntiles;
-      if (groups < 1) groups = 1;
-      int per = ssde_cdiv(total, groups);
-      if (per < 8) per = 8;                        // (at least 8 stages per run)
-      if (per < S || groups >= kPos) {             // otherwise whole positions per group: the plain form with one split
-        p->sk_on = 1; p->sk_per = per; p->sk_S = S; p->sk_groups = ssde_cdiv(total, per);
-        p->splits = ssde_cdiv(S, per) + 1;         // the most slots a position can have
-      }
+  set_splits(p, splits);
+  if (!(a->flags & SSDE_WGRADF_NO_STREAMK)) {      // (default on; the flag: the plain split, for A/B runs and tests)
+    // Stream-K: three workgroups per CU are what the kernel's registers and LDS keep resident beside each other at full rate
+    const int ntiles = p->co_tiles * p->ci_tiles;
+    const int S = ssde_cdiv(p->T, BK), total = kPos * S;
+    int groups = 3 * ssde_num_cus() / ntiles;
+    if (groups < 1) groups = 1;
+    int per = ssde_cdiv(total, groups);
+    if (per < 8) per = 8;                          // (at least 8 stages per run)
+    if (per < S || groups >= kPos) {               // otherwise whole positions per group: the plain form with one split
+      p->sk_on = 1; p->sk_per = per; p->sk_S = S; p->sk_groups = ssde_cdiv(total, per);
+      p->splits = ssde_cdiv(S, per) + 1;           // the most slots a position can have
     }
   }
-  p->scale = a->scale; p->dw = a->dw;
-  p->xcd_order = !(a->flags & SSDE_WGRADF_NO_XCD_ORDER);
+  pl->scratch_floats = pl->fixed_floats + pl->split_floats * p->splits;
+  if (a->splits > 0) set_splits(p, a->splits);     // an explicit split is a plain one
+  pl->splits = p->splits;
+  return SSDE_OK;
 }
+int ssde_wgrad_wino4_plan(const ssde_wgrad_args* a, ssde_wgrad_plan* pl) { W4Params p; return plan_params(a, &p, pl); }
 
-int64_t scratch_floats(const W4Params& p) {
-  return (int64_t)kPos * p.T * (p.Ctot + p.Cout) + (int64_t)p.splits * kPos * p.Cout * p.Ctot;
-}
+static unsigned grid_for(long long total) { const long long b = (total + 255) / 256; return (unsigned)(b > 256 * 32 ? 256 * 32 : (b < 1 ? 1 : b)); }
 
-}  // namespace
-
-// ssde_conv_wgrad / ssde_wgrad_scratch_floats (wgrad.hip) route eligible launches here, before wgrad_wino.hip
-bool ssde_wgrad_wino4_wants(const ssde_wgrad_args* a) {
-  const int m = mode(a);
-  if ((m != 4 && m != 44) || a->ksize != 3 || a->stride != 1 || a->pad != 1 || a->pad_end != 0 || a->transpose_out) return false;
-  if (a->h_in != a->h_out || a->w_in != a->w_out || a->h_out % 4 != 0 || a->w_out % 4 != 0 || a->h_out < 8 || a->w_out < 8) return false;
-  const ssde_src& s = a->src;
-  const int Ctot = s.c0 + s.c1;
-  if (a->c_out % 32 != 0 || Ctot % 32 != 0 || a->cin_store != Ctot) return false;
-  if (a->g_ld % 4 != 0 || a->g_off % 4 != 0 || s.c0 % 4 != 0 || s.c1 % 4 != 0) return false;
-  // what wgrad.hip's make_plan would have checked had it been asked first: the transforms read one (mean, rstd) per channel
-  // quad, and the gradient block must lie inside a row of the parameter's gradient
-  if (a->g_off + a->c_out > a->g_ld) return false;
-  if ((s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) &&
-      (s.gn_groups <= 0 || Ctot % s.gn_groups != 0 || (Ctot / s.gn_groups) % 4 != 0)) return false;
-  const long long T = (long long)a->n * (a->h_out / 4) * (a->w_out / 4);
-  // where it pays (profiles/r3_wgrad_wino4_ab.txt, batch 128): from 16x16 maps up when a channel count exceeds 128, 128 -> 128
-  // from 8192 tiles (32x32 maps at batch 128: +3-4 % since the transforms move two channels per thread), and on 8x8 maps from
-  // 512 input channels; the rest stays on the fused F(2x2,3x3) kernel
-  if (m == 4 && !((T >= 1024 && (Ctot > 128 || a->c_out > 128)) || T >= 8192 || (T >= 512 && Ctot >= 512))) return false;
-  return (long long)a->n * a->h_out * a->w_out < (1ll << 30) && T * (Ctot > a->c_out ? Ctot : a->c_out) * kPos < (1ll << 40);
-}
-
-int64_t ssde_wgrad_wino4_scratch_floats(const ssde_wgrad_args* a) {
-  W4Params p;
-  ssde_wgrad_args b = *a;
-  b.splits = 0;
-  plan(&b, &p);
-  return scratch_floats(p);
-}
-
-int ssde_wgrad_wino4_launch(const ssde_wgrad_args* a, void* stream) {
-  const ssde_src& s = a->src;
-  SSDE_REQUIRE(a->g && a->dw && s.p0 && (s.c1 == 0 || s.p1), "wgrad(winograd 4x4): null tensors");
-  const bool gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
-  if (gn) {
-    SSDE_REQUIRE(s.gn_groups > 0 && (s.c0 + s.c1) % s.gn_groups == 0, "wgrad(winograd 4x4): GroupNorm groups");
-    SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "wgrad(winograd 4x4): GroupNorm pointers missing");
-  }
-  SSDE_REQUIRE(s.drop_thresh == 0 || s.drop_seed, "wgrad(winograd 4x4): dropout seed pointer missing");
-  W4Params p;
-  plan(a, &p);
-  if (a->scratch_floats < scratch_floats(p)) {          // fewer splits when scratch is short (the operands must fit)
-    const int64_t left = a->scratch_floats - (int64_t)kPos * p.T * (p.Ctot + p.Cout);
-    const int fit = (int)(left / ((int64_t)kPos * p.Cout * p.Ctot));
-    SSDE_REQUIRE(fit >= 1 && a->scratch, "wgrad(winograd 4x4): scratch of %lld floats needed at least",
-                 (long long)kPos * p.T * (p.Ctot + p.Cout) + (long long)kPos * p.Cout * p.Ctot);
-    p.k_per_split = ssde_cdiv(ssde_cdiv(p.T, fit), BK) * BK;
-    p.splits = ssde_cdiv(p.T, p.k_per_split);
-    p.sk_on = 0;
-  }
+int ssde_wgrad_wino4_launch(const ssde_wgrad_args* a, hipStream_t st) {
+  W4Params p; ssde_wgrad_plan pl;
+  if (int rc = plan_params(a, &p, &pl)) return rc;
+  if (int rc = ssde_wgrad_tensors_check(a, "wgrad(winograd 4x4)")) return rc;
+  // fewer splits when scratch is short (the operands must fit), and never stream-K
+  const int fit = ssde_wgrad_fit_splits(a, pl);
+  SSDE_REQUIRE(fit >= 1, "wgrad(winograd 4x4): scratch of %lld floats needed at least", (long long)(pl.fixed_floats + pl.split_floats));
   SSDE_REQUIRE(a->scratch, "wgrad(winograd 4x4): scratch missing");
-  // v_pre: the forward launch of this layer left V behind (conv_wino4.hip, kEmitV): no input-transform pass here
+  if (fit < p.splits) set_splits(&p, fit);
+  // scratch = V, Z, slabs.  v_pre: the forward launch of this layer left V behind (conv_wino4.hip, kEmitV): no input-transform pass here
   const bool have_v = a->v_pre != nullptr;
-  p.V = have_v ? const_cast<float*>(a->v_pre) : a->scratch;
   p.v_quads = have_v ? 1 : 0;
-  if (have_v) {
-    p.Z = a->scratch;
-    p.slabs = p.Z + (size_t)kPos * p.T * p.Cout;
-  } else {
-  p.Z = p.V + (size_t)kPos * p.T * p.Ctot;
+  p.V = have_v ? const_cast<float*>(a->v_pre) : a->scratch;
+  p.Z = a->scratch + (have_v ? 0 : (size_t)kPos * p.T * p.Ctot);
   p.slabs = p.Z + (size_t)kPos * p.T * p.Cout;
+  // the transforms: two channels per thread where every operand allows 8-byte accesses
+  using Kernel = void (*)(const W4Params);
+  struct Xforms { Kernel v_gn, v_plain, z; };
+  static const Xforms xforms[2] = {{wino4_xform_v_kernel<true, 2>, wino4_xform_v_kernel<false, 2>, wino4_xform_z_kernel<2>},
+                                   {wino4_xform_v_kernel<true, 1>, wino4_xform_v_kernel<false, 1>, wino4_xform_z_kernel<1>}};
+  const ssde_src& s = a->src;
+  const bool gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
+  const bool v2 = !(a->flags & SSDE_WGRADF_XVEC1) && p.Ctot % 2 == 0 && p.Cout % 2 == 0 && s.c0 % 2 == 0 && p.g_ld % 2 == 0 && p.g_off % 2 == 0;
+  const Xforms& xf = xforms[v2 ? 0 : 1];
+  if (!have_v) {
+    hipLaunchKernelGGL((gn ? xf.v_gn : xf.v_plain), dim3(grid_for((long long)p.T * p.Ctot / (v2 ? 2 : 1))), dim3(256), 0, st, p);
+    SSDE_LAUNCH_CHECK();
   }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  auto grid_for = [](long long total) { long long b = (total + 255) / 256; return (unsigned)(b > 256 * 32 ? 256 * 32 : (b < 1 ? 1 : b)); };
-  const int xvec = (a->flags & SSDE_WGRADF_XVEC1) ? 1 : 2;      // channels per transform thread
-  const bool v2 = xvec == 2 && p.Ctot % 2 == 0 && p.Cout % 2 == 0 && s.c0 % 2 == 0 && p.g_ld % 2 == 0 && p.g_off % 2 == 0;
-  const dim3 gv(grid_for((long long)p.T * p.Ctot / (v2 ? 2 : 1))), gz(grid_for((long long)p.T * p.Cout / (v2 ? 2 : 1)));
-  if (v2) {
-    if (!have_v) {
-      if (gn) hipLaunchKernelGGL((wino4_xform_v_kernel<true, 2>), gv, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((wino4_xform_v_kernel<false, 2>), gv, dim3(256), 0, st, p);
-      SSDE_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(wino4_xform_z_kernel<2>, gz, dim3(256), 0, st, p);
-  } else {
-    if (!have_v) {
-      if (gn) hipLaunchKernelGGL((wino4_xform_v_kernel<true, 1>), gv, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((wino4_xform_v_kernel<false, 1>), gv, dim3(256), 0, st, p);
-      SSDE_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(wino4_xform_z_kernel<1>, gz, dim3(256), 0, st, p);
-  }
+  hipLaunchKernelGGL(xf.z, dim3(grid_for((long long)p.T * p.Cout / (v2 ? 2 : 1))), dim3(256), 0, st, p);
   SSDE_LAUNCH_CHECK();
-  const int lds = 2 * kStage * 4;
   const dim3 gg(ssde_cdiv(p.sk_on ? p.sk_groups : kPos * p.splits, 8) * 8 * p.co_tiles * p.ci_tiles);
-  if (have_v) hipLaunchKernelGGL(wgrad4_gemm_kernel<true>, gg, dim3(kGemmThreads), lds, st, p);
-  else hipLaunchKernelGGL(wgrad4_gemm_kernel<false>, gg, dim3(kGemmThreads), lds, st, p);
+  const Kernel gemm = have_v ? wgrad4_gemm_kernel<true> : wgrad4_gemm_kernel<false>;
+  hipLaunchKernelGGL(gemm, gg, dim3(kGemmThreads), 2 * kStage * 4, st, p);
   SSDE_LAUNCH_CHECK();
   if (p.splits > 1) {
     hipLaunchKernelGGL(wgrad4_sum_splits_kernel, dim3(grid_for((long long)kPos * p.Cout * p.Ctot / 4)), dim3(256), 0, st, p);
@@ -620,3 +582,4 @@ int ssde_wgrad_wino4_launch(const ssde_wgrad_args* a, void* stream) {
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
 }
+

@@ -885,15 +885,10 @@ class Lowering:
         meta = self.w.meta.get(id(f["w_main"]))
         if meta is None or len(meta["parts"]) != 1 or meta["parts"][0]["transpose"]:
             return False
-        a = L.WgradArgs()
-        s = f["main"]
-        a.src.c0, a.src.c1, a.src.pro_mode, a.src.gn_groups = s["c0"], s["c1"], s["pro_mode"], s["gn_groups"]
-        a.g_ld, a.g_off = f["c_out"], meta["parts"][0]["row0"]
-        a.n, a.h_in, a.w_in, a.h_out, a.w_out = f["n"], f["h_in"], f["w_in"], f["h_out"], f["w_out"]
-        a.c_out, a.ksize, a.stride, a.pad = meta["parts"][0]["rows"], 3, f["stride"], f["pad"]
-        a.pad_end = f.get("pad_end", 0)
-        a.cin_store, a.transpose_out = meta["cin_store"], 0
-        a.flags = L.wgrad_route_flags()
+        part = meta["parts"][0]
+        a = L.wgrad_shape_args(f["main"], g_ld=f["c_out"], g_off=part["row0"], n=f["n"], h_in=f["h_in"], w_in=f["w_in"],
+                               h_out=f["h_out"], w_out=f["w_out"], c_out=part["rows"], ksize=3, stride=f["stride"], pad=f["pad"],
+                               pad_end=f.get("pad_end", 0), cin_store=meta["cin_store"], transpose_out=0)
         return bool(L.load().ssde_wgrad_wants_winograd4(C.byref(a)))
 
     def conv3_route(self, h, w, c_out, c_in, aux=False):

@@ -271,21 +271,17 @@ def conv_wgrad(x, g, ksize, dw, stride=1, pad=1, x2=None, pro=L.PRO_NONE, gn=Non
     """dw += scale * sum_pixels g[:, g_off:g_off+c_out]^T pro(x)[shifted]; x, g NHWC; dw in the reference layout.
     flags: SSDE_WGRADF_* (None: the A/B variables of the environment, _lib.wgrad_route_flags)."""
     _need_cuda(x, g, dw)
-    a = L.WgradArgs()
-    a.flags = L.wgrad_route_flags() if flags is None else flags
+    ctot = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
+    a = L.wgrad_shape_args(dict(c0=x.shape[-1], c1=ctot - x.shape[-1], pro_mode=pro, gn_groups=gn[4] if gn is not None else 0), flags,
+                           g_ld=g.shape[-1], g_off=g_off, n=x.shape[0], h_in=x.shape[1], w_in=x.shape[2], h_out=g.shape[1],
+                           w_out=g.shape[2], c_out=c_out if c_out is not None else g.shape[-1] - g_off, ksize=ksize, stride=stride,
+                           pad=pad, pad_end=pad_end, cin_store=cin_store if cin_store is not None else ctot,
+                           transpose_out=transpose_out)
+    need = wgrad_scratch_floats(a)       # slabs of the library's preferred split
     _fill_src(a.src, x, x2, pro, gn)
     if dropout is not None:
         set_dropout(a.src, *dropout)
-    a.g, a.g_ld, a.g_off = _p(g), g.shape[-1], g_off
-    a.n, a.h_in, a.w_in, a.h_out, a.w_out = x.shape[0], x.shape[1], x.shape[2], g.shape[1], g.shape[2]
-    a.c_out = c_out if c_out is not None else g.shape[-1] - g_off
-    ctot = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
-    a.ksize, a.stride, a.pad, a.pad_end = ksize, stride, pad, pad_end
-    a.cin_store = cin_store if cin_store is not None else ctot
-    a.transpose_out, a.splits, a.scale, a.dw = int(transpose_out), splits, scale, _p(dw)
-    a.splits = 0
-    need = wgrad_scratch_floats(a)       # slabs of the library's preferred split
-    a.splits = splits
+    a.g, a.splits, a.scale, a.dw = _p(g), splits, scale, _p(dw)
     if splits > 1:                       # explicit split (tests): a slab is at most one padded copy of dw per tile grid
         bt = 64 if ksize == 3 else 128
         slab = ksize * ksize * (-(-a.c_out // bt) * bt) * (-(-a.cin_store // bt) * bt)

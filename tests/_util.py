@@ -14,6 +14,15 @@ if ROOT not in sys.path:
 from score_sde_pytorch_amd import configs as cfgs  # noqa: E402
 
 
+def load_tool(name):
+    """tools/<name>.py as a module: a test that recomputes a recorded fixture takes its cases from the tool that recorded it"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def small_config(kind="ncsnpp", image_size=16, nf=32, ch_mult=(1, 2), num_res_blocks=1, attn=(8,)):
     """Down-sized variants of the BASELINE configs that keep every code path of the full ones."""
     base = {"ncsnpp": "ve/cifar10_ncsnpp_continuous", "ddpmpp": "subvp/cifar10_ddpmpp_continuous",

@@ -300,6 +300,31 @@ def test_wgrad_winograd_kernel(ops, n, h, w, c1, c2, cout, pro, drop, wmode, mon
     assert rel_err(dw.cpu(), 0.5 * wt.grad) < 2e-5
 
 
+_RWP = _util.load_tool("record_wgrad_plans")
+
+
+@pytest.fixture(scope="module")
+def wgrad_launches():
+    import json
+    with open(_RWP.FIXTURE) as f:
+        return json.load(f)["launches"]
+
+
+@pytest.mark.parametrize("route", ["f4", "f2", "direct", "1x1", "chunked"])
+def test_wgrad_launch_plans_match_the_recorded_hashes(route, wgrad_launches):
+    """The split a weight-gradient launch takes decides the order of its sums, hence the bits of dw: SHA-256 of dw after
+    ssde_conv_wgrad for the cases of tools/record_wgrad_plans.py (every route at the smallest shapes at which its plan can go
+    wrong: preferred, explicit and scratch-limited splits, stream-K, every flag), against the hashes recorded before the
+    dispatch got its route table.  The emulator is built without floating-point contraction, so its bits are reproducible.
+    (test_wgrad_winograd_kernel and the training tests check the same kernels against autograd.)"""
+    names = [n for n, c in _RWP.CASES.items() if c["route"] == route]
+    assert sorted(wgrad_launches) == sorted(_RWP.CASES) and len(names) >= 5
+    got = _RWP.launch_hashes(names, check=False)        # (the tool compared every case with fp64 autograd before it wrote the hashes)
+    assert {n: h for n, (h, _) in got.items()} == {n: wgrad_launches[n] for n in names}
+    for a, b in _RWP.SPLIT_PAIRS:                                             # the cases see the split at all
+        assert wgrad_launches[a] != wgrad_launches[b]
+
+
 def test_rk45_stage_kernels_reproduce_scipy(ops):
     """ssde_rk_combine / ssde_rk_error_norm (the integrator's fp64 stage arithmetic and RMS error norm) driving the same
     step-size controller as scipy's RK45: identical function-evaluation count and solution on an analytic system"""

@@ -273,6 +273,37 @@ def test_conv_plan_queries_match_the_recorded_grid():
     assert all(seen[r][0] >= 100 and seen[r][1] >= 10 for r in rcp.ROUTES), seen
 
 
+def test_wgrad_plan_queries_match_the_recorded_grid():
+    """ssde_wgrad_scratch_floats / ssde_wgrad_wants_winograd4 and the route prefix of a refusal over
+    tests/golden/wgrad_plan_queries.json (tools/record_wgrad_plans.py: the answers recorded before the library's weight-gradient
+    dispatch got its route table; the 288 points that the F(2x2,3x3) route then accepted although their gradient block lies
+    beyond the row of g -- the direct kernels always refused them -- are recorded as the refusals they are now)."""
+    import json
+    rwp = _util.load_tool("record_wgrad_plans")
+    with open(rwp.FIXTURE) as f:
+        want = rwp.decode(json.load(f))
+    got = rwp.record()
+    assert sorted(got) == sorted(want) and len(got) >= 150
+    bad = [(key, pt, g, w) for combo, points in rwp.combinations() for key in [rwp.key_of(combo)]
+           for pt, g, w in zip(points, got[key], want[key]) if g != w]
+    assert all(len(got[k]) == len(want[k]) for k in got) and not bad, (len(bad), bad[:5])
+    # every route of the table accepts points of the grid; what every route asks is refused in front of them all
+    seen = rwp.census(want)
+    assert all(seen[r][0] >= 1000 for r in rwp.ROUTES) and all(seen[r][1] >= 100 for r in ("f2", "1x1", "direct")), seen
+
+
+def test_wgrad_shape_args_takes_every_field_or_none():
+    from score_sde_pytorch_amd import _lib as L
+    src = dict(c0=8, c1=4, pro_mode=L.PRO_GN_SILU, gn_groups=3)
+    geometry = {k: i + 1 for i, k in enumerate(L.WGRAD_GEOMETRY)}
+    a = L.wgrad_shape_args(src, L.WGRADF_F2, **geometry)
+    assert [getattr(a, k) for k in L.WGRAD_GEOMETRY] == list(geometry.values()) and a.pad_end == geometry["pad_end"]
+    assert (a.src.c0, a.src.c1, a.src.pro_mode, a.src.gn_groups, a.flags, a.splits) == (8, 4, L.PRO_GN_SILU, 3, L.WGRADF_F2, 0)
+    del geometry["pad_end"]
+    with pytest.raises(TypeError):
+        L.wgrad_shape_args(src, **geometry)
+
+
 def test_conv3_route_table_names_every_tile():
     from score_sde_pytorch_amd import engine as E, _lib as L
     assert [r.name for r in E.CONV3_ROUTES] == ["direct", "f2", "f4", "f4r", "f4p"]
