@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 13  /* (13, no new version: ssde_upfirdn2d takes kernels of 1..SSDE_FIR_MAX_TAPS taps per axis and negative pads, which crop -- ssde_upfirdn_args.taps is appended behind dst2 (a device array for kernels past 4x4; the structure grows inside the op union, so every op record keeps its size and every earlier field its offset) and ssde_upfirdn_args.flags takes the former pad word (SSDE_FIRF_GENERAL, SSDE_FIRF_TILED); a caller of version 13 zero-fills its records, so it sends flags = 0 and taps = NULL, every launch it could make keeps its kernel and its bits, and plan blobs of version 13 load unchanged, so the number stays -- an older library refuses a kernel past 4x4 by message) (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 13  /* (13, no layout change and no new version: controllable generation from sampler plans -- new exports ssde_project_prepare (one launch, no program op: the op union keeps its 34 kinds and its size) and ssde_pc_projection / ssde_pc_set_known / ssde_pc_reset_known / ssde_pc_set_noise, which find their buffers in the SSDE_OP_PROJECT / SSDE_OP_LANGEVIN / SSDE_OP_PREDICTOR ops of a loaded SSDE_PLAN_PC plan; ssde_pc_run now refuses a projection plan whose known data was never set; no structure, header field or I/O slot changes and every blob of version 13 stays byte-identical, so the number stays -- a binding that needs the new exports finds out by name when it binds) (13, no new version: ssde_upfirdn2d takes kernels of 1..SSDE_FIR_MAX_TAPS taps per axis and negative pads, which crop -- ssde_upfirdn_args.taps is appended behind dst2 (a device array for kernels past 4x4; the structure grows inside the op union, so every op record keeps its size and every earlier field its offset) and ssde_upfirdn_args.flags takes the former pad word (SSDE_FIRF_GENERAL, SSDE_FIRF_TILED); a caller of version 13 zero-fills its records, so it sends flags = 0 and taps = NULL, every launch it could make keeps its kernel and its bits, and plan blobs of version 13 load unchanged, so the number stays -- an older library refuses a kernel past 4x4 by message) (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
@@ -373,6 +373,23 @@ typedef struct ssde_project_args {
   int32_t use_matrix;
   float M[9], invM[9];            /* row-major [i][j]: y_j = sum_i x_i M[i][j]  (einsum 'bihw,ij->bjhw', :108-113) */
 } ssde_project_args;
+typedef struct ssde_project_prepare_args {
+  /* what controllable generation does BEFORE the loop, one launch per request (not a program op): the known data in the
+   * projection's space -- the `data` ssde_project_args reads --, the mask, and the reference's start state
+   * (controllable_generation.py:74 inpainting; :170-172 colorization, which masks the prior in PIXEL space before it
+   * decouples it).  A, A^-1 = identity, or M, invM when use_matrix (c == 3; the convention of ssde_project_args):
+   *   known    = A data
+   *   mask_out = mask, or with mask == NULL (use_matrix only): 1 on channel 0, 0 on channels 1 and 2 (get_mask, :148-151)
+   *   prior != NULL:  x = A^-1 (known mask_out + A (prior (1 - mask_out)));  x_mean = x
+   * Identity form: known == data and x == data * mask + prior * (1. - mask), bit for bit.
+   * data == NULL (prior != NULL): `known` is read as an earlier launch wrote it instead of being formed (`mask` may be
+   * that launch's mask_out).  mask_out may alias mask; known, mask_out, x_mean may be NULL (not written). */
+  const float* data; const float* mask; const float* prior;   /* [n, c, hw] */
+  float* known; float* mask_out; float* x; float* x_mean;     /* [n, c, hw] */
+  int32_t n, c, hw;
+  int32_t use_matrix;
+  float M[9], invM[9];
+} ssde_project_prepare_args;
 
 
 /* =============================== training path ====================================
@@ -645,6 +662,7 @@ int ssde_sample_update(const ssde_sample_update_args* a, void* stream);
 int ssde_fill_from_table(const ssde_fill_args* a, void* stream);
 int ssde_step_inc(const ssde_step_inc_args* a, void* stream);
 int ssde_project_update(const ssde_project_args* a, void* stream);
+int ssde_project_prepare(const ssde_project_prepare_args* a, void* stream);   /* (added under ABI 13) single launch, no program op */
 int ssde_rk_combine(const ssde_rk_combine_args* a, void* stream);
 int ssde_rk_error_norm(const ssde_rk_error_args* a, void* stream);
 int ssde_rk_combine_rows(const ssde_rk_combine_rows_args* a, void* stream);
@@ -804,6 +822,28 @@ int ssde_unet_backward(ssde_plan* p, const float* dout, float* dx, float* dparam
  * (e.g. SSDE_IO_PARAMS: the flat parameter buffer after training steps), 1 writes it */
 int ssde_plan_copy_io(ssde_plan* p, int32_t slot, void* buf, int64_t bytes, int32_t to_plan, void* stream);
 int ssde_pc_state(ssde_plan* p, float* x, float* x_mean, void* stream);
+/* ---- controllable generation on sampler plans (added under ABI 13): SSDE_PLAN_PC blobs exported from the engine behind
+ * get_pc_inpainter / get_pc_colorizer (controllable_generation.<fn>.engine(model, shape) -> plan_export.export_pc_plan), whose
+ * iteration holds two SSDE_OP_PROJECT ops ----
+ * replaces pc_inpainter / pc_colorizer (controllable_generation.py:59-80, :156-179): hand over the known data, form the
+ * start state from a prior sample (:73, :170-172), iterate with ssde_pc_run, read x_mean with ssde_pc_state.  The library
+ * finds its buffers in the relocated ops: the first / second SSDE_OP_PROJECT (after the corrector / the predictor) give data,
+ * mask, noise, shape and matrices, SSDE_OP_LANGEVIN.noise and SSDE_OP_PREDICTOR.noise the other two noise buffers -- no header
+ * field, no I/O slot.  All tensors are DEVICE pointers, [B,C,H,W] fp32.  Prior sampling (ssde_randn times the prior's
+ * scale), the denoise choice and the inverse scaler stay with the host.  ssde_pc_run refuses a projection plan whose known
+ * data was never set (a zero mask would run an unconditional sampler); ssde_pc_reset stays valid on such plans for a host
+ * that composes the start state itself. */
+enum { SSDE_PC_PROJ_NONE = 0, SSDE_PC_PROJ_MASK = 1, SSDE_PC_PROJ_COLOR = 2 };
+int ssde_pc_projection(const ssde_plan* p);    /* which of the three the plan's iteration contains; < 0: error */
+/* data: in the model's input scaling (inpainting: the image; colorization: the grey image repeated over RGB); mask: 0 / 1,
+ * or NULL = the task's own mask (colorization only).  Fills the plan's known-data and mask regions (ssde_project_prepare). */
+int ssde_pc_set_known(ssde_plan* p, const float* data, const float* mask, void* stream);
+/* the reference's start state from a prior sample (needs ssde_pc_set_known first); x_mean = x, step = 0, seed word = seed */
+int ssde_pc_reset_known(ssde_plan* p, const float* prior, uint64_t seed, void* stream);
+/* plans exported with with_rng=False only: hand the next iteration its noise.  which = 0 corrector, 1 predictor,
+ * 2 projection after the corrector, 3 projection after the predictor; a stage the sampler lacks (corrector or predictor
+ * `none`) is refused */
+int ssde_pc_set_noise(ssde_plan* p, int32_t which, const float* z, void* stream);
 /* ---- ODE plans (SSDE_PLAN_ODE / SSDE_PLAN_LIKELIHOOD, exported from ode.FusedDrift / ode.FusedLikelihoodRhs by
  * plan_export.export_ode_plan) ----
  * replaces scipy.integrate.solve_ivp(method=...) around the network as the reference's get_ode_sampler and

@@ -186,6 +186,13 @@ class ProjectArgs(C.Structure):
                 ("M", C.c_float * 9), ("invM", C.c_float * 9)]
 
 
+class ProjectPrepareArgs(C.Structure):
+    """include/ssde.h: ssde_project_prepare_args (a single launch, no program op)"""
+    _fields_ = [("data", _fp), ("mask", _fp), ("prior", _fp), ("known", _fp), ("mask_out", _fp), ("x", _fp), ("x_mean", _fp),
+                ("n", C.c_int32), ("c", C.c_int32), ("hw", C.c_int32), ("use_matrix", C.c_int32),
+                ("M", C.c_float * 9), ("invM", C.c_float * 9)]
+
+
 class WgradArgs(C.Structure):
     _fields_ = [("src", Src), ("g", _fp), ("g_ld", C.c_int32), ("g_off", C.c_int32),
                 ("n", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("h_out", C.c_int32), ("w_out", C.c_int32),
@@ -312,12 +319,13 @@ EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attent
            "ssde_conv_wgrad", "ssde_colsum", "ssde_gn_bwd_reduce", "ssde_prologue_bwd", "ssde_attention_bwd",
            "ssde_perturb", "ssde_dsm_loss", "ssde_sumsq_flat", "ssde_adam_clip_ema", "ssde_memset", "ssde_axpy",
            "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_conv_ws_floats", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_rk_combine_rows", "ssde_rk_error_norm_rows", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
-           "ssde_gn_apply", "ssde_gn_apply_bwd",
+           "ssde_gn_apply", "ssde_gn_apply_bwd", "ssde_project_prepare",
            # plan-level entry points (csrc/plan.hip; argument types: plan_export.bind)
            "ssde_plan_load", "ssde_plan_load_file", "ssde_plan_destroy", "ssde_plan_info", "ssde_plan_param",
            "ssde_plan_refresh_weights", "ssde_unet_forward", "ssde_pc_reset", "ssde_pc_run", "ssde_pc_state",
            "ssde_train_step", "ssde_train_forward", "ssde_unet_backward", "ssde_plan_copy_io",
-           "ssde_ode_reset", "ssde_ode_eval", "ssde_ode_solve", "ssde_ode_solve_method", "ssde_ode_state"]
+           "ssde_ode_reset", "ssde_ode_eval", "ssde_ode_solve", "ssde_ode_solve_method", "ssde_ode_state",
+           "ssde_pc_projection", "ssde_pc_set_known", "ssde_pc_reset_known", "ssde_pc_set_noise"]
 
 _lib = None
 
@@ -427,6 +435,7 @@ def bind(lib):
     lib.ssde_rk_combine_rows.argtypes = [C.POINTER(RkCombineRowsArgs), C.c_void_p]
     lib.ssde_rk_error_norm_rows.argtypes = [C.POINTER(RkErrorRowsArgs), C.c_void_p]
     lib.ssde_sample_update.argtypes = [C.POINTER(SampleUpdateArgs), C.c_void_p]
+    lib.ssde_project_prepare.argtypes = [C.POINTER(ProjectPrepareArgs), C.c_void_p]
     lib.ssde_conv_lds_bytes.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_attention_route.argtypes = [C.POINTER(AttnArgs)]
     lib.ssde_conv_gn_slices.argtypes = [C.POINTER(ConvArgs)]

@@ -7,6 +7,10 @@ model the whole iteration -- both U-Net evaluations, the updates and the two pro
 (`ssde_project_update`, include/ssde.h) -- is one step program replayed as a hipGraph; user-registered
 predictors / correctors run the generic loop, calling their `update_fn` with our `score_fn`.
 
+`fn.engine(model, shape, device=None)` of a returned function is the fused engine a call would use (None where the generic
+loop runs): `plan_export.export_pc_plan(fn.engine(model, shape))` serialises its iteration for hosts without Python, which
+fill it through ssde_pc_set_known / ssde_pc_reset_known (include/ssde.h).
+
 Extra keyword arguments of the returned functions exist for parity testing (the reference's RNG stream
 cannot be reproduced): `prior` (the prior sample) and `noises` ([N, 4, *shape]: corrector,
 predictor, projection-after-corrector, projection-after-predictor noise of every iteration).
@@ -39,16 +43,34 @@ def _controlled_pc(sde, predictor, corrector, inverse_scaler, snr, n_steps, prob
         x_mean = from_space(to_space(x) * (1. - mask) + known_mean * mask)
         return x, x_mean
 
-    def run(model, x, data_in_space, mask, noises, seed, use_graph, max_steps):
+    def fused_engine(model, shape, device, like):
+        """the FusedPCSampler of (model, shape) on `device`, built once; None where the generic loop runs.  `like`: what
+        plan_fused inspects of the state (its device kind)"""
         from . import pc_engine
-        plan = pc_engine.plan_fused(sde, predictor, corrector, model, continuous, x, probability_flow)
-        if plan is not None:
-            key = (id(model), tuple(x.shape))
-            eng = fused_cache.get(key)
-            if eng is None:
-                eng = fused_cache[key] = pc_engine.FusedPCSampler(
-                    model, sde, plan, tuple(x.shape), snr=snr, n_steps=n_steps, probability_flow=probability_flow,
-                    eps=eps, device=x.device, projection=matrices)
+        plan = pc_engine.plan_fused(sde, predictor, corrector, model, continuous, like, probability_flow)
+        if plan is None:
+            return None
+        key = (id(model), tuple(shape)) + (() if device.type == "cuda" else (device.type,))
+        eng = fused_cache.get(key)
+        if eng is None:
+            eng = fused_cache[key] = pc_engine.FusedPCSampler(
+                model, sde, plan, tuple(shape), snr=snr, n_steps=n_steps, probability_flow=probability_flow,
+                eps=eps, device=device, projection=matrices)
+        return eng
+
+    def engine(model, shape, device=None):
+        """The FusedPCSampler a call on `model` with a state of `shape` uses (built and cached as the call would), or None
+        where the generic loop would run; plan_export.export_pc_plan(fn.engine(model, shape), with_rng=...) serialises its
+        iteration for hosts without Python.  device=None: the model's device; device="cpu": a dry lowering (export needs no
+        GPU), as engine.UNetEngine(..., device="cpu")."""
+        import types
+        dry = device is not None and torch.device(device).type == "cpu"
+        device = next(model.parameters()).device if device is None else torch.device(device)
+        return fused_engine(model, shape, device, types.SimpleNamespace(is_cuda=device.type == "cuda" or dry))
+
+    def run(model, x, data_in_space, mask, noises, seed, use_graph, max_steps):
+        eng = fused_engine(model, x.shape, x.device, x)
+        if eng is not None:
             eng.set_projection_inputs(data_in_space, mask)
             x_fin, x_mean = eng.run(x, noises=noises, seed=seed, use_graph=use_graph, max_steps=max_steps)
             run.last_path = eng.last_path
@@ -72,6 +94,7 @@ def _controlled_pc(sde, predictor, corrector, inverse_scaler, snr, n_steps, prob
         return x, x_mean
 
     run.last_path = None
+    run.engine = engine
     return run
 
 
@@ -93,6 +116,7 @@ def get_pc_inpainter(sde, predictor, corrector, inverse_scaler, snr, n_steps=1, 
             return inverse_scaler(x_mean if denoise else x)
 
     pc_inpainter.last_path = None
+    pc_inpainter.engine = run.engine
     return pc_inpainter
 
 
@@ -127,4 +151,5 @@ def get_pc_colorizer(sde, predictor, corrector, inverse_scaler, snr, n_steps=1, 
             return inverse_scaler(x_mean if denoise else x)
 
     pc_colorizer.last_path = None
+    pc_colorizer.engine = run.engine
     return pc_colorizer

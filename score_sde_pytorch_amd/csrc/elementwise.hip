@@ -250,6 +250,65 @@ __global__ __launch_bounds__(256) void project_color_kernel(float* __restrict__ 
   }
 }
 
+// ---- what controllable generation does before the loop (controllable_generation.py:73, :170-172; ssde_project_prepare) ----
+// Identity form: known = data ; x = x_mean = data mask + prior (1 - mask), torch's operation order.  data == nullptr: known is
+// read, not written.  No __restrict__: mask_out may alias mask.
+__global__ __launch_bounds__(256) void project_prepare_kernel(const float* data, const float* mask, const float* prior, float* known,
+                                                              float* mask_out, float* x, float* x_mean, size_t numel) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (size_t)gridDim.x * blockDim.x) {
+    const float mk = mask[i];
+    const float kn = data ? data[i] : known[i];
+    if (data && known) known[i] = kn;
+    if (mask_out) mask_out[i] = mk;
+    if (prior) {
+      const float xn = __fadd_rn(__fmul_rn(kn, mk), __fmul_rn(prior[i], __fsub_rn(1.0f, mk)));
+      x[i] = xn;
+      if (x_mean) x_mean[i] = xn;
+    }
+  }
+}
+
+// Colour-space form: one thread per pixel.  known = M data -- project_color_kernel's product, were `data` the state --, the
+// prior is masked in PIXEL space before it is decoupled (:170-172), x = invM (known mask + M (prior (1 - mask))).
+// mask == nullptr: the colorizer's own mask, 1 on the grey channel (get_mask, :148-151).
+__global__ __launch_bounds__(256) void project_prepare_color_kernel(const float* data, const float* mask, const float* prior, float* known,
+                                                                    float* mask_out, float* x, float* x_mean, int n, int hw,
+                                                                    SsdeMat3 M, SsdeMat3 invM) {
+  const size_t pixels = (size_t)n * hw;
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += (size_t)gridDim.x * blockDim.x) {
+    const size_t base = (p / hw) * 3 * (size_t)hw + (p % hw);
+    float d[3], kn[3], mk[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const size_t i = base + (size_t)c * hw;
+      mk[c] = mask ? mask[i] : (c == 0 ? 1.0f : 0.0f);
+      if (data) d[c] = data[i];
+      else kn[c] = known[i];
+    }
+    if (data) mat3_apply(M, d, kn);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const size_t i = base + (size_t)c * hw;
+      if (data && known) known[i] = kn[c];
+      if (mask_out) mask_out[i] = mk[c];
+    }
+    if (prior) {
+      float pm[3], ap[3], y[3], xn[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) pm[c] = __fmul_rn(prior[base + (size_t)c * hw], __fsub_rn(1.0f, mk[c]));
+      mat3_apply(M, pm, ap);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) y[c] = __fadd_rn(__fmul_rn(kn[c], mk[c]), ap[c]);
+      mat3_apply(invM, y, xn);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        x[base + (size_t)c * hw] = xn[c];
+        if (x_mean) x_mean[base + (size_t)c * hw] = xn[c];
+      }
+    }
+  }
+}
+
 __global__ void fill_kernel(float* __restrict__ dst, const float* __restrict__ tab, const int* __restrict__ step_ptr, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = tab[step_ptr ? *step_ptr : 0];
@@ -562,6 +621,28 @@ extern "C" int ssde_project_update(const ssde_project_args* a, void* stream) {
   } else {
     hipLaunchKernelGGL(project_kernel, dim3(grid_for((size_t)a->n * a->c * a->hw)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        a->x, a->x_mean, a->data, a->mask, a->noise, a->coef, a->step_ptr, (size_t)a->n * a->c * a->hw);
+  }
+  SSDE_LAUNCH_CHECK();
+  return SSDE_OK;
+}
+
+extern "C" int ssde_project_prepare(const ssde_project_prepare_args* a, void* stream) {
+  SSDE_REQUIRE(a, "project_prepare: null args");
+  SSDE_REQUIRE(a->n > 0 && a->c > 0 && a->hw > 0, "project_prepare: bad shape");
+  SSDE_REQUIRE(a->mask || a->use_matrix, "project_prepare: mask == NULL (the task's own mask) needs the colour-space form");
+  SSDE_REQUIRE(a->data || (a->prior && a->known), "project_prepare: without data the launch reads known and needs a prior");
+  SSDE_REQUIRE(a->data || !a->mask_out || a->mask_out == a->mask, "project_prepare: without data there is no mask to write");
+  SSDE_REQUIRE(!a->prior || a->x, "project_prepare: a prior needs the state x to write");
+  SSDE_REQUIRE(a->prior || a->known || a->mask_out, "project_prepare: nothing to write");
+  if (a->use_matrix) {
+    SSDE_REQUIRE(a->c == 3, "project_prepare: the colour-space form needs 3 channels (got %d)", a->c);
+    SsdeMat3 M, invM;
+    for (int i = 0; i < 9; ++i) { M.m[i] = a->M[i]; invM.m[i] = a->invM[i]; }
+    hipLaunchKernelGGL(project_prepare_color_kernel, dim3(grid_for((size_t)a->n * a->hw)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       a->data, a->mask, a->prior, a->known, a->mask_out, a->x, a->x_mean, a->n, a->hw, M, invM);
+  } else {
+    hipLaunchKernelGGL(project_prepare_kernel, dim3(grid_for((size_t)a->n * a->c * a->hw)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       a->data, a->mask, a->prior, a->known, a->mask_out, a->x, a->x_mean, (size_t)a->n * a->c * a->hw);
   }
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;

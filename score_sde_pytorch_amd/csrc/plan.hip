@@ -34,6 +34,8 @@ struct ssde_plan {
   ssde_ode_dyn* ode_ring = nullptr;
   int ode_slot = 0, ode_inflight = 0;
   hipStream_t ode_stream = nullptr;
+  // sampler plans with a projection: ssde_pc_set_known has filled the known-data and mask regions
+  bool known_set = false;
 };
 
 namespace {
@@ -223,8 +225,123 @@ extern "C" int ssde_pc_reset(ssde_plan* p, const float* x_T, uint64_t seed, void
 
 // n PC iterations on `stream`; use_graph != 0: the iteration is captured into a hipGraph on first use (stream must then
 // be a non-default stream) and replayed -- the device step counter and seed word make every replay a new iteration.
+// What the iteration of a sampler plan says about itself (controllable generation: pc_engine's emit_projection puts one
+// SSDE_OP_PROJECT after the corrector block and one after the predictor block, both on the same known data and mask).
+namespace {
+struct PcView {
+  const ssde_project_args* proj[2] = {nullptr, nullptr};   // after the corrector, after the predictor
+  float* noise[4] = {nullptr, nullptr, nullptr, nullptr};  // corrector, predictor, the two projections (the order of `noises[:, k]`)
+  int n_proj = 0;
+  bool draws_noise = false;                                // the iteration holds SSDE_OP_RANDN: it fills the buffers itself
+};
+
+int pc_view(const ssde_plan* p, PcView* v, const char* who) {
+  SSDE_REQUIRE(p && p->hdr.kind == SSDE_PLAN_PC, "%s: not a sampler plan", who);
+  for (const ssde_op& op : p->ops) {
+    if (op.kind == SSDE_OP_RANDN) v->draws_noise = true;
+    else if (op.kind == SSDE_OP_LANGEVIN && !v->noise[0]) v->noise[0] = const_cast<float*>(op.u.langevin.noise);
+    else if (op.kind == SSDE_OP_PREDICTOR && !v->noise[1]) v->noise[1] = const_cast<float*>(op.u.predictor.noise);
+    else if (op.kind == SSDE_OP_PROJECT) {
+      if (v->n_proj < 2) { v->proj[v->n_proj] = &op.u.project; v->noise[2 + v->n_proj] = const_cast<float*>(op.u.project.noise); }
+      v->n_proj++;
+    }
+  }
+  const ssde_plan_header& h = p->hdr;
+  const size_t img = (size_t)h.batch * h.channels * h.height * h.width * sizeof(float);
+  auto holds = [&](const void* q) {                        // a whole image at q lies inside one region of the plan
+    const char* c = static_cast<const char*>(q);
+    for (const Region& r : p->regions) {
+      const char* base = static_cast<const char*>(r.dev);
+      if (base && c >= base && c + img <= base + r.bytes) return true;
+    }
+    return false;
+  };
+  for (int k = 0; k < 4; ++k) SSDE_REQUIRE(!v->noise[k] || holds(v->noise[k]), "%s: noise buffer %d of the plan is smaller than the state", who, k);
+  if (v->n_proj == 0) return SSDE_OK;
+  const ssde_project_args *a = v->proj[0], *b = v->proj[1];
+  SSDE_REQUIRE(v->n_proj == 2 && a->data && a->mask && a->x && a->x_mean && a->data == b->data && a->mask == b->mask && a->x == b->x &&
+                   a->x_mean == b->x_mean && a->use_matrix == b->use_matrix,
+               "%s: the plan's iteration holds %d projections that do not share one known-data / mask / state (expected two that do)", who, v->n_proj);
+  SSDE_REQUIRE(a->n == h.batch && a->c == h.channels && a->hw == h.height * h.width, "%s: the projection is [%d,%d,%d], the plan [%d,%d,%d x %d]", who,
+               a->n, a->c, a->hw, h.batch, h.channels, h.height, h.width);
+  SSDE_REQUIRE(holds(a->data) && holds(a->mask) && holds(a->x) && holds(a->x_mean), "%s: a projection buffer of the plan is smaller than the state", who);
+  return SSDE_OK;
+}
+
+// the launch arguments shared by set_known and reset_known: shape, form and matrices of the plan's own projection
+void prepare_args_of(const ssde_project_args* pj, ssde_project_prepare_args* a) {
+  memset(a, 0, sizeof(*a));
+  a->n = pj->n; a->c = pj->c; a->hw = pj->hw; a->use_matrix = pj->use_matrix;
+  memcpy(a->M, pj->M, sizeof(a->M));
+  memcpy(a->invM, pj->invM, sizeof(a->invM));
+}
+}  // namespace
+
+extern "C" int ssde_pc_projection(const ssde_plan* p) {
+  PcView v;
+  if (int rc = pc_view(p, &v, "pc_projection")) return rc;
+  return v.n_proj == 0 ? SSDE_PC_PROJ_NONE : v.proj[0]->use_matrix ? SSDE_PC_PROJ_COLOR : SSDE_PC_PROJ_MASK;
+}
+
+extern "C" int ssde_pc_set_known(ssde_plan* p, const float* data, const float* mask, void* stream) {
+  PcView v;
+  if (int rc = pc_view(p, &v, "pc_set_known")) return rc;
+  SSDE_REQUIRE(v.n_proj > 0, "pc_set_known: the plan's iteration has no projection (an unconditional sampler)");
+  SSDE_REQUIRE(data, "pc_set_known: null data");
+  SSDE_REQUIRE(mask || v.proj[0]->use_matrix, "pc_set_known: an inpainting plan needs a mask (NULL = the task's own mask: colorization only)");
+  ssde_project_prepare_args a;
+  prepare_args_of(v.proj[0], &a);
+  a.data = data; a.mask = mask;
+  a.known = const_cast<float*>(v.proj[0]->data);
+  a.mask_out = const_cast<float*>(v.proj[0]->mask);
+  if (int rc = ssde_project_prepare(&a, stream)) return rc;
+  p->known_set = true;
+  return SSDE_OK;
+}
+
+extern "C" int ssde_pc_reset_known(ssde_plan* p, const float* prior, uint64_t seed, void* stream) {
+  PcView v;
+  if (int rc = pc_view(p, &v, "pc_reset_known")) return rc;
+  SSDE_REQUIRE(v.n_proj > 0, "pc_reset_known: the plan's iteration has no projection (an unconditional sampler: ssde_pc_reset)");
+  SSDE_REQUIRE(p->known_set, "pc_reset_known: the known data was never set (ssde_pc_set_known comes first)");
+  SSDE_REQUIRE(prior, "pc_reset_known: null prior");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ssde_plan_header& h = p->hdr;
+  SSDE_REQUIRE(region_ptr(p, h.io[SSDE_IO_STEP]) && region_ptr(p, h.io[SSDE_IO_SEED]), "pc_reset_known: the plan has no step counter / seed word");
+  ssde_project_prepare_args a;
+  prepare_args_of(v.proj[0], &a);
+  a.prior = prior;
+  a.known = const_cast<float*>(v.proj[0]->data);     // read: data == NULL
+  a.mask = v.proj[0]->mask;
+  a.x = v.proj[0]->x; a.x_mean = v.proj[0]->x_mean;
+  if (int rc = ssde_project_prepare(&a, stream)) return rc;
+  SSDE_HIP_CHECK(hipMemsetAsync(region_ptr(p, h.io[SSDE_IO_STEP]), 0, sizeof(int32_t), st));
+  SSDE_HIP_CHECK(hipStreamSynchronize(st));
+  SSDE_HIP_CHECK(hipMemcpy(region_ptr(p, h.io[SSDE_IO_SEED]), &seed, sizeof(seed), hipMemcpyHostToDevice));
+  return SSDE_OK;
+}
+
+extern "C" int ssde_pc_set_noise(ssde_plan* p, int32_t which, const float* z, void* stream) {
+  PcView v;
+  if (int rc = pc_view(p, &v, "pc_set_noise")) return rc;
+  SSDE_REQUIRE(!v.draws_noise, "pc_set_noise: the plan draws its own noise (it contains SSDE_OP_RANDN; export it with with_rng=False)");
+  SSDE_REQUIRE(which >= 0 && which < 4 && z, "pc_set_noise: which = %d (0 corrector, 1 predictor, 2 / 3 the projections) or null noise", which);
+  static const char* const kStage[4] = {"corrector", "predictor", "projection after the corrector", "projection after the predictor"};
+  SSDE_REQUIRE(v.noise[which], "pc_set_noise: the plan has no %s stage", kStage[which]);
+  const ssde_plan_header& h = p->hdr;
+  const size_t img = (size_t)h.batch * h.channels * h.height * h.width * sizeof(float);
+  SSDE_HIP_CHECK(hipMemcpyAsync(v.noise[which], z, img, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  return SSDE_OK;
+}
+
 extern "C" int ssde_pc_run(ssde_plan* p, int32_t n_iterations, int32_t use_graph, void* stream) {
   SSDE_REQUIRE(p && p->hdr.kind == SSDE_PLAN_PC && n_iterations >= 0, "pc_run: bad args");
+  if (!p->known_set) {
+    PcView v;
+    if (int rc = pc_view(p, &v, "pc_run")) return rc;
+    SSDE_REQUIRE(v.n_proj == 0, "pc_run: the plan's iteration projects onto known data that was never set (ssde_pc_set_known; a zero mask "
+                                "would run an unconditional sampler)");
+  }
   if (use_graph) {
     if (!p->graph || p->graph_stream != static_cast<hipStream_t>(stream)) {
       if (p->graph) { ssde_graph_destroy(p->graph); p->graph = nullptr; }

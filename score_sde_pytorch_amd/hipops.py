@@ -431,6 +431,27 @@ def sample_update(x, y=None, b=None, z=None, c=None, a=None):
     return x_out, x_mean
 
 
+def project_prepare(data, mask=None, prior=None, M=None, invM=None):
+    """What controllable generation does before its loop, in one launch (ssde_project_prepare): data, mask, prior
+    [N, C, H, W]; M / invM: the nine floats each of the colour decoupling and its inverse (colorization), or None (inpainting);
+    mask=None: the colorizer's own mask.  Returns (known = A data, the mask used, x0 or None without a prior) -- what
+    FusedPCSampler.set_projection_inputs and .run take."""
+    _need_cuda(data, mask, prior)
+    ten = lambda t: None if t is None else t.to(torch.float32).expand_as(data).contiguous()   # noqa: E731
+    data = data.to(torch.float32).contiguous()
+    mask, prior = ten(mask), ten(prior)
+    known, mask_out = torch.empty_like(data), torch.empty_like(data)
+    x = torch.empty_like(data) if prior is not None else None
+    a = L.ProjectPrepareArgs()
+    a.data, a.mask, a.prior, a.known, a.mask_out, a.x = _p(data), _p(mask), _p(prior), _p(known), _p(mask_out), _p(x)
+    a.n, a.c, a.hw = data.shape[0], data.shape[1], data[0, 0].numel()
+    a.use_matrix = int(M is not None)
+    if M is not None:
+        a.M, a.invM = (C.c_float * 9)(*M), (C.c_float * 9)(*invM)
+    L.check(L.load().ssde_project_prepare(C.byref(a), _stream()), "ssde_project_prepare")
+    return known, mask_out, x
+
+
 def dsm_loss(score, z, s, g2=None, reduce_mean=False, likelihood_weighting=False, want_grad=True, grad_scale=1.0):
     _need_cuda(score, z, s)
     n = score.shape[0]

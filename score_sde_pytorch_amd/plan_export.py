@@ -1,6 +1,6 @@
 """Serialise a lowered program as a position-independent PLAN BLOB for hosts without Python (include/ssde.h, "plans";
 loader and runner: csrc/plan.hip -> ssde_plan_load, ssde_unet_forward, ssde_pc_reset / ssde_pc_run / ssde_pc_state,
-ssde_ode_reset / ssde_ode_eval / ssde_ode_solve / ssde_ode_state).
+ssde_pc_set_known / ssde_pc_reset_known / ssde_pc_set_noise (inpainting, colorization), ssde_ode_reset / ssde_ode_eval / ssde_ode_solve / ssde_ode_state).
 
 The lowering of NCSNpp.forward (reference models/ncsnpp.py:232-381) and of the predictor-corrector loop body
 (sampling.py:403-407) exists once, in engine.py / pc_engine.py.  This module walks what that lowering produced:
@@ -34,6 +34,7 @@ IO_ODE_DYN, IO_ODE_K, IO_ODE_STATE, IO_ODE_PROBE = range(20, 24)
 IO_SLOTS = 24
 ODE_PARTIALS = 1024                      # include/ssde.h: SSDE_ODE_PARTIALS
 ODE_METHODS = {"RK45": 0, "RK23": 1, "DOP853": 2}   # include/ssde.h: SSDE_ODE_*
+PC_PROJ_NONE, PC_PROJ_MASK, PC_PROJ_COLOR = 0, 1, 2  # include/ssde.h: SSDE_PC_PROJ_*
 
 
 class PlanHeader(C.Structure):
@@ -67,17 +68,21 @@ class _Regions:
     def __init__(self):
         self.by_ptr, self.list = {}, []      # storage data_ptr -> id ; [dict(ptr, bytes, kind, name, storage_tensor)]
 
-    def add(self, t, kind, name):
+    def add(self, t, kind, name, own=False):
+        """own=True: a tensor that is a piece of a larger storage becomes a region of its own extent (a parameter that a
+        training engine has since moved into its flat buffer exports as it did before the move)"""
         if t is None:
             return None
         st = t.untyped_storage()
-        key = st.data_ptr()
+        key, nbytes, piece = st.data_ptr(), st.nbytes(), False
+        if own and t.is_contiguous() and (t.data_ptr() != key or t.numel() * t.element_size() != nbytes):
+            key, nbytes, piece = t.data_ptr(), t.numel() * t.element_size(), True
         if key in self.by_ptr:
             r = self.list[self.by_ptr[key]]
             r["kind"] = max(r["kind"], kind)
             return self.by_ptr[key]
         self.by_ptr[key] = len(self.list)
-        self.list.append(dict(ptr=key, bytes=st.nbytes(), kind=kind, name=name, keep=t))
+        self.list.append(dict(ptr=key, bytes=nbytes, kind=kind, name=name, keep=t, piece=piece))
         return len(self.list) - 1
 
     def freeze(self):
@@ -96,6 +101,8 @@ class _Regions:
     def data(self, rid):
         r = self.list[rid]
         t = r["keep"]
+        if r["piece"]:
+            return t.detach().cpu().contiguous().view(-1).view(torch.uint8).numpy().tobytes()
         flat = torch.empty(0, dtype=torch.uint8).set_(t.untyped_storage().cpu() if t.is_cuda else t.untyped_storage())
         return bytes(flat.numpy().tobytes())
 
@@ -105,10 +112,14 @@ def _collect_unet(regions, eng):
         regions.add(blk, REGION_ZERO, "arena%d" % i)
     for i, t in enumerate(eng.b.keep):
         regions.add(t, REGION_CONST, "table%d" % i)
+    # An inference engine on a model whose parameters a training engine has flattened since (backward.FlatParams: views into
+    # one buffer) exports one region per parameter, as before the move: the blob of an engine does not depend on what was
+    # built on its model afterwards.  A training engine exports its own flat buffer whole.
+    own = getattr(eng, "flat", None) is None
     for i, e in enumerate(eng.weights.entries):
         regions.add(e.packed, REGION_CONST, "packed%d" % i)
         for s in e.sources:
-            regions.add(s.detach(), REGION_CONST, "param")
+            regions.add(s.detach(), REGION_CONST, "param", own=own)
     for i, (_, raw) in enumerate(eng.weights.pack_tables()):
         regions.add(raw, REGION_CONST, "packtab%d" % i)
 
@@ -208,7 +219,11 @@ def export_unet_plan(eng):
 
 
 def export_pc_plan(sampler, with_rng=True):
-    """pc_engine.FusedPCSampler -> blob for ssde_pc_reset / ssde_pc_run / ssde_pc_state (one program = one PC iteration)."""
+    """pc_engine.FusedPCSampler -> blob for ssde_pc_reset / ssde_pc_run / ssde_pc_state (one program = one PC iteration).
+
+    The engine of an inpainter / colorizer (controllable_generation: fn.engine(model, shape)) exports the same way; its
+    iteration holds the SSDE_OP_PROJECT ops through which ssde_pc_set_known / ssde_pc_reset_known find the known-data and mask
+    regions.  with_rng=False leaves the noise to the host: ssde_pc_set_noise before every iteration."""
     eng = sampler.unet
     eng.weights.refresh()
     prog = sampler.step_program(with_rng=with_rng)
@@ -326,6 +341,10 @@ def bind(lib):
     lib.ssde_pc_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.ssde_pc_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.ssde_pc_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ssde_pc_projection.argtypes = [C.c_void_p]
+    lib.ssde_pc_set_known.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ssde_pc_reset_known.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.ssde_pc_set_noise.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.ssde_train_step.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p]
     lib.ssde_train_forward.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_void_p]
     lib.ssde_unet_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -386,6 +405,42 @@ class LoadedPlan:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
         L.check(self.lib.ssde_unet_forward(self.handle, p(x), p(cond), p(sigma), p(std), p(out), C.c_void_p(stream or 0)), "ssde_unet_forward")
         return out
+
+    # ---- sampler plans (ssde_pc_*): tensors are fp32, contiguous, on the plan's device, and stay alive until `stream` has run
+    def pc_reset(self, x_T, seed, stream=None):
+        L.check(self.lib.ssde_pc_reset(self.handle, C.c_void_p(x_T.data_ptr()), int(seed), C.c_void_p(stream or 0)), "ssde_pc_reset")
+
+    def pc_run(self, n_iterations, use_graph=False, stream=None):
+        L.check(self.lib.ssde_pc_run(self.handle, int(n_iterations), int(bool(use_graph)), C.c_void_p(stream or 0)), "ssde_pc_run")
+
+    def pc_state(self, like, stream=None):
+        """(x, x_mean) shaped / placed like `like`"""
+        x, x_mean = torch.empty_like(like, dtype=torch.float32), torch.empty_like(like, dtype=torch.float32)
+        L.check(self.lib.ssde_pc_state(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(x_mean.data_ptr()), C.c_void_p(stream or 0)),
+                "ssde_pc_state")
+        return x, x_mean
+
+    def pc_projection(self):
+        """PC_PROJ_NONE, PC_PROJ_MASK (inpainting) or PC_PROJ_COLOR (colorization): what the plan's iteration contains"""
+        kind = self.lib.ssde_pc_projection(self.handle)
+        if kind < 0:
+            L.check(kind, "ssde_pc_projection")
+        return kind
+
+    def pc_set_known(self, data, mask=None, stream=None):
+        """the known data (model input scaling; colorization: the grey image on all three channels) and the 0 / 1 mask
+        (None: the colorizer's own)"""
+        L.check(self.lib.ssde_pc_set_known(self.handle, C.c_void_p(data.data_ptr()), C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                           C.c_void_p(stream or 0)), "ssde_pc_set_known")
+
+    def pc_reset_known(self, prior, seed, stream=None):
+        """the reference's start state from a prior sample (after pc_set_known); step 0, seed word `seed`"""
+        L.check(self.lib.ssde_pc_reset_known(self.handle, C.c_void_p(prior.data_ptr()), int(seed), C.c_void_p(stream or 0)),
+                "ssde_pc_reset_known")
+
+    def pc_set_noise(self, which, z, stream=None):
+        """plans exported with with_rng=False: which = 0 corrector, 1 predictor, 2 / 3 the projections after them"""
+        L.check(self.lib.ssde_pc_set_noise(self.handle, int(which), C.c_void_p(z.data_ptr()), C.c_void_p(stream or 0)), "ssde_pc_set_noise")
 
     def train_step(self, batch, z, a, s, labels, hyper9, seed, g2=None, stream=None):
         """one optimisation step through the C entry point; returns the loss as a 1-element tensor on the inputs' device"""
