@@ -26,19 +26,29 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 13  /* (13, no layout change and no new version: controllable generation from sampler plans -- new exports ssde_project_prepare (one launch, no program op: the op union keeps its 34 kinds and its size) and ssde_pc_projection / ssde_pc_set_known / ssde_pc_reset_known / ssde_pc_set_noise, which find their buffers in the SSDE_OP_PROJECT / SSDE_OP_LANGEVIN / SSDE_OP_PREDICTOR ops of a loaded SSDE_PLAN_PC plan; ssde_pc_run now refuses a projection plan whose known data was never set; no structure, header field or I/O slot changes and every blob of version 13 stays byte-identical, so the number stays -- a binding that needs the new exports finds out by name when it binds) (13, no new version: ssde_upfirdn2d takes kernels of 1..SSDE_FIR_MAX_TAPS taps per axis and negative pads, which crop -- ssde_upfirdn_args.taps is appended behind dst2 (a device array for kernels past 4x4; the structure grows inside the op union, so every op record keeps its size and every earlier field its offset) and ssde_upfirdn_args.flags takes the former pad word (SSDE_FIRF_GENERAL, SSDE_FIRF_TILED); a caller of version 13 zero-fills its records, so it sends flags = 0 and taps = NULL, every launch it could make keeps its kernel and its bits, and plan blobs of version 13 load unchanged, so the number stays -- an older library refuses a kernel past 4x4 by message) (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 13  /* (13, no layout change and no new version: ssde_src.act -- the spare word at the end of ssde_src, the former _pad, names the activation that SSDE_PRO_GN_SILU / SSDE_PRO_SILU apply: SSDE_ACT_SILU = 0, SSDE_ACT_ELU, SSDE_ACT_RELU, SSDE_ACT_LRELU (get_act, models/layers.py:29-41); only ssde_gn_apply / ssde_gn_apply_bwd (and SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD) evaluate a non-zero value, and they now also take SSDE_PRO_SILU (activation only); every other entry point that reads an ssde_src refuses act != 0 in its argument check; a caller of version 13 zero-fills its records, so it sends SiLU, every launch it could make keeps its kernel and its bits, no structure changes size, no field moves and plan blobs of version 13 stay byte-identical, so the number stays -- an older library ignores the word, so a binding that needs it checks for the refusal) (13, no layout change and no new version: controllable generation from sampler plans -- new exports ssde_project_prepare (one launch, no program op: the op union keeps its 34 kinds and its size) and ssde_pc_projection / ssde_pc_set_known / ssde_pc_reset_known / ssde_pc_set_noise, which find their buffers in the SSDE_OP_PROJECT / SSDE_OP_LANGEVIN / SSDE_OP_PREDICTOR ops of a loaded SSDE_PLAN_PC plan; ssde_pc_run now refuses a projection plan whose known data was never set; no structure, header field or I/O slot changes and every blob of version 13 stays byte-identical, so the number stays -- a binding that needs the new exports finds out by name when it binds) (13, no new version: ssde_upfirdn2d takes kernels of 1..SSDE_FIR_MAX_TAPS taps per axis and negative pads, which crop -- ssde_upfirdn_args.taps is appended behind dst2 (a device array for kernels past 4x4; the structure grows inside the op union, so every op record keeps its size and every earlier field its offset) and ssde_upfirdn_args.flags takes the former pad word (SSDE_FIRF_GENERAL, SSDE_FIRF_TILED); a caller of version 13 zero-fills its records, so it sends flags = 0 and taps = NULL, every launch it could make keeps its kernel and its bits, and plan blobs of version 13 load unchanged, so the number stays -- an older library refuses a kernel past 4x4 by message) (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
   SSDE_PRO_NONE = 0,    /* x                                            */
   SSDE_PRO_GN = 1,      /* GroupNorm(x)            (AttnBlockpp, layerspp.py:77)   */
-  SSDE_PRO_GN_SILU = 2, /* SiLU(GroupNorm(x))      (ResnetBlockBigGANpp, layerspp.py:243,264) */
-  SSDE_PRO_SILU = 3     /* SiLU(x)                 (Dense_0(act(temb)), layerspp.py:263) */
+  SSDE_PRO_GN_SILU = 2, /* act(GroupNorm(x))       (ResnetBlockBigGANpp, layerspp.py:243,264) */
+  SSDE_PRO_SILU = 3     /* act(x)                  (Dense_0(act(temb)), layerspp.py:263) */
+};
+/* The activation of SSDE_PRO_GN_SILU / SSDE_PRO_SILU: ssde_src.act (config.model.nonlinearity, get_act, models/layers.py:29-41).
+ * The prologues the consumers fuse into their staging are SiLU only; the others run in ssde_gn_apply / ssde_gn_apply_bwd. */
+enum {
+  SSDE_ACT_SILU = 0,    /* 'swish': x * sigmoid(x)                          */
+  SSDE_ACT_ELU = 1,     /* 'elu', alpha 1: x > 0 ? x : expm1(x)             */
+  SSDE_ACT_RELU = 2,    /* 'relu'; derivative 0 at x <= 0                   */
+  SSDE_ACT_LRELU = 3    /* 'lrelu': LeakyReLU, slope 0.2 (the reference's only one); derivative 0.2 at x <= 0 */
 };
 
 /* A source operand: the channel-concatenation of up to two NHWC tensors
  * (torch.cat([h, hs.pop()], dim=1), ncsnpp.py:318, without materialising it)
- * plus an optional fused GroupNorm/SiLU prologue. */
+ * plus an optional fused GroupNorm / activation prologue.  The activation is SiLU (act == 0, what a zero-filled record says)
+ * for every consumer that applies the prologue itself; ssde_gn_apply / ssde_gn_apply_bwd honour the other SSDE_ACT_* values
+ * and every other entry point refuses them, so a fused prologue never runs SiLU for a network built with another one. */
 typedef struct ssde_src {
   const float* p0;       /* [N, H, W, c0]                                  */
   const float* p1;       /* [N, H, W, c1] or NULL                          */
@@ -58,7 +68,7 @@ typedef struct ssde_src {
   float drop_scale;
   const uint32_t* drop_seed;  /* device word, rewritten by the host / a step kernel every training step */
   uint32_t drop_salt;
-  int32_t _pad;
+  int32_t act;           /* SSDE_ACT_*: the activation of SSDE_PRO_GN_SILU / SSDE_PRO_SILU (the former pad word; 0 = SiLU) */
 } ssde_src;
 
 /* ---- convolution / pointwise GEMM -------------------------------------------
@@ -198,17 +208,22 @@ enum { SSDE_GNSTATF_ANY_WIDTH = 1u };  /* take the any-width kernel also for a m
  * HBM-bound: one read of the (possibly concatenated) source, one write, 16-byte lanes; the group of a channel comes from
  * a per-workgroup table.  Dropout: element e = pixel * (c0 + c1) + channel of the virtual concat tensor, as in ssde_src.
  * SSDE_PRO_NONE is accepted too: the plain copy of a concatenation whose boundary c0 the matrix kernels refuse (c0 % 32 != 0:
- * 16 + 16 channels at the top level of the nf = 16 networks); its adjoint is two ssde_prologue_bwd slices of the gradient. */
+ * 16 + 16 channels at the top level of the nf = 16 networks); its adjoint is two ssde_prologue_bwd slices of the gradient.
+ * act = src.act, any of SSDE_ACT_*: a network whose nonlinearity is not SiLU takes this launch for EVERY normalise-and-activate
+ * site.  SSDE_PRO_SILU is accepted too: dst = drop(act(x)), no statistics and no affine (Dense(act(temb)), ncsnpp.py:263,
+ * layerspp.py:263: hw = 1).  A value of src.act outside SSDE_ACT_* is refused. */
 typedef struct ssde_gn_apply_args {
-  ssde_src src;                  /* p0 / p1, statistics, affine, dropout identity; c0 % 4 == 0, c1 % 4 == 0 */
+  ssde_src src;                  /* p0 / p1, statistics, affine, activation, dropout identity; c0 % 4 == 0, c1 % 4 == 0 */
   int32_t n, hw;
   float* dst;                    /* [N, hw, c0 + c1] */
 } ssde_gn_apply_args;
 
-/* Its adjoint: with u = xhat * gamma + beta, du = dy * mask * silu'(u), dxh = du * gamma,
+/* Its adjoint: with u = xhat * gamma + beta, du = dy * mask * act'(u), dxh = du * gamma,
  *   dgamma = sum du * xhat, dbeta = sum du, dx = rstd * (dxh - mean_g(dxh) - xhat * mean_g(dxh * xhat)).
  * Three launches (channel sums per (image, pixel slice); their fixed-order merge into sums / dgamma / dbeta; apply): no float
- * atomics, bit-reproducible.  SiLU' and the dropout mask are recomputed. */
+ * atomics, bit-reproducible.  act' (of src.act, torch's conventions: ELU' = exp(u), ReLU' = 0, LeakyReLU' = 0.2 at u <= 0) and
+ * the dropout mask are recomputed.  SSDE_PRO_SILU: dx = dy * mask * act'(x), the last launch alone; sums, scratch, dgamma and
+ * dbeta are not used (dgamma / dbeta must be NULL). */
 typedef struct ssde_gn_apply_bwd_args {
   ssde_src src;                  /* as in the forward */
   const float* dy;               /* [N * hw, c0 + c1] gradient of dst */

@@ -13,6 +13,10 @@ LIB_PATH = os.environ.get("SSDE_LIB_PATH") or os.path.join(_HERE, "libssde_hip.s
 ABI_VERSION = 13
 
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_SILU = 0, 1, 2, 3
+# include/ssde.h: SSDE_ACT_*, the activation of PRO_GN_SILU / PRO_SILU (ssde_src.act); only ssde_gn_apply / ssde_gn_apply_bwd run
+# one that is not SiLU.  ACT_BY_NAME: config.model.nonlinearity, lower case (get_act, models/layers.py:29-41)
+ACT_SILU, ACT_ELU, ACT_RELU, ACT_LRELU = 0, 1, 2, 3
+ACT_BY_NAME = {"swish": ACT_SILU, "elu": ACT_ELU, "relu": ACT_RELU, "lrelu": ACT_LRELU}
 TILE_AUTO, TILE_256x64, TILE_128x64, TILE_64x64, TILE_256x32, TILE_WINOGRAD, TILE_WINOGRAD4 = 0, 1, 2, 3, 4, 5, 6
 TILE_WINOGRAD4R = 9       # (7, 8: the bf16-split and the LDS-fed F(4x4,3x3) kernels of round 4, tools/experiments/)
 TILE_WINOGRAD4P = 10      # F(4x4,3x3) as position-batched GEMMs (conv_wino4p.hip): the 4x4 maps
@@ -41,7 +45,7 @@ class Src(C.Structure):
                 ("pro_mode", C.c_int32), ("gn_groups", C.c_int32),
                 ("gn_mean", _fp), ("gn_rstd", _fp), ("gn_gamma", _fp), ("gn_beta", _fp),
                 ("drop_thresh", C.c_uint32), ("drop_scale", C.c_float), ("drop_seed", _fp),
-                ("drop_salt", C.c_uint32), ("_pad", C.c_int32)]
+                ("drop_salt", C.c_uint32), ("act", C.c_int32)]
 
 
 class ConvArgs(C.Structure):

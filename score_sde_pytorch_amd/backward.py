@@ -319,8 +319,26 @@ class TrainEngine(E.UNetEngine):
             return
         e0 = self._gentry(src["p0"]) if self._needs(src["p0"]) else None
         e1 = self._gentry(src["p1"]) if self._needs(src["p1"]) else None
-        if e0 is None and e1 is None and not self.param_grads:
+        if src["pro_mode"] == L.PRO_SILU:
+            # a materialised act(x) -- act(temb) of a network whose activation is not SiLU: the gradient of x is dy * act'(x), where
+            # a SiLU network has the SiLU' gate of OP_PROLOGUE_BWD; the apply launch alone, src["act"] travels in the source
+            if e0 is not None or e1 is not None:
+                b.add(L.OP_GN_APPLY_BWD, dict(src=src, dy=e[0], n=n, hw=hw, sums=None, dgamma=None, dbeta=None, scratch=None, slices=1,
+                                              g0=e0[0] if e0 else None, g1=e1[0] if e1 else None,
+                                              acc0=int(e0[1]) if e0 else 0, acc1=int(e1[1]) if e1 else 0), FC_BWD)
+        elif e0 is None and e1 is None and not self.param_grads:
             return
+        else:
+            self._bwd_gn_apply_norm(f, e, e0, e1)
+        if e0:
+            e0[1] = True
+        if e1:
+            e1[1] = True
+
+    def _bwd_gn_apply_norm(self, f, e, e0, e1):
+        """OP_GN_APPLY_BWD of a source with a GroupNorm: dgamma, dbeta and the gradients of the sources that need one"""
+        b, src, n, hw = self.b, f["src"], f["n"], f["hw"]
+        ctot = src["c0"] + src["c1"]
         slices = max(1, min(int(math.ceil(256 / n)), hw // 64)) if hw >= 128 else 1
         b.add(L.OP_GN_APPLY_BWD, dict(
             src=src, dy=e[0], n=n, hw=hw, sums=b.buf(n, src["gn_groups"], 2, name="gn_apply_bwd_sums"),
@@ -329,10 +347,6 @@ class TrainEngine(E.UNetEngine):
             scratch=b.buf(n * slices * ctot * 2, name="gn_apply_bwd_scratch"), slices=slices,
             g0=e0[0] if e0 else None, g1=e1[0] if e1 else None,
             acc0=int(e0[1]) if e0 else 0, acc1=int(e1[1]) if e1 else 0), FC_BWD)
-        if e0:
-            e0[1] = True
-        if e1:
-            e1[1] = True
 
     @staticmethod
     def _gn_bwd_rows(fields):

@@ -635,7 +635,7 @@ int src_ok(const ssde_src& s, const char* who, bool need_x) {
     SSDE_REQUIRE(s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta, "%s: GroupNorm pointers missing", who);
   }
   SSDE_REQUIRE(s.drop_thresh == 0 || s.drop_seed, "%s: dropout seed pointer missing", who);
-  return SSDE_OK;
+  return ssde_src_act_check(s, who, "");
 }
 
 }  // namespace

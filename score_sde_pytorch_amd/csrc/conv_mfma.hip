@@ -545,11 +545,13 @@ const ssde_conv_route kRoutes[] = {
     {"direct", [](const ssde_conv_args*) { return true; }, direct_plan, direct_launch, true},
 };
 
-// The route of a launch.  nullptr (error set): end padding on a route that knows none -- refused here, before any of the route's
-// own checks.  Null arguments go to the direct kernel's row, which reports them.
+// The route of a launch.  nullptr (error set): a source with an activation other than SiLU, or end padding on a route that knows
+// none -- refused here, before any of the route's own checks.  Null arguments go to the direct kernel's row, which reports them.
 const ssde_conv_route* route_of(const ssde_conv_args* a) {
   const ssde_conv_route* r = kRoutes + sizeof(kRoutes) / sizeof(kRoutes[0]) - 1;
   if (!a) return r;
+  // (ssde_src.act: no route's prologue knows an activation but SiLU -- refused for the launch and for the plan queries alike)
+  if (ssde_src_act_check(a->main, "conv", "main ") || ssde_src_act_check(a->aux, "conv", "aux ")) return nullptr;
   for (r = kRoutes; !r->wants(a); ++r) {}        // (the last row wants everything)
   if (a->pad_end != 0 && !r->takes_pad_end) {
     ssde_set_error("conv: pad_end %d with Winograd tile %d (end padding runs on the direct kernel only)", a->pad_end, a->tile);

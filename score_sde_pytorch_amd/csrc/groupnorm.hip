@@ -264,7 +264,9 @@ __global__ __launch_bounds__(kGnThreads) void gn_stats_any_kernel(const GnParams
 }
 
 // ---- GroupNorm as a launch of its own: dst = drop(act(gamma (x - mean) rstd + beta)) ------------------------------------
-// The consumers' prologue (ssde_pro_apply) materialised, for the group widths they refuse.  grid = (pixel runs, n), thread
+// The consumers' prologue (ssde_pro_apply) materialised, for the group widths they refuse and for the activations they do not
+// know (ssde_src.act: the kernels below are instantiated per SSDE_ACT_*, the SiLU instance is the code of ABI 13's first form;
+// SSDE_PRO_SILU is the activation alone, with neither statistics nor affine).  grid = (pixel runs, n), thread
 // (pl, cl) as in the statistics kernels: a thread keeps ONE channel quad for all its pixels, so the statistics of its four
 // channels' groups -- read from a per-workgroup LDS table, one division per channel and workgroup -- gamma and beta live in
 // registers, and the loop is a 16-byte load, the arithmetic and a 16-byte store: one read and one write of the tensor.
@@ -277,7 +279,7 @@ struct GnQuad { float4 mu, rs, gam, bet; const float* src; int Cs; };
 
 // table [2][C] (mean, rstd of every channel's group in image n), then this thread's quad
 __device__ __forceinline__ void gn_quad_table(const GnApplyParams& p, float* tab, int n, int C) {
-  if (p.s.pro_mode == SSDE_PRO_NONE) return;           // a plain copy of the concatenation: no statistics
+  if (p.s.pro_mode != SSDE_PRO_GN && p.s.pro_mode != SSDE_PRO_GN_SILU) return;   // a plain copy of the concatenation, or the activation alone: no statistics
   const int cpg = C / p.s.gn_groups;
   for (int c = threadIdx.x; c < C; c += kGnThreads) {
     const int g = c / cpg;
@@ -288,7 +290,7 @@ __device__ __forceinline__ void gn_quad_table(const GnApplyParams& p, float* tab
 __device__ __forceinline__ GnQuad gn_quad_load(const GnApplyParams& p, const float* tab, int n, int C, int ch) {
   GnQuad q;
   q.mu = q.rs = q.gam = q.bet = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p.s.pro_mode != SSDE_PRO_NONE) {
+  if (p.s.pro_mode == SSDE_PRO_GN || p.s.pro_mode == SSDE_PRO_GN_SILU) {
     q.mu = *reinterpret_cast<const float4*>(tab + ch);
     q.rs = *reinterpret_cast<const float4*>(tab + C + ch);
     q.gam = *reinterpret_cast<const float4*>(p.s.gn_gamma + ch);
@@ -299,6 +301,7 @@ __device__ __forceinline__ GnQuad gn_quad_load(const GnApplyParams& p, const flo
   return q;
 }
 
+template <int ACT>
 __global__ __launch_bounds__(kGnThreads) void gn_apply_kernel(const GnApplyParams p) {
   SSDE_LDS(tab);
   const int n = blockIdx.y, tid = threadIdx.x;
@@ -318,7 +321,7 @@ __global__ __launch_bounds__(kGnThreads) void gn_apply_kernel(const GnApplyParam
       v.z = (v.z - q.mu.z) * q.rs.z * q.gam.z + q.bet.z;
       v.w = (v.w - q.mu.w) * q.rs.w * q.gam.w + q.bet.w;
     }
-    if (pro.silu) { v.x = ssde_silu(v.x); v.y = ssde_silu(v.y); v.z = ssde_silu(v.z); v.w = ssde_silu(v.w); }
+    if (pro.silu) { v.x = ssde_act<ACT>(v.x); v.y = ssde_act<ACT>(v.y); v.z = ssde_act<ACT>(v.z); v.w = ssde_act<ACT>(v.w); }
     if (__builtin_expect(pro.drop, 0)) {
       const uint32_t e0 = ((uint32_t)n * (uint32_t)p.hw + (uint32_t)px) * (uint32_t)C + (uint32_t)ch;
       v.x *= ssde_keep(e0, pro); v.y *= ssde_keep(e0 + 1u, pro); v.z *= ssde_keep(e0 + 2u, pro); v.w *= ssde_keep(e0 + 3u, pro);
@@ -337,7 +340,9 @@ __global__ __launch_bounds__(kGnThreads) void gn_apply_kernel(const GnApplyParam
 }
 
 // ---- its adjoint ------------------------------------------------------------------------------------------------------
-// du = dy * mask * silu'(u) and xhat of one quad of one pixel (SiLU' and the mask recomputed, as in backward.hip)
+// du = dy * mask * act'(u) and xhat of one quad of one pixel (act' and the mask recomputed, as in backward.hip); without a
+// GroupNorm (SSDE_PRO_SILU) u is x itself and xhat is not used
+template <int ACT>
 __device__ __forceinline__ void gn_quad_du(const GnApplyParams& p, const GnQuad& q, const SsdePro& pro, const float4& x, const float4& dy,
                                            int n, int px, int C, int ch, float (&xh)[4], float (&du)[4]) {
   const float xv[4] = {x.x, x.y, x.z, x.w}, dv[4] = {dy.x, dy.y, dy.z, dy.w};
@@ -348,13 +353,14 @@ __device__ __forceinline__ void gn_quad_du(const GnApplyParams& p, const GnQuad&
   for (int k = 0; k < 4; ++k) {
     xh[k] = (xv[k] - mu[k]) * rs[k];
     float d = dv[k];
-    if (pro.silu) d *= ssde_silu_grad(xh[k] * gm[k] + bt[k]);
+    if (pro.silu) d *= ssde_act_grad<ACT>(pro.gn ? xh[k] * gm[k] + bt[k] : xv[k]);
     if (__builtin_expect(pro.drop, 0)) d *= ssde_keep(e0 + (uint32_t)k, pro);
     du[k] = d;
   }
 }
 
 // launch 1: per (image, pixel slice, channel) the sums of du and du * xhat -> scratch [n][slices][C][2]; grid = (slices, n)
+template <int ACT>
 __global__ __launch_bounds__(kGnThreads) void gn_apply_bwd_reduce_kernel(const GnApplyParams p) {
   SSDE_LDS(smem);                                    // [8][kGnThreads] lane sums, then the table [2][C]
   const int n = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x;
@@ -374,7 +380,7 @@ __global__ __launch_bounds__(kGnThreads) void gn_apply_bwd_reduce_kernel(const G
       const float4 x = *reinterpret_cast<const float4*>(q.src + (size_t)px * q.Cs);
       const float4 d = *reinterpret_cast<const float4*>(dy + (size_t)px * C);
       float xh[4], du[4];
-      gn_quad_du(p, q, pro, x, d, n, px, C, ch, xh, du);
+      gn_quad_du<ACT>(p, q, pro, x, d, n, px, C, ch, xh, du);
 #pragma unroll
       for (int k = 0; k < 4; ++k) { db[k] += du[k]; dg[k] += du[k] * xh[k]; }
     }
@@ -436,16 +442,19 @@ __global__ __launch_bounds__(256) void gn_apply_bwd_finish_kernel(const GnApplyP
   }
 }
 
-// launch 3: dx = rstd * (dxh - mean_g(dxh) - xhat * mean_g(dxh * xhat)) into the gradients of p0 / p1; grid = (pixel runs, n)
+// launch 3: dx = rstd * (dxh - mean_g(dxh) - xhat * mean_g(dxh * xhat)) into the gradients of p0 / p1; grid = (pixel runs, n).
+// SSDE_PRO_SILU (no GroupNorm): dx = du, the only launch of the adjoint
+template <int ACT>
 __global__ __launch_bounds__(kGnThreads) void gn_apply_bwd_apply_kernel(const GnApplyParams p) {
   SSDE_LDS(tab);                                     // [2][C] mean, rstd, then [2][C] the group sums of every channel
   const int n = blockIdx.y, tid = threadIdx.x;
-  const int C = p.s.c0 + p.s.c1, CL = C >> 2, PL = kGnThreads / CL, cpg = C / p.s.gn_groups;
+  const bool has_gn = p.s.pro_mode == SSDE_PRO_GN || p.s.pro_mode == SSDE_PRO_GN_SILU;
+  const int C = p.s.c0 + p.s.c1, CL = C >> 2, PL = kGnThreads / CL, cpg = has_gn ? C / p.s.gn_groups : C;
   gn_quad_table(p, tab, n, C);
   for (int c = tid; c < C; c += kGnThreads) {
     const int g = c / cpg;
-    tab[2 * C + c] = p.sums[((size_t)n * p.s.gn_groups + g) * 2];
-    tab[3 * C + c] = p.sums[((size_t)n * p.s.gn_groups + g) * 2 + 1];
+    tab[2 * C + c] = has_gn ? p.sums[((size_t)n * p.s.gn_groups + g) * 2] : 0.f;
+    tab[3 * C + c] = has_gn ? p.sums[((size_t)n * p.s.gn_groups + g) * 2 + 1] : 0.f;
   }
   __syncthreads();
   if (tid >= CL * PL) return;
@@ -465,9 +474,9 @@ __global__ __launch_bounds__(kGnThreads) void gn_apply_bwd_apply_kernel(const Gn
     const float4 x = *reinterpret_cast<const float4*>(q.src + (size_t)px * q.Cs);
     const float4 d = *reinterpret_cast<const float4*>(dy + (size_t)px * C);
     float xh[4], du[4], r[4];
-    gn_quad_du(p, q, pro, x, d, n, px, C, ch, xh, du);
+    gn_quad_du<ACT>(p, q, pro, x, d, n, px, C, ch, xh, du);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = rs[k] * (du[k] * gm[k] - sa[k] - xh[k] * sb[k]);
+    for (int k = 0; k < 4; ++k) r[k] = pro.gn ? rs[k] * (du[k] * gm[k] - sa[k] - xh[k] * sb[k]) : du[k];
     float4* o = reinterpret_cast<float4*>(g + (size_t)px * q.Cs);
     float4 v = make_float4(r[0], r[1], r[2], r[3]);
     if (acc) { const float4 t = *o; v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
@@ -519,7 +528,8 @@ extern "C" int ssde_groupnorm_stats(const ssde_gn_stats_args* a, void* stream) {
 static int gn_apply_check(const ssde_src& s, int n, int hw, bool copy_ok, const char* what) {
   const int C = s.c0 + s.c1;
   const bool gn = s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU;
-  SSDE_REQUIRE(gn || (copy_ok && s.pro_mode == SSDE_PRO_NONE), "%s: prologue mode %d is not handled", what, s.pro_mode);
+  SSDE_REQUIRE(gn || s.pro_mode == SSDE_PRO_SILU || (copy_ok && s.pro_mode == SSDE_PRO_NONE), "%s: prologue mode %d is not handled", what, s.pro_mode);
+  SSDE_REQUIRE(s.act >= SSDE_ACT_SILU && s.act <= SSDE_ACT_LRELU, "%s: activation %d (src.act) is none of SSDE_ACT_*", what, s.act);
   SSDE_REQUIRE(s.p0 && (!gn || (s.gn_mean && s.gn_rstd && s.gn_gamma && s.gn_beta)), "%s: null args", what);
   SSDE_REQUIRE(s.c0 > 0 && s.c0 % 4 == 0 && s.c1 >= 0 && s.c1 % 4 == 0 && C <= 4 * kGnThreads, "%s: bad channel counts %d + %d", what, s.c0, s.c1);
   SSDE_REQUIRE(s.c1 == 0 || s.p1, "%s: second tensor missing", what);
@@ -535,6 +545,14 @@ static int gn_apply_px_per_wg(int C, int hw) {
   while (ssde_cdiv(hw, px) > 65535) px *= 2;
   return px;
 }
+// the instantiation of a kernel template for src.act (checked by gn_apply_check: one of SSDE_ACT_*)
+#define GN_LAUNCH_ACT(kernel, act, ...)                                                          \
+  switch (act) {                                                                                 \
+    case SSDE_ACT_ELU: hipLaunchKernelGGL(kernel<SSDE_ACT_ELU>, __VA_ARGS__); break;             \
+    case SSDE_ACT_RELU: hipLaunchKernelGGL(kernel<SSDE_ACT_RELU>, __VA_ARGS__); break;           \
+    case SSDE_ACT_LRELU: hipLaunchKernelGGL(kernel<SSDE_ACT_LRELU>, __VA_ARGS__); break;         \
+    default: hipLaunchKernelGGL(kernel<SSDE_ACT_SILU>, __VA_ARGS__); break;                      \
+  }
 
 extern "C" int ssde_gn_apply(const ssde_gn_apply_args* a, void* stream) {
   SSDE_REQUIRE(a && a->dst, "gn_apply: null args");
@@ -543,32 +561,37 @@ extern "C" int ssde_gn_apply(const ssde_gn_apply_args* a, void* stream) {
   GnApplyParams p{};
   p.s = a->src; p.n = a->n; p.hw = a->hw; p.dst = a->dst;
   p.px_per_wg = gn_apply_px_per_wg(C, a->hw);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(ssde_cdiv(a->hw, p.px_per_wg), a->n), dim3(kGnThreads), 2 * C * sizeof(float),
-                     static_cast<hipStream_t>(stream), p);
+  GN_LAUNCH_ACT(gn_apply_kernel, a->src.act, dim3(ssde_cdiv(a->hw, p.px_per_wg), a->n), dim3(kGnThreads), 2 * C * sizeof(float),
+                static_cast<hipStream_t>(stream), p);
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
 }
 
 extern "C" int ssde_gn_apply_bwd(const ssde_gn_apply_bwd_args* a, void* stream) {
-  SSDE_REQUIRE(a && a->dy && a->sums && a->scratch, "gn_apply_bwd: null args");
+  SSDE_REQUIRE(a && a->dy, "gn_apply_bwd: null args");
   if (int rc = gn_apply_check(a->src, a->n, a->hw, false, "gn_apply_bwd")) return rc;
+  const bool act_only = a->src.pro_mode == SSDE_PRO_SILU;
+  SSDE_REQUIRE(act_only || (a->sums && a->scratch), "gn_apply_bwd: null args");
+  SSDE_REQUIRE(!act_only || (!a->dgamma && !a->dbeta && (a->g0 || a->g1)), "gn_apply_bwd: SSDE_PRO_SILU has no dgamma / dbeta and needs g0 or g1");
   SSDE_REQUIRE((a->dgamma == nullptr) == (a->dbeta == nullptr), "gn_apply_bwd: dgamma and dbeta go together");
-  SSDE_REQUIRE(a->slices >= 1 && a->slices <= 65535, "gn_apply_bwd: bad slice count %d", a->slices);
+  SSDE_REQUIRE(act_only || (a->slices >= 1 && a->slices <= 65535), "gn_apply_bwd: bad slice count %d", a->slices);
   SSDE_REQUIRE(a->g1 == nullptr || a->src.c1 > 0, "gn_apply_bwd: g1 without a second tensor");
   const int C = a->src.c0 + a->src.c1;
   hipStream_t st = static_cast<hipStream_t>(stream);
   GnApplyParams p{};
   p.s = a->src; p.n = a->n; p.hw = a->hw; p.dy = a->dy; p.sums = a->sums; p.scratch = a->scratch; p.slices = a->slices;
-  hipLaunchKernelGGL(gn_apply_bwd_reduce_kernel, dim3(a->slices, a->n), dim3(kGnThreads), (8 * kGnThreads + 2 * C) * sizeof(float), st, p);
-  SSDE_LAUNCH_CHECK();
-  GnApplyParams f = p;
-  f.g0 = a->dbeta; f.g1 = a->dgamma;
-  hipLaunchKernelGGL(gn_apply_bwd_finish_kernel, dim3(a->n * a->src.gn_groups + (a->dgamma ? C : 0)), dim3(256), 256 * 2 * sizeof(float), st, f);
-  SSDE_LAUNCH_CHECK();
+  if (!act_only) {
+    GN_LAUNCH_ACT(gn_apply_bwd_reduce_kernel, a->src.act, dim3(a->slices, a->n), dim3(kGnThreads), (8 * kGnThreads + 2 * C) * sizeof(float), st, p);
+    SSDE_LAUNCH_CHECK();
+    GnApplyParams f = p;
+    f.g0 = a->dbeta; f.g1 = a->dgamma;
+    hipLaunchKernelGGL(gn_apply_bwd_finish_kernel, dim3(a->n * a->src.gn_groups + (a->dgamma ? C : 0)), dim3(256), 256 * 2 * sizeof(float), st, f);
+    SSDE_LAUNCH_CHECK();
+  }
   if (a->g0 || a->g1) {
     p.g0 = a->g0; p.g1 = a->g1; p.acc0 = a->acc0; p.acc1 = a->acc1;
     p.px_per_wg = gn_apply_px_per_wg(C, a->hw);
-    hipLaunchKernelGGL(gn_apply_bwd_apply_kernel, dim3(ssde_cdiv(a->hw, p.px_per_wg), a->n), dim3(kGnThreads), 4 * C * sizeof(float), st, p);
+    GN_LAUNCH_ACT(gn_apply_bwd_apply_kernel, a->src.act, dim3(ssde_cdiv(a->hw, p.px_per_wg), a->n), dim3(kGnThreads), 4 * C * sizeof(float), st, p);
     SSDE_LAUNCH_CHECK();
   }
   return SSDE_OK;

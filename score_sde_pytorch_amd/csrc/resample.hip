@@ -340,6 +340,7 @@ int pow2_ceil(int v) { int q = 1; while (q < v) q *= 2; return q; }
 extern "C" int ssde_upfirdn2d(const ssde_upfirdn_args* a, void* stream) {
   SSDE_REQUIRE(a && a->src.p0 && a->dst, "upfirdn2d: null args");
   SSDE_REQUIRE(a->src.p1 == nullptr && a->src.c1 == 0, "upfirdn2d: concatenated source not supported");
+  if (int rc = ssde_src_act_check(a->src, "upfirdn2d", "")) return rc;
   SSDE_REQUIRE(a->c > 0 && a->c % 4 == 0 && a->src.c0 == a->c, "upfirdn2d: channels must be a multiple of 4 and match src.c0");
   SSDE_REQUIRE(a->kh >= 1 && a->kh <= SSDE_FIR_MAX_TAPS && a->kw >= 1 && a->kw <= SSDE_FIR_MAX_TAPS,
                "upfirdn2d: kernel %dx%d, at most %dx%d taps", a->kh, a->kw, SSDE_FIR_MAX_TAPS, SSDE_FIR_MAX_TAPS);

@@ -111,6 +111,13 @@ static inline int ssde_src_check(const ssde_src& s, const char* route, const cha
   SSDE_REQUIRE(!(checks & SSDE_SRC_SEED) || s.drop_thresh == 0 || s.drop_seed, "%s: %sdropout seed pointer missing", route, what);
   return SSDE_OK;
 }
+// ssde_src.act: the prologues the consumers fuse are SiLU only.  Every entry point that reads an ssde_src -- all but ssde_gn_apply /
+// ssde_gn_apply_bwd, which run the other activations -- refuses a non-zero word here, by its own name, before any launch.
+static inline int ssde_src_act_check(const ssde_src& s, const char* entry, const char* what) {
+  SSDE_REQUIRE(s.act == SSDE_ACT_SILU, "%s: %ssource asks for activation %d (src.act); this entry point applies SiLU only -- "
+               "materialise the source with ssde_gn_apply", entry, what, s.act);
+  return SSDE_OK;
+}
 
 // ---- host helpers of the weight-gradient routes ---------------------------------------------------------------------
 // SSDE_WGRADF_* -> the Winograd forms a launch may take: 0 = none (_DIRECT), 2 = F(2x2,3x3) wherever legal (_F2), 44 = F(4x4,3x3)
@@ -330,6 +337,23 @@ __device__ __forceinline__ float ssde_silu(float x) {
 __device__ __forceinline__ float ssde_silu_grad(float u) {
   const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-u));
   return sg * (1.0f + u * (1.0f - sg));
+}
+// The activation A (SSDE_ACT_*, ssde_src.act) and its derivative, torch's conventions (get_act, models/layers.py:29-41: nn.ELU(),
+// nn.ReLU(), nn.LeakyReLU(0.2)): ELU' = exp(u), ReLU' = 0, LeakyReLU' = 0.2 at u <= 0.  expm1f, not expf(u) - 1, which cancels
+// near 0.  A = SSDE_ACT_SILU is ssde_silu / ssde_silu_grad themselves.
+template <int A>
+__device__ __forceinline__ float ssde_act(float u) {
+  if constexpr (A == SSDE_ACT_ELU) return u > 0.f ? u : expm1f(u);
+  else if constexpr (A == SSDE_ACT_RELU) return u > 0.f ? u : 0.f;
+  else if constexpr (A == SSDE_ACT_LRELU) return u > 0.f ? u : 0.2f * u;
+  else return ssde_silu(u);
+}
+template <int A>
+__device__ __forceinline__ float ssde_act_grad(float u) {
+  if constexpr (A == SSDE_ACT_ELU) return u > 0.f ? 1.0f : expf(u);
+  else if constexpr (A == SSDE_ACT_RELU) return u > 0.f ? 1.0f : 0.f;
+  else if constexpr (A == SSDE_ACT_LRELU) return u > 0.f ? 1.0f : 0.2f;
+  else return ssde_silu_grad(u);
 }
 
 // ---- prologue (GroupNorm apply, SiLU, dropout) shared by every kernel that stages a source ----

@@ -529,7 +529,7 @@ int wgrad_args_check(const ssde_wgrad_args* a) {
   }
   if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU)
     SSDE_REQUIRE(s.gn_groups > 0 && Ctot % s.gn_groups == 0 && (Ctot / s.gn_groups) % 4 == 0, "wgrad: GroupNorm channels-per-group %% 4");
-  return SSDE_OK;
+  return ssde_src_act_check(s, "wgrad", "");
 }
 
 // ---- the table: the first route that wants a launch gets it ----

@@ -19,6 +19,8 @@ Fusions encoded in the program (per ResnetBlockBigGANpp, models/layerspp.py:242-
 A GroupNorm whose channels-per-group is no multiple of 4 (nn.GroupNorm(min(C // 4, 32), C) on 192 = 128 + 64 channels: 32 groups
 of 6 -- the 1024-px configs, layerspp.py:219,231) is NOT fused: no consumer's prologue accepts a channel quad that spans two
 groups.  It runs as launches of its own (statistics pass + ssde_gn_apply) and its consumers read a plain tensor (Lowering.src).
+So does every act(GroupNorm(x)) and act(temb) of a network whose nonlinearity is elu, relu or lrelu (get_act, models/layers.py:29-41):
+the fused prologues are SiLU, the apply launch evaluates the others (ssde_src.act).
 """
 import ctypes as C
 import math
@@ -677,9 +679,9 @@ class WeightStore:
 
 
 # --------------------------------------------------------------------------- lowering helpers
-def _src(t, c, t2=None, c2=0, pro=L.PRO_NONE, gn=None, drop=None):
+def _src(t, c, t2=None, c2=0, pro=L.PRO_NONE, gn=None, drop=None, act=L.ACT_SILU):
     d = dict(p0=t, p1=t2, c0=c, c1=c2, pro_mode=pro, gn_groups=0, gn_mean=None, gn_rstd=None, gn_gamma=None, gn_beta=None,
-             drop_thresh=0, drop_scale=1.0, drop_seed=None, drop_salt=0)
+             drop_thresh=0, drop_scale=1.0, drop_seed=None, drop_salt=0, act=act)
     if gn is not None:
         d.update(gn_groups=gn["groups"], gn_mean=gn["mean"], gn_rstd=gn["rstd"], gn_gamma=gn["gamma"], gn_beta=gn["beta"])
         d["_gn"] = gn        # (lowering-time only: the statistics may still be partials, Lowering._materialize_stats)
@@ -691,7 +693,7 @@ def _src(t, c, t2=None, c2=0, pro=L.PRO_NONE, gn=None, drop=None):
 
 
 _NOSRC = dict(p0=None, p1=None, c0=0, c1=0, pro_mode=0, gn_groups=0, gn_mean=None, gn_rstd=None, gn_gamma=None, gn_beta=None,
-              drop_thresh=0, drop_scale=1.0, drop_seed=None, drop_salt=0)
+              drop_thresh=0, drop_scale=1.0, drop_seed=None, drop_salt=0, act=L.ACT_SILU)
 
 
 def fir_taps(k, gain=1.0):
@@ -708,6 +710,9 @@ class Lowering:
 
     def __init__(self, builder, weights, batch):
         self.b, self.w, self.n = builder, weights, batch
+        # the model's activation (L.ACT_*; UNetEngine sets it from model.act_kind).  Only OP_GN_APPLY / OP_GN_APPLY_BWD run one that
+        # is not SiLU: src() materialises every prologue with an activation for such a network
+        self.act = L.ACT_SILU
         self.parts = {}      # id(activation Buf) -> (partials Buf, slices per image, channels): written by its producer's epilogue
         # compute units of the device the program will run on: the kernel choice below asks "does this launch fill the
         # chip?" (256 on the MI355X; also the value used for CPU dry lowering).  SSDE_NUM_CUS overrides (tests)
@@ -735,6 +740,7 @@ class Lowering:
             dst.p0 = dummy if src["p0"] is not None else None
             dst.p1 = dummy if src["p1"] is not None else None
             dst.c0, dst.c1, dst.pro_mode, dst.gn_groups = src["c0"], src["c1"], src["pro_mode"], src["gn_groups"]
+            dst.act = src.get("act", L.ACT_SILU)
             if src["gn_groups"]:
                 dst.gn_mean = dst.gn_rstd = dst.gn_gamma = dst.gn_beta = dummy
             if src["drop_thresh"]:
@@ -787,13 +793,17 @@ class Lowering:
         tensor of c + c2 channels -- and the consumer (whichever 3x3 route, the resampler, the 1x1 GEMM, conv_small) gets a
         plain source; so do its weight gradient and its input gradient (backward.TrainEngine._bwd_gn_apply is the adjoint).
         The same launch materialises a concatenation whose boundary the matrix kernels refuse (c % 32 != 0: 16 + 16 channels at
-        the top level of the nf = 16 networks), with or without a GroupNorm."""
-        if not (gn is not None and gn.get("narrow")) and not (t2 is not None and c % 32 != 0):
+        the top level of the nf = 16 networks), with or without a GroupNorm -- and every prologue that contains an activation
+        when the model's is not SiLU (self.act: the fused prologues know SiLU only; the word travels in the launch's source and
+        nowhere else, the time embedding's act(temb) included: pro = PRO_SILU, hw = 1)."""
+        other_act = self.act != L.ACT_SILU and pro in (L.PRO_GN_SILU, L.PRO_SILU)
+        if not (gn is not None and gn.get("narrow")) and not (t2 is not None and c % 32 != 0) and not other_act:
             return _src(t, c, t2, c2, pro=pro, gn=gn, drop=drop)
         self._materialize_stats(gn)
         ctot = c + c2
         dst = self.b.buf(self.n, hw, ctot, name="gn_applied")
-        self.b.add(L.OP_GN_APPLY, dict(src=_src(t, c, t2, c2, pro=pro, gn=gn, drop=drop), n=self.n, hw=hw, dst=dst), FC_GN)
+        self.b.add(L.OP_GN_APPLY, dict(src=_src(t, c, t2, c2, pro=pro, gn=gn, drop=drop, act=self.act if other_act else L.ACT_SILU),
+                                       n=self.n, hw=hw, dst=dst), FC_GN)
         return _src(dst, ctot)
 
     def _materialize_stats(self, gn, fields=None):
@@ -998,6 +1008,7 @@ class UNetEngine:
         self.b = ProgramBuilder(device)
         self.weights = WeightStore(device)
         self.low = Lowering(self.b, self.weights, batch)
+        self.low.act = getattr(model, "act_kind", L.ACT_SILU)
         # a training program with parameter gradients (backward.TrainEngine sets param_grads before lowering): the forward
         # F(4x4,3x3) launches leave their transformed input behind for the weight gradients
         self.low.emit_wino_v = bool(getattr(self, "param_grads", False))
@@ -1080,7 +1091,9 @@ class UNetEngine:
             low.conv(t0, 1, 1, 4 * nf, aux=_src(emb, emb_dim), w_aux=self.weights.matrix([(lin0.weight, False)]),
                      bias=self.weights.vector([lin0.bias]))
             temb = b.buf(n, 4 * nf, name="temb", persistent=True)
-            low.conv(temb, 1, 1, 4 * nf, aux=_src(t0, 4 * nf, pro=L.PRO_SILU),
+            # (act(t0) and act(temb): fused into the GEMMs for SiLU; any other activation is materialised by low.src -- once per
+            #  evaluation, inside the conditioning chain: the Dense_0 projections of all blocks are one GEMM, one reader)
+            low.conv(temb, 1, 1, 4 * nf, aux=low.src(t0, 4 * nf, 1, pro=L.PRO_SILU),
                      w_aux=self.weights.matrix([(lin1.weight, False)]),
                      bias=self.weights.vector([lin1.bias]))
             # every Dense_0(act(temb)) of every residual block as ONE GEMM (layerspp.py:263)
@@ -1093,7 +1106,7 @@ class UNetEngine:
             wd = self.weights.matrix([(d.weight, False) for d in dense])
             bd = self.weights.vector([d.bias for d in dense])
             self._tproj = b.buf(n, off, name="tproj", persistent=True)
-            low.conv(self._tproj, 1, 1, off, aux=_src(temb, 4 * nf, pro=L.PRO_SILU), w_aux=wd, bias=bd)
+            low.conv(self._tproj, 1, 1, off, aux=low.src(temb, 4 * nf, 1, pro=L.PRO_SILU), w_aux=wd, bias=bd)
         self._cond_specs = len(b.specs)            # the leading specs that read nothing but the noise level
         return idx
 

@@ -27,10 +27,10 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-def _fill_src(s, t, t2=None, pro=L.PRO_NONE, gn=None):
+def _fill_src(s, t, t2=None, pro=L.PRO_NONE, gn=None, act=L.ACT_SILU):
     s.p0, s.c0 = _p(t), t.shape[-1]
     s.p1, s.c1 = (_p(t2), t2.shape[-1]) if t2 is not None else (None, 0)
-    s.pro_mode = pro
+    s.pro_mode, s.act = pro, act
     if gn is not None:
         mean, rstd, gamma, beta, groups = gn
         s.gn_groups, s.gn_mean, s.gn_rstd, s.gn_gamma, s.gn_beta = groups, _p(mean), _p(rstd), _p(gamma), _p(beta)
@@ -64,32 +64,45 @@ def _fill_drop(s, drop):
         s.drop_seed, s.drop_salt = _p(seed_t), salt & 0xFFFFFFFF
 
 
-def groupnorm_apply(x, gn, x2=None, silu=True, drop=None):
+def _apply_mode(gn, silu):
+    """the prologue mode of the two apply wrappers: gn=None is the activation alone (SSDE_PRO_SILU)"""
+    if gn is None:
+        if not silu:
+            raise ValueError("groupnorm_apply without a GroupNorm and without an activation is a copy")
+        return L.PRO_SILU
+    return L.PRO_GN_SILU if silu else L.PRO_GN
+
+
+def groupnorm_apply(x, gn, x2=None, silu=True, drop=None, act=L.ACT_SILU):
     """drop(act(GroupNorm(cat(x, x2)))) as one contiguous NHWC tensor (ssde_gn_apply): the launch that stands in for the
-    consumers' fused prologue where channels-per-group is no multiple of 4.  gn = (mean, rstd, gamma, beta, groups)."""
+    consumers' fused prologue where channels-per-group is no multiple of 4, or where the activation is not SiLU.
+    gn = (mean, rstd, gamma, beta, groups), or None for the activation alone; silu=False: no activation; act: L.ACT_*."""
     _need_cuda(x, x2)
     n, hw = x.shape[0], int(np.prod(x.shape[1:-1]))
     c = x.shape[-1] + (x2.shape[-1] if x2 is not None else 0)
     out = torch.empty(tuple(x.shape[:-1]) + (c,), device=x.device)
     a = L.GnApplyArgs()
-    _fill_src(a.src, x, x2, L.PRO_GN_SILU if silu else L.PRO_GN, gn)
+    _fill_src(a.src, x, x2, _apply_mode(gn, silu), gn, act)
     _fill_drop(a.src, drop)
     a.n, a.hw, a.dst = n, hw, _p(out)
     L.check(L.load().ssde_gn_apply(C.byref(a), _stream()), "ssde_gn_apply")
     return out
 
 
-def groupnorm_apply_bwd(dy, x, gn, x2=None, silu=True, drop=None, slices=1, g0=None, g1=None):
-    """Adjoint of groupnorm_apply (ssde_gn_apply_bwd): returns (dx, dx2, dgamma, dbeta); g0 / g1 given = accumulate into them."""
+def groupnorm_apply_bwd(dy, x, gn, x2=None, silu=True, drop=None, slices=1, g0=None, g1=None, act=L.ACT_SILU):
+    """Adjoint of groupnorm_apply (ssde_gn_apply_bwd): returns (dx, dx2, dgamma, dbeta); g0 / g1 given = accumulate into them.
+    gn=None (the activation alone): dgamma and dbeta are None."""
     _need_cuda(dy, x, x2)
     n, hw = x.shape[0], int(np.prod(x.shape[1:-1]))
     c = dy.shape[-1]
     a = L.GnApplyBwdArgs()
-    _fill_src(a.src, x, x2, L.PRO_GN_SILU if silu else L.PRO_GN, gn)
+    _fill_src(a.src, x, x2, _apply_mode(gn, silu), gn, act)
     _fill_drop(a.src, drop)
-    sums = torch.empty(n, gn[4], 2, device=x.device)
-    scratch = torch.empty(n * slices * c * 2, device=x.device)
-    dgamma, dbeta = torch.empty(c, device=x.device), torch.empty(c, device=x.device)
+    sums = scratch = dgamma = dbeta = None
+    if gn is not None:
+        sums = torch.empty(n, gn[4], 2, device=x.device)
+        scratch = torch.empty(n * slices * c * 2, device=x.device)
+        dgamma, dbeta = torch.empty(c, device=x.device), torch.empty(c, device=x.device)
     a.acc0, a.acc1 = int(g0 is not None), int(g1 is not None)
     g0 = torch.empty_like(x) if g0 is None else g0
     g1 = (torch.empty_like(x2) if g1 is None else g1) if x2 is not None else None

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import utils
+from .. import _lib
 
 
 # --------------------------------------------------------------------------- init
@@ -206,8 +207,11 @@ class NCSNpp(HipUNet):
         super().__init__()
         self.config = config
         m = config.model
-        if m.nonlinearity.lower() != "swish":
-            raise NotImplementedError("the HIP path fuses SiLU; nonlinearity=%r is not built" % m.nonlinearity)
+        # get_act (models/layers.py:29-41): 'swish', 'elu', 'relu' or 'lrelu' (LeakyReLU, slope 0.2), case-insensitive.  The consumers
+        # fuse SiLU; any other activation runs in the apply launch (engine.Lowering.src, ssde_src.act)
+        if m.nonlinearity.lower() not in _lib.ACT_BY_NAME:
+            raise NotImplementedError("activation function does not exist!")
+        self.act_kind = _lib.ACT_BY_NAME[m.nonlinearity.lower()]
         if m.resblock_type.lower() != "biggan":
             raise NotImplementedError("resblock_type=%r: every shipped ncsnpp config uses 'biggan'" % m.resblock_type)
         self.register_buffer("sigmas", torch.tensor(utils.get_sigmas(config)))

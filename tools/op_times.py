@@ -1,6 +1,11 @@
 #!/usr/bin/env python
 """Per-launch HIP-event times of ONE U-Net evaluation (default: the CIFAR-10 NCSN++ sampler at batch 256; any preset of either model family) (GPU only): every op of the
-lowered program with its kind, shape and ms, the list sorted by time, and the sums per (kind, shape).  What to look at next."""
+lowered program with its kind, shape and ms, the list sorted by time, and the sums per (kind, shape).  What to look at next.
+
+    python tools/op_times.py [batch [preset | small [nonlinearity]]]
+
+`small` is tests/_util.small_config(); nonlinearity overrides config.model.nonlinearity (swish, elu, relu, lrelu: what the apply
+launches of a non-swish network cost next to the swish one)."""
 import collections
 import os
 import sys
@@ -39,8 +44,8 @@ def describe(op):
         return "gn_stats c %d+%d hw %d (%.1f MB read)" % (a.c0, a.c1, a.hw, 4e-6 * a.n * a.hw * (a.c0 + a.c1))
     if k == L.OP_GN_APPLY:
         a = op.u.gn_apply
-        return "gn_apply%s c %d+%d hw %d (%.1f MB read + as much written)" % (" (copy)" if a.src.pro_mode == L.PRO_NONE else "", a.src.c0, a.src.c1,
-                                                                            a.hw, 4e-6 * a.n * a.hw * (a.src.c0 + a.src.c1))
+        what = " (copy)" if a.src.pro_mode == L.PRO_NONE else " (act only)" if a.src.pro_mode == L.PRO_SILU else ""
+        return "gn_apply%s c %d+%d hw %d (%.1f MB read + as much written)" % (what, a.src.c0, a.src.c1, a.hw, 4e-6 * a.n * a.hw * (a.src.c0 + a.src.c1))
     return KIND.get(k, str(k))
 
 
@@ -48,7 +53,10 @@ if __name__ == "__main__":
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     dev = torch.device("cuda")
     name = sys.argv[2] if len(sys.argv) > 2 else "ve/cifar10_ncsnpp_continuous"      # e.g. 16 ve/ffhq_256_ncsnpp_continuous, 256 vp/ddpm/cifar10
-    cfg = _util.cfgs.get_config(name)
+    cfg = _util.small_config() if name == "small" else _util.cfgs.get_config(name)
+    if len(sys.argv) > 3:
+        cfg.model.nonlinearity = sys.argv[3]
+        name += ", nonlinearity " + sys.argv[3]
     R = cfg.data.image_size
     torch.manual_seed(0)
     model = mutils.get_model(cfg.model.name)(cfg)
