@@ -516,8 +516,8 @@ __global__ __launch_bounds__(256) void perturb_kernel(const float* __restrict__ 
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (size_t)gridDim.x * blockDim.x) {
     const int n = (int)(i / per);
     // mean + std[:, None, None, None] * z  (losses.py:86-87); mean = a[n] * x
-    const float mean = a ? __fmul_rn(a[n], x[i]) : x[i];
-    dst[i] = __fadd_rn(mean, __fmul_rn(s[n], z[i]));
+    const float mean = a ? ssde_fmul_rn(a[n], x[i]) : x[i];
+    dst[i] = ssde_fadd_rn(mean, ssde_fmul_rn(s[n], z[i]));
   }
 }
 
@@ -536,7 +536,7 @@ __global__ __launch_bounds__(256) void dsm_loss_kernel(const float* __restrict__
   float acc = 0.f;
   for (int i = tid; i < per; i += 256) {
     const size_t k = (size_t)n * per + i;
-    const float r = lw ? __fadd_rn(score[k], __fdiv_rn(z[k], sd)) : __fadd_rn(__fmul_rn(score[k], sd), z[k]);
+    const float r = lw ? ssde_fadd_rn(score[k], ssde_fdiv_rn(z[k], sd)) : ssde_fadd_rn(ssde_fmul_rn(score[k], sd), z[k]);
     acc += r * r;
     if (dscore) dscore[k] = r * gfac;
   }
@@ -836,6 +836,7 @@ extern "C" int ssde_dsm_loss(const ssde_dsm_loss_args* a, void* stream) {
 
 extern "C" int ssde_sumsq_flat(const ssde_sumsq_flat_args* a, void* stream) {
   SSDE_REQUIRE(a && a->x && a->partial && a->out && a->numel > 0, "sumsq_flat: bad args (partial needs %d floats)", kSumsqBlocks);
+  SSDE_REQUIRE(reinterpret_cast<uintptr_t>(a->x) % 16 == 0, "sumsq_flat: x must be 16-byte aligned (it is read as float4)");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int blocks = (int)grid_for((size_t)a->numel / 4, 256, kSumsqBlocks);
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(blocks), dim3(256), 64, st, a->x, (size_t)a->numel, a->partial);

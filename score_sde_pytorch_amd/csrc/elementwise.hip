@@ -1,8 +1,8 @@
 // HBM-bound glue kernels of the hot path: time embeddings, NCHW<->NHWC boundary,
 // fused bias+activation, and the predictor/corrector state update.
 // Reference lines are cited per kernel.  Arithmetic that the parity tests compare
-// bit-for-bit against the reference's torch expression order uses __fmul_rn /
-// __fadd_rn so hipcc cannot contract it into FMAs.
+// bit-for-bit against the reference's torch expression order uses ssde_fmul_rn /
+// ssde_fadd_rn (ssde_common.h) so hipcc cannot contract it into FMAs.
 #include "ssde_common.h"
 #include <math.h>
 #include <string.h>
@@ -24,9 +24,9 @@ __global__ void embed_kernel(const float* __restrict__ cond, const float* __rest
   float arg;
   if (kind == 0) {
     const float x = logf(cond[b]);
-    arg = __fmul_rn(__fmul_rn(__fmul_rn(x, w[j]), 2.0f), 3.14159265358979323846f);
+    arg = ssde_fmul_rn(ssde_fmul_rn(ssde_fmul_rn(x, w[j]), 2.0f), 3.14159265358979323846f);
   } else {
-    arg = __fmul_rn(cond[b], w[j]);
+    arg = ssde_fmul_rn(cond[b], w[j]);
   }
   dst[(size_t)b * dim + j] = sinf(arg);
   dst[(size_t)b * dim + half + j] = cosf(arg);
@@ -41,11 +41,11 @@ __global__ void to_nhwc_kernel(const float* __restrict__ src, float* __restrict_
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const size_t img = idx / hw, pix = idx - img * hw;
     float f = a;
-    if (mode == 1) f = __fdiv_rn(a, vec[img]);
-    else if (mode == 2) f = __fdiv_rn(-a, vec[img]);
+    if (mode == 1) f = ssde_fdiv_rn(a, vec[img]);
+    else if (mode == 2) f = ssde_fdiv_rn(-a, vec[img]);
     for (int ch = 0; ch < c_pad; ++ch) {
       float v = 0.f;
-      if (ch < c) v = __fadd_rn(__fmul_rn(f, src[(img * c + ch) * hw + pix]), b);
+      if (ch < c) v = ssde_fadd_rn(ssde_fmul_rn(f, src[(img * c + ch) * hw + pix]), b);
       dst[idx * c_pad + ch] = v;
     }
   }
@@ -62,9 +62,9 @@ __global__ void to_nchw_kernel(const float* __restrict__ src, float* __restrict_
     const int ch = (int)(t % c);
     const size_t img = t / c;
     float x = src[(img * hw + pix) * c_src + ch];
-    if (mode == 1) x = __fdiv_rn(x, v[img]);
-    else if (mode == 2) x = __fdiv_rn(-x, v[img]);
-    if (alpha != 1.0f) x = __fmul_rn(alpha, x);
+    if (mode == 1) x = ssde_fdiv_rn(x, v[img]);
+    else if (mode == 2) x = ssde_fdiv_rn(-x, v[img]);
+    if (alpha != 1.0f) x = ssde_fmul_rn(alpha, x);
     dst[idx] = accumulate ? dst[idx] + x : x;
   }
 }
@@ -150,17 +150,17 @@ __global__ __launch_bounds__(256) void langevin_kernel(float* __restrict__ x, fl
     const float gn = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)n;
     const float zn = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)n;
     const float alpha = alpha_tab ? alpha_tab[step_ptr ? *step_ptr : 0] : 1.0f;
-    const float r = __fdiv_rn(__fmul_rn(snr, zn), gn);
-    const float step = __fmul_rn(__fmul_rn(__fmul_rn(r, r), 2.0f), alpha);
+    const float r = ssde_fdiv_rn(ssde_fmul_rn(snr, zn), gn);
+    const float step = ssde_fmul_rn(ssde_fmul_rn(ssde_fmul_rn(r, r), 2.0f), alpha);
     s_step[0] = step;
-    s_step[1] = sqrtf(__fmul_rn(step, 2.0f));
+    s_step[1] = sqrtf(ssde_fmul_rn(step, 2.0f));
   }
   __syncthreads();
   const float step = s_step[0], nz = s_step[1];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + tid; i < numel; i += (size_t)gridDim.x * blockDim.x) {
-    const float xm = __fadd_rn(x[i], __fmul_rn(step, g[i]));
+    const float xm = ssde_fadd_rn(x[i], ssde_fmul_rn(step, g[i]));
     x_mean[i] = xm;
-    x[i] = __fadd_rn(xm, __fmul_rn(nz, z[i]));
+    x[i] = ssde_fadd_rn(xm, ssde_fmul_rn(nz, z[i]));
   }
 }
 
@@ -174,10 +174,10 @@ __global__ __launch_bounds__(256) void predictor_kernel(float* __restrict__ x, f
   const int st = step_ptr ? *step_ptr : 0;
   const float a = coef[3 * st], b = coef[3 * st + 1], c = coef[3 * st + 2];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (size_t)gridDim.x * blockDim.x) {
-    const float xa = (a == 1.0f) ? x[i] : __fmul_rn(a, x[i]);
-    const float xm = __fadd_rn(xa, __fmul_rn(b, s[i]));
+    const float xa = (a == 1.0f) ? x[i] : ssde_fmul_rn(a, x[i]);
+    const float xm = ssde_fadd_rn(xa, ssde_fmul_rn(b, s[i]));
     x_mean[i] = xm;
-    x[i] = z ? __fadd_rn(xm, __fmul_rn(c, z[i])) : xm;
+    x[i] = z ? ssde_fadd_rn(xm, ssde_fmul_rn(c, z[i])) : xm;
   }
 }
 
@@ -187,10 +187,10 @@ __global__ __launch_bounds__(256) void sample_update_kernel(const float* __restr
                                                             float* __restrict__ x_mean, float* __restrict__ x_out, int per, size_t numel) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (size_t)gridDim.x * blockDim.x) {
     const size_t n = i / (size_t)per;
-    float xm = a ? __fmul_rn(a[n], x[i]) : x[i];
-    if (y) xm = __fadd_rn(xm, __fmul_rn(b[n], y[i]));
+    float xm = a ? ssde_fmul_rn(a[n], x[i]) : x[i];
+    if (y) xm = ssde_fadd_rn(xm, ssde_fmul_rn(b[n], y[i]));
     x_mean[i] = xm;
-    x_out[i] = z ? __fadd_rn(xm, __fmul_rn(c[n], z[i])) : xm;
+    x_out[i] = z ? ssde_fadd_rn(xm, ssde_fmul_rn(c[n], z[i])) : xm;
   }
 }
 
@@ -203,12 +203,12 @@ __global__ __launch_bounds__(256) void project_kernel(float* __restrict__ x, flo
   const int st = step_ptr ? *step_ptr : 0;
   const float m = coef[2 * st], s = coef[2 * st + 1];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (size_t)gridDim.x * blockDim.x) {
-    const float mk = mask[i], inv = __fsub_rn(1.0f, mk);
-    const float mean = (m == 1.0f) ? data[i] : __fmul_rn(m, data[i]);
-    const float known = __fadd_rn(mean, __fmul_rn(z[i], s));
-    const float xn = __fadd_rn(__fmul_rn(x[i], inv), __fmul_rn(known, mk));
+    const float mk = mask[i], inv = ssde_fsub_rn(1.0f, mk);
+    const float mean = (m == 1.0f) ? data[i] : ssde_fmul_rn(m, data[i]);
+    const float known = ssde_fadd_rn(mean, ssde_fmul_rn(z[i], s));
+    const float xn = ssde_fadd_rn(ssde_fmul_rn(x[i], inv), ssde_fmul_rn(known, mk));
     x[i] = xn;
-    x_mean[i] = __fadd_rn(__fmul_rn(xn, inv), __fmul_rn(mean, mk));
+    x_mean[i] = ssde_fadd_rn(ssde_fmul_rn(xn, inv), ssde_fmul_rn(mean, mk));
   }
 }
 
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void project_kernel(float* __restrict__ x, flo
 struct SsdeMat3 { float m[9]; };
 __device__ __forceinline__ void mat3_apply(const SsdeMat3& a, const float (&v)[3], float (&o)[3]) {
 #pragma unroll
-  for (int j = 0; j < 3; ++j) o[j] = fmaf(v[2], a.m[6 + j], fmaf(v[1], a.m[3 + j], __fmul_rn(v[0], a.m[j])));
+  for (int j = 0; j < 3; ++j) o[j] = fmaf(v[2], a.m[6 + j], fmaf(v[1], a.m[3 + j], ssde_fmul_rn(v[0], a.m[j])));
 }
 __global__ __launch_bounds__(256) void project_color_kernel(float* __restrict__ x, float* __restrict__ x_mean,
                                                             const float* __restrict__ data, const float* __restrict__ mask,
@@ -236,14 +236,14 @@ __global__ __launch_bounds__(256) void project_color_kernel(float* __restrict__ 
     for (int c = 0; c < 3; ++c) {
       const size_t i = base + (size_t)c * hw;
       mk[c] = mask[i];
-      mean[c] = (m == 1.0f) ? data[i] : __fmul_rn(m, data[i]);
-      const float known = __fadd_rn(mean[c], __fmul_rn(z[i], s));
-      yn[c] = __fadd_rn(__fmul_rn(y[c], __fsub_rn(1.0f, mk[c])), __fmul_rn(known, mk[c]));
+      mean[c] = (m == 1.0f) ? data[i] : ssde_fmul_rn(m, data[i]);
+      const float known = ssde_fadd_rn(mean[c], ssde_fmul_rn(z[i], s));
+      yn[c] = ssde_fadd_rn(ssde_fmul_rn(y[c], ssde_fsub_rn(1.0f, mk[c])), ssde_fmul_rn(known, mk[c]));
     }
     mat3_apply(invM, yn, xn);
     mat3_apply(M, xn, y2);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) ym[c] = __fadd_rn(__fmul_rn(y2[c], __fsub_rn(1.0f, mk[c])), __fmul_rn(mean[c], mk[c]));
+    for (int c = 0; c < 3; ++c) ym[c] = ssde_fadd_rn(ssde_fmul_rn(y2[c], ssde_fsub_rn(1.0f, mk[c])), ssde_fmul_rn(mean[c], mk[c]));
     mat3_apply(invM, ym, xm);
 #pragma unroll
     for (int c = 0; c < 3; ++c) { x[base + (size_t)c * hw] = xn[c]; x_mean[base + (size_t)c * hw] = xm[c]; }
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void project_prepare_kernel(const float* data,
     if (data && known) known[i] = kn;
     if (mask_out) mask_out[i] = mk;
     if (prior) {
-      const float xn = __fadd_rn(__fmul_rn(kn, mk), __fmul_rn(prior[i], __fsub_rn(1.0f, mk)));
+      const float xn = ssde_fadd_rn(ssde_fmul_rn(kn, mk), ssde_fmul_rn(prior[i], ssde_fsub_rn(1.0f, mk)));
       x[i] = xn;
       if (x_mean) x_mean[i] = xn;
     }
@@ -295,10 +295,10 @@ __global__ __launch_bounds__(256) void project_prepare_color_kernel(const float*
     if (prior) {
       float pm[3], ap[3], y[3], xn[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) pm[c] = __fmul_rn(prior[base + (size_t)c * hw], __fsub_rn(1.0f, mk[c]));
+      for (int c = 0; c < 3; ++c) pm[c] = ssde_fmul_rn(prior[base + (size_t)c * hw], ssde_fsub_rn(1.0f, mk[c]));
       mat3_apply(M, pm, ap);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) y[c] = __fadd_rn(__fmul_rn(kn[c], mk[c]), ap[c]);
+      for (int c = 0; c < 3; ++c) y[c] = ssde_fadd_rn(ssde_fmul_rn(kn[c], mk[c]), ap[c]);
       mat3_apply(invM, y, xn);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
@@ -457,9 +457,9 @@ __global__ __launch_bounds__(256) void pf_drift_kernel(const float* __restrict__
                                                        size_t numel, float a, float g2, const ssde_ode_dyn* __restrict__ dyn) {
   if (dyn) { a = dyn->a; g2 = dyn->g2; dst = dyn->dst; }
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (size_t)gridDim.x * blockDim.x) {
-    const float f = __fmul_rn(a, x[i]);
-    const float d = __fmul_rn(__fmul_rn(g2, score[i]), 0.5f);
-    dst[i] = (double)__fsub_rn(f, d);
+    const float f = ssde_fmul_rn(a, x[i]);
+    const float d = ssde_fmul_rn(ssde_fmul_rn(g2, score[i]), 0.5f);
+    dst[i] = (double)ssde_fsub_rn(f, d);
   }
 }
 
@@ -476,8 +476,8 @@ __global__ __launch_bounds__(256) void hutch_div_kernel(const float* __restrict_
   double acc = 0.0;
   for (int i = threadIdx.x; i < per; i += 256) {
     const float e = eps[base + i];
-    const float t = __fsub_rn(__fmul_rn(a, e), __fmul_rn(__fmul_rn(g2, gx[base + i]), 0.5f));
-    acc += (double)__fmul_rn(t, e);
+    const float t = ssde_fsub_rn(ssde_fmul_rn(a, e), ssde_fmul_rn(ssde_fmul_rn(g2, gx[base + i]), 0.5f));
+    acc += (double)ssde_fmul_rn(t, e);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
@@ -565,6 +565,7 @@ extern "C" int ssde_hutch_div(const ssde_hutch_div_args* a, void* stream) {
 extern "C" int ssde_randn(const ssde_randn_args* a, void* stream) {
   SSDE_REQUIRE(a && a->dst && a->numel > 0, "randn: bad args");
   SSDE_REQUIRE(a->stream_id >= 0 && a->stream_id < 16, "randn: stream_id must be in 0..15");
+  SSDE_REQUIRE(reinterpret_cast<uintptr_t>(a->dst) % 16 == 0, "randn: dst must be 16-byte aligned (it is written as float4)");
   hipLaunchKernelGGL(randn_kernel, dim3(grid_for((size_t)a->numel / 4, 256, 1024)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a->dst, (size_t)a->numel, (unsigned long long)a->seed, a->step_ptr, a->stream_id,
                      reinterpret_cast<const unsigned long long*>(a->seed_ptr));

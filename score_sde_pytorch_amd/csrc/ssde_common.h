@@ -709,4 +709,26 @@ __device__ __forceinline__ float ssde_wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// One product / sum / difference / quotient, rounded once, that hipcc cannot fuse with a neighbour into an FMA: arithmetic the
+// parity tests compare bit for bit with the reference's torch expression order.  hipcc's own __fmul_rn / __fadd_rn are a plain
+// `*` / `+` (without OCML_BASIC_ROUNDED_OPERATIONS), which -ffp-contract=fast -- the default -- fuses after inlining: a predictor
+// update came out as v_mul + 2 v_fmac, one ulp off torch wherever the product is inexact.  Operations compiled under contract(off)
+// carry no `contract` flag, and a fusion needs the flag on both of its halves.
+__device__ __forceinline__ float ssde_fmul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float ssde_fadd_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float ssde_fsub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ float ssde_fdiv_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a / b;
+}
 #endif
