@@ -152,7 +152,9 @@ enum { SSDE_CONVF_V_GIVEN = 1u,      /* SSDE_TILE_WINOGRAD4R: wino_v already hol
        SSDE_CONVF_X6_WIDE = 512u,    /* bf16x6 GEMM: force the 128 x 256 tile wherever c_out % 256 == 0 (default: where its workgroups fill the device) */
        SSDE_CONVF_X6_NO_WIDE = 1024u,/* bf16x6 GEMM: never take it */
        SSDE_CONVF_KSPLIT2 = 2048u,   /* SSDE_TILE_WINOGRAD4P: two reduction shares where the channel count allows (else one) */
-       SSDE_CONVF_KSPLIT4 = 4096u }; /* SSDE_TILE_WINOGRAD4P: four shares (else two, else one); SSDE_CONVF_NO_KSPLIT: one */
+       SSDE_CONVF_KSPLIT4 = 4096u,   /* SSDE_TILE_WINOGRAD4P: four shares (else two, else one); SSDE_CONVF_NO_KSPLIT: one */
+       SSDE_CONVF_XFORM_PLAIN = 8192u };/* SSDE_TILE_WINOGRAD4R: the transform pass writes V with plain stores everywhere (default:
+                                         non-temporal stores where they were measured to pay, wino4_xform.hip; A/B runs, tests) */
 enum { SSDE_TILE_AUTO = 0, SSDE_TILE_256x64 = 1, SSDE_TILE_128x64 = 2, SSDE_TILE_64x64 = 3, SSDE_TILE_256x32 = 4,
        /* Winograd F(2x2,3x3) kernel (3x3, stride 1, pad 1, even output, no aux): w_main must then be packed as
         * [ceil(Cin/8)][ceil(Cout/64)][16 positions][4 channel pairs][64 couts, bit 4 ^= pair parity][2], G g G^T */
@@ -662,6 +664,10 @@ int ssde_gn_apply_bwd(const ssde_gn_apply_bwd_args* a, void* stream);
 int ssde_conv_gn_slices(const ssde_conv_args* a);
 /* floats of ssde_conv_args.wino_ws this launch needs (plan only, no device access): 0 = its route takes no workspace, < 0 = invalid */
 int64_t ssde_conv_ws_floats(const ssde_conv_args* a);
+/* the input-transform pass of SSDE_TILE_WINOGRAD4R on its own: wino_v = B^T pro(main) B of an h_in x w_in map (multiples of 4,
+ * (c0 + c1) % 4 == 0; tile = SSDE_TILE_WINOGRAD4R), exactly as the two-kernel launch leaves it -- gn_in_part0 (where the pass can
+ * merge the partials itself) and SSDE_CONVF_XFORM_PLAIN included; weights, output and epilogue arguments are not read.  For a caller that fills wino_v itself (SSDE_CONVF_V_GIVEN), A/B runs and tests */
+int ssde_wino4_input_transform(const ssde_conv_args* a, void* stream);
 int ssde_upfirdn2d(const ssde_upfirdn_args* a, void* stream);
 int ssde_attention(const ssde_attn_args* a, void* stream);
 int ssde_attention_route(const ssde_attn_args* a);   /* plan query (added under ABI 13): SSDE_ATTN_ROUTE_* or < 0 with ssde_last_error set; pointers are not read */

@@ -23,7 +23,8 @@ TILE_WINOGRAD4P = 10      # F(4x4,3x3) as position-batched GEMMs (conv_wino4p.hi
 TILES_WINOGRAD4 = (TILE_WINOGRAD4, TILE_WINOGRAD4R, TILE_WINOGRAD4P)
 # routing switches of a launch (include/ssde.h: SSDE_CONVF_*, SSDE_WGRADF_*, SSDE_GNBWDF_*)
 CONVF_V_GIVEN, CONVF_BF16X6, CONVF_NO_KSPLIT, CONVF_BKC8, CONVF_GEMM_PIPE, CONVF_NO_GEMM_PIPE, CONVF_X6_BM64, CONVF_X6_PF2, \
-    CONVF_NO_SMALL_COUT, CONVF_X6_WIDE, CONVF_X6_NO_WIDE, CONVF_KSPLIT2, CONVF_KSPLIT4 = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
+    CONVF_NO_SMALL_COUT, CONVF_X6_WIDE, CONVF_X6_NO_WIDE, CONVF_KSPLIT2, CONVF_KSPLIT4, CONVF_XFORM_PLAIN = \
+    1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
 WGRADF_DIRECT, WGRADF_F2, WGRADF_F4_FORCE, WGRADF_NO_STREAMK, WGRADF_NO_XCD_ORDER, WGRADF_1X1_CHUNKED, WGRADF_XVEC1 = 1, 2, 4, 8, 16, 32, 64
 GNBWDF_THREE_KERNELS, GNBWDF_DEFER_PARAMS = 1, 2
 (OP_CONV, OP_GN_STATS, OP_UPFIRDN, OP_ATTN, OP_EMBED, OP_TO_NHWC, OP_TO_NCHW, OP_BIAS_ACT, OP_SUMSQ,
@@ -323,7 +324,7 @@ EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attent
            "ssde_conv_wgrad", "ssde_colsum", "ssde_gn_bwd_reduce", "ssde_prologue_bwd", "ssde_attention_bwd",
            "ssde_perturb", "ssde_dsm_loss", "ssde_sumsq_flat", "ssde_adam_clip_ema", "ssde_memset", "ssde_axpy",
            "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_conv_ws_floats", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_rk_combine_rows", "ssde_rk_error_norm_rows", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
-           "ssde_gn_apply", "ssde_gn_apply_bwd", "ssde_project_prepare",
+           "ssde_gn_apply", "ssde_gn_apply_bwd", "ssde_project_prepare", "ssde_wino4_input_transform",
            # plan-level entry points (csrc/plan.hip; argument types: plan_export.bind)
            "ssde_plan_load", "ssde_plan_load_file", "ssde_plan_destroy", "ssde_plan_info", "ssde_plan_param",
            "ssde_plan_refresh_weights", "ssde_unet_forward", "ssde_pc_reset", "ssde_pc_run", "ssde_pc_state",
@@ -362,6 +363,8 @@ def conv_route_flags(env=None):
         f |= CONVF_X6_WIDE
     if e.get("SSDE_X6_WIDE", "") == "0":
         f |= CONVF_X6_NO_WIDE
+    if e.get("SSDE_XFORM_NT", "1") == "0":
+        f |= CONVF_XFORM_PLAIN
     return f
 
 
@@ -445,6 +448,7 @@ def bind(lib):
     lib.ssde_conv_gn_slices.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_conv_ws_floats.argtypes = [C.POINTER(ConvArgs)]
     lib.ssde_conv_ws_floats.restype = C.c_int64
+    lib.ssde_wino4_input_transform.argtypes = [C.POINTER(ConvArgs), C.c_void_p]
     lib.ssde_wgrad_scratch_floats.argtypes = [C.POINTER(WgradArgs)]
     lib.ssde_wgrad_scratch_floats.restype = C.c_int64
     lib.ssde_wgrad_wants_winograd4.argtypes = [C.POINTER(WgradArgs)]

@@ -15,7 +15,9 @@ namespace {
 // per element and tile; out-of-image pixels are zeros of the ACTIVATED tensor), both 1-D passes in registers, 36 float4 stores.
 // A wave = 16 consecutive tiles x 4 consecutive quads, lane = quad * 16 + tile: a store instruction writes four 256-byte runs,
 // a load instruction reads 64 contiguous bytes (4 quads) of 16 pixels.  HBM-bound: x read ~2.25x through the tile overlap (L2),
-// V written once.
+// V written once -- with non-temporal stores where ssde_wino4_xform_streams_v (below) says so (kNt): the next reader of V is
+// another kernel, and streamed out it does not push x out of the caches.  Workgroups run in launch order: walking the tile
+// blocks of an image on one XCD was measured and left out (tools/experiments/wino4_xform_xcd_order.patch).
 // GroupNorm statistics merged by the pass itself (ssde_conv_args.gn_in_part0, ABI 10): a workgroup covers 16 tiles -- part of
 // one image, or up to four whole ones on the 8x8 maps -- and 16 channel quads, i.e. at most 4 x 16 (image, group) pairs.  A
 // merging workgroup does it FIRST: its sixteen teams of 16 lanes merge the producers' partials of those pairs (ssde_gn_merge16,
@@ -37,13 +39,18 @@ struct XformVqParams {
 };
 constexpr int kXfPairs = 64;                   // (image, group) pairs of a workgroup, at most
 
+// The fused multiply-adds are written out and the compiler adds none (as ssde_stat_merge, ssde_common.h): left to -ffp-contract,
+// two instantiations of the kernel that differ in their stores alone were contracted differently (1 ulp in 4 % of V on the
+// device), and V must be the same bits whichever instantiation a launch takes.
 __device__ __forceinline__ void bt6q(const float4 (&d)[6], float4 (&o)[6]) {
+#pragma clang fp contract(off)
 #define SSDE_BT6_LANE(c)                                                                                             \
   {                                                                                                                  \
-    const float t1 = d[4].c - 4.f * d[2].c, t2 = d[3].c - 4.f * d[1].c, t3 = d[4].c - d[2].c, t4 = d[3].c - d[1].c;   \
-    o[0].c = 4.f * d[0].c - 5.f * d[2].c + d[4].c;                                                                    \
-    o[1].c = t1 + t2; o[2].c = t1 - t2; o[3].c = t3 + 2.f * t4; o[4].c = t3 - 2.f * t4;                               \
-    o[5].c = 4.f * d[1].c - 5.f * d[3].c + d[5].c;                                                                    \
+    const float t1 = __builtin_fmaf(-4.f, d[2].c, d[4].c), t2 = __builtin_fmaf(-4.f, d[1].c, d[3].c);                 \
+    const float t3 = d[4].c - d[2].c, t4 = d[3].c - d[1].c;                                                           \
+    o[0].c = __builtin_fmaf(4.f, d[0].c, __builtin_fmaf(-5.f, d[2].c, d[4].c));                                       \
+    o[1].c = t1 + t2; o[2].c = t1 - t2; o[3].c = __builtin_fmaf(2.f, t4, t3); o[4].c = __builtin_fmaf(-2.f, t4, t3);  \
+    o[5].c = __builtin_fmaf(4.f, d[1].c, __builtin_fmaf(-5.f, d[3].c, d[5].c));                                       \
   }
   SSDE_BT6_LANE(x) SSDE_BT6_LANE(y) SSDE_BT6_LANE(z) SSDE_BT6_LANE(w)
 #undef SSDE_BT6_LANE
@@ -51,7 +58,9 @@ __device__ __forceinline__ void bt6q(const float4 (&d)[6], float4 (&o)[6]) {
 
 constexpr int kXfThreads = 256;
 
-template <bool kGn, bool kMerge>
+typedef float xf_v4f __attribute__((ext_vector_type(4)));
+
+template <bool kGn, bool kMerge, bool kNt>
 __global__ __launch_bounds__(kXfThreads, 2) void wino4_xform_vq_kernel(const XformVqParams p) {
   static_assert(kGn || !kMerge, "only a GroupNorm prologue has statistics to merge");
   const ssde_src& s = p.src;
@@ -152,7 +161,11 @@ __global__ __launch_bounds__(kXfThreads, 2) void wino4_xform_vq_kernel(const Xfo
     float4 o[6];
     bt6q(v[a], o);
 #pragma unroll
-    for (int b = 0; b < 6; ++b) *reinterpret_cast<float4*>(dst + (size_t)(a * 6 + b) * plane) = o[b];
+    for (int b = 0; b < 6; ++b) {
+      float* at = dst + (size_t)(a * 6 + b) * plane;
+      if constexpr (kNt) __builtin_nontemporal_store(xf_v4f{o[b].x, o[b].y, o[b].z, o[b].w}, reinterpret_cast<xf_v4f*>(at));
+      else *reinterpret_cast<float4*>(at) = o[b];
+    }
   }
 }
 
@@ -170,6 +183,16 @@ bool ssde_wino4_xform_merges_gn(const ssde_conv_args* a) {
   return per_img >= 4 && s.gn_groups > 0 && s.gn_mean && s.gn_rstd;
 }
 
+// does the pass of this launch write V with non-temporal stores?  V is written once and next read by another kernel; streamed
+// past the caches it leaves them to x -- the rows the neighbouring tile blocks re-read, and what the launches around the pass
+// still want of it.  Measured per launch inside the CIFAR-10 program at batch 256 (profiles/xform_nt_xcd_op_times.txt, two rounds
+// A-B-A-B, pass + matrix kernel): 128 ch @32x32 -3 %, 256 ch @16x16 -2.5 %, 384 ch @32x32 -2 %, 256 ch @8x8 -1.5 %, 256 ch @32x32
+// level, 512 ch @16x16 +1 % and @8x8 level: the launches of 512 channels and more keep plain stores, and so does the
+// position-batched route (conv_wino4p.hip), which was not measured.  SSDE_CONVF_XFORM_PLAIN: plain stores everywhere.
+static bool ssde_wino4_xform_streams_v(const ssde_conv_args* a) {
+  return a->tile == SSDE_TILE_WINOGRAD4R && !(a->flags & SSDE_CONVF_XFORM_PLAIN) && a->main.c0 + a->main.c1 < 512;
+}
+
 int ssde_wino4_xform_vq_launch(const ssde_conv_args* a, void* stream) {
   SSDE_REQUIRE(a && a->main.p0 && a->wino_v, "conv(winograd 4x4, two kernels): the transformed-input buffer (ssde_conv_args.wino_v) is missing");
   const ssde_src& s = a->main;
@@ -185,9 +208,26 @@ int ssde_wino4_xform_vq_launch(const ssde_conv_args* a, void* stream) {
   }
   const dim3 grid(ssde_cdiv(p.T, 16), ssde_cdiv(p.Ctot >> 2, 16));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (gn && p.part0) hipLaunchKernelGGL((wino4_xform_vq_kernel<true, true>), grid, dim3(kXfThreads), kXfPairs * 2 * sizeof(float), st, p);
-  else if (gn) hipLaunchKernelGGL((wino4_xform_vq_kernel<true, false>), grid, dim3(kXfThreads), 0, st, p);
-  else hipLaunchKernelGGL((wino4_xform_vq_kernel<false, false>), grid, dim3(kXfThreads), 0, st, p);
+  const bool nt = ssde_wino4_xform_streams_v(a);
+  const size_t lds = kXfPairs * 2 * sizeof(float);
+#define SSDE_XF_LAUNCH(GN, MERGE, LDS)                                                                                \
+  do {                                                                                                                \
+    if (nt) hipLaunchKernelGGL((wino4_xform_vq_kernel<GN, MERGE, true>), grid, dim3(kXfThreads), LDS, st, p);          \
+    else hipLaunchKernelGGL((wino4_xform_vq_kernel<GN, MERGE, false>), grid, dim3(kXfThreads), LDS, st, p);            \
+  } while (0)
+  if (gn && p.part0) SSDE_XF_LAUNCH(true, true, lds);
+  else if (gn) SSDE_XF_LAUNCH(true, false, 0);
+  else SSDE_XF_LAUNCH(false, false, 0);
+#undef SSDE_XF_LAUNCH
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
+}
+
+// The pass on its own (include/ssde.h): what ssde_conv2d does in front of the matrix kernel of SSDE_TILE_WINOGRAD4R, and nothing else.
+extern "C" int ssde_wino4_input_transform(const ssde_conv_args* a, void* stream) {
+  SSDE_REQUIRE(a && a->tile == SSDE_TILE_WINOGRAD4R && !(a->flags & SSDE_CONVF_V_GIVEN),
+               "wino4 input transform: needs the arguments of an SSDE_TILE_WINOGRAD4R launch without SSDE_CONVF_V_GIVEN");
+  SSDE_REQUIRE(!a->gn_in_part0 || ssde_wino4_xform_merges_gn(a),
+               "wino4 input transform: the pass cannot merge these GroupNorm partials itself (ssde_gn_finalize first)");
+  return ssde_wino4_xform_vq_launch(a, stream);
 }
