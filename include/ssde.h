@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSDE_ABI_VERSION 13  /* (13, no layout change and no new version: ssde_src.act -- the spare word at the end of ssde_src, the former _pad, names the activation that SSDE_PRO_GN_SILU / SSDE_PRO_SILU apply: SSDE_ACT_SILU = 0, SSDE_ACT_ELU, SSDE_ACT_RELU, SSDE_ACT_LRELU (get_act, models/layers.py:29-41); only ssde_gn_apply / ssde_gn_apply_bwd (and SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD) evaluate a non-zero value, and they now also take SSDE_PRO_SILU (activation only); every other entry point that reads an ssde_src refuses act != 0 in its argument check; a caller of version 13 zero-fills its records, so it sends SiLU, every launch it could make keeps its kernel and its bits, no structure changes size, no field moves and plan blobs of version 13 stay byte-identical, so the number stays -- an older library ignores the word, so a binding that needs it checks for the refusal) (13, no layout change and no new version: controllable generation from sampler plans -- new exports ssde_project_prepare (one launch, no program op: the op union keeps its 34 kinds and its size) and ssde_pc_projection / ssde_pc_set_known / ssde_pc_reset_known / ssde_pc_set_noise, which find their buffers in the SSDE_OP_PROJECT / SSDE_OP_LANGEVIN / SSDE_OP_PREDICTOR ops of a loaded SSDE_PLAN_PC plan; ssde_pc_run now refuses a projection plan whose known data was never set; no structure, header field or I/O slot changes and every blob of version 13 stays byte-identical, so the number stays -- a binding that needs the new exports finds out by name when it binds) (13, no new version: ssde_upfirdn2d takes kernels of 1..SSDE_FIR_MAX_TAPS taps per axis and negative pads, which crop -- ssde_upfirdn_args.taps is appended behind dst2 (a device array for kernels past 4x4; the structure grows inside the op union, so every op record keeps its size and every earlier field its offset) and ssde_upfirdn_args.flags takes the former pad word (SSDE_FIRF_GENERAL, SSDE_FIRF_TILED); a caller of version 13 zero-fills its records, so it sends flags = 0 and taps = NULL, every launch it could make keeps its kernel and its bits, and plan blobs of version 13 load unchanged, so the number stays -- an older library refuses a kernel past 4x4 by message) (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
+#define SSDE_ABI_VERSION 13  /* (13, no layout change and no new version: ssde_concat / SSDE_OP_CONCAT = 35, a materialised channel concatenation for progressive_combine = 'cat' -- a new export and a new op kind at the end of the enum; its record is smaller than the op union, so sizeof(ssde_op) and every existing blob stay as they are; an older library answers the new kind with "unknown op kind") (13, no layout change and no new version: ssde_src.act -- the spare word at the end of ssde_src, the former _pad, names the activation that SSDE_PRO_GN_SILU / SSDE_PRO_SILU apply: SSDE_ACT_SILU = 0, SSDE_ACT_ELU, SSDE_ACT_RELU, SSDE_ACT_LRELU (get_act, models/layers.py:29-41); only ssde_gn_apply / ssde_gn_apply_bwd (and SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD) evaluate a non-zero value, and they now also take SSDE_PRO_SILU (activation only); every other entry point that reads an ssde_src refuses act != 0 in its argument check; a caller of version 13 zero-fills its records, so it sends SiLU, every launch it could make keeps its kernel and its bits, no structure changes size, no field moves and plan blobs of version 13 stay byte-identical, so the number stays -- an older library ignores the word, so a binding that needs it checks for the refusal) (13, no layout change and no new version: controllable generation from sampler plans -- new exports ssde_project_prepare (one launch, no program op: the op union keeps its 34 kinds and its size) and ssde_pc_projection / ssde_pc_set_known / ssde_pc_reset_known / ssde_pc_set_noise, which find their buffers in the SSDE_OP_PROJECT / SSDE_OP_LANGEVIN / SSDE_OP_PREDICTOR ops of a loaded SSDE_PLAN_PC plan; ssde_pc_run now refuses a projection plan whose known data was never set; no structure, header field or I/O slot changes and every blob of version 13 stays byte-identical, so the number stays -- a binding that needs the new exports finds out by name when it binds) (13, no new version: ssde_upfirdn2d takes kernels of 1..SSDE_FIR_MAX_TAPS taps per axis and negative pads, which crop -- ssde_upfirdn_args.taps is appended behind dst2 (a device array for kernels past 4x4; the structure grows inside the op union, so every op record keeps its size and every earlier field its offset) and ssde_upfirdn_args.flags takes the former pad word (SSDE_FIRF_GENERAL, SSDE_FIRF_TILED); a caller of version 13 zero-fills its records, so it sends flags = 0 and taps = NULL, every launch it could make keeps its kernel and its bits, and plan blobs of version 13 load unchanged, so the number stays -- an older library refuses a kernel past 4x4 by message) (13, no layout change and no new version: attention over more than 256 tokens -- ssde_attention / ssde_attention_bwd take 256 < l <= SSDE_ATTN_L_MAX on streaming kernels (attention.hip), SSDE_ATTNF_STREAM forces the streaming forward at any l, new export ssde_attention_route (plan query, no device access); no structure changes layout, every launch with l <= 256 keeps its kernel and its bits and plan blobs of version 13 load unchanged, so the number stays -- a binding that needs the new export finds out by name when it binds) 13: ssde_gn_apply / ssde_gn_apply_bwd + SSDE_OP_GN_APPLY / SSDE_OP_GN_APPLY_BWD (a GroupNorm whose channels-per-group is no multiple of 4 runs as launches of its own and hands its consumers a plain tensor), ssde_gn_stats_args.flags (in the former pad slot) and ssde_groupnorm_stats accepts any group width >= 4; no existing structure changes size, no existing launch changes; 12: ssde_conv_args.pad_end (in the spare slot behind gn_in_eps: no field moves) / ssde_wgrad_args.pad_end (appended): zero rows and columns after the last input row / column on top of pad -- DDPM's Downsample, F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 (models/layers.py:608-611), as one launch of the direct kernels; 0 keeps every launch of ABI 11 bit for bit; 11: SSDE_TILE_WINOGRAD4P + SSDE_PACK_WINO4P (F(4x4,3x3) as a transform pass, 36 position-batched GEMMs and an output pass: conv_wino4p.hip), ssde_conv_args.wino_ws / wino_ws_floats (that route's workspace, ssde_conv_ws_floats), SSDE_CONVF_KSPLIT2 / SSDE_CONVF_KSPLIT4; (10, no layout change: SSDE_CONVF_X6_WIDE / SSDE_CONVF_X6_NO_WIDE -- the 128 x 256 tile of the bf16x6 GEMM -- are new routing flags old callers never set) 10: ssde_conv_args.gn_in_part0 / gn_in_part1 / gn_in_slices0 / gn_in_slices1 / gn_in_eps (the consuming launch merges the GroupNorm partials of its main source itself: no ssde_gn_finalize launch in front of it), ssde_gn_finalize merges with teams of 16 lanes, ssde_attn_args.flags (SSDE_ATTNF_BF16X6); 9: SSDE_CONVF_NO_SMALL_COUT (3x3 convolutions onto at most four channels have their own kernel, conv_small.hip), the register-fed F(4x4,3x3) matrix kernel splits its reduction (no interface change); 8: routing switches moved from environment variables into ssde_conv_args.flags / ssde_wgrad_args.flags / ssde_gn_bwd_reduce_args.flags, SSDE_TILE_WINOGRAD4R + SSDE_PACK_WINO4R (register-fed F(4x4,3x3) matrix kernel), SSDE_TILE_WINOGRAD4X removed; 7: ssde_gn_bwd_reduce_args.g0 / g1 (GroupNorm backward in one pass over dp and x); 6: ssde_conv_args.wino_v / ssde_wgrad_args.v_pre (forward by-product feeds the weight gradient); 5: SSDE_PACK_WINO4 image re-ordered per wave (plan blobs of version 4 carry the old image), ODE ops in programs */
 
 /* ---- prologue applied to a source tensor while it is staged into LDS ---- */
 enum {
@@ -237,6 +237,17 @@ typedef struct ssde_gn_apply_bwd_args {
   float* g0; float* g1;          /* gradients of p0 [N * hw, c0] and p1 [N * hw, c1] (NULL: that source needs no gradient) */
   int32_t acc0, acc1;            /* 1: g += ..., 0: g = ... */
 } ssde_gn_apply_bwd_args;
+
+/* Channel concatenation as a tensor (added under ABI 13): dst[N, hw, c0 + c1] = cat(p0[N, hw, c0], p1[N, hw, c1]), NHWC -- a copy,
+ * bit for bit.  ssde_src joins two tensors for its consumer; progressive_combine = 'cat' (layerspp.Combine, models/layerspp.py:44-59)
+ * makes a feature map that is itself a pair and is read together with a third tensor, so the pair is written out once.  c0 and c1
+ * are positive multiples of 4, n and hw positive, the three pointers 16-byte aligned: anything else is SSDE_EINVAL, decided on the
+ * host before any launch. */
+typedef struct ssde_concat_args {
+  const float* p0; const float* p1;   /* [N * hw, c0], [N * hw, c1] */
+  float* dst;                         /* [N * hw, c0 + c1] */
+  int32_t n, hw, c0, c1;
+} ssde_concat_args;
 
 /* GroupNorm statistics from the PRODUCERS' partials instead of a pass over the tensor: merges, in a fixed order,
  * the (mean, M2, count) triples the convolution epilogues wrote (ssde_conv_args.gn_part) over the slices and the
@@ -658,6 +669,7 @@ int ssde_groupnorm_stats(const ssde_gn_stats_args* a, void* stream);
 int ssde_gn_finalize(const ssde_gn_finalize_args* a, void* stream);
 int ssde_gn_apply(const ssde_gn_apply_args* a, void* stream);
 int ssde_gn_apply_bwd(const ssde_gn_apply_bwd_args* a, void* stream);
+int ssde_concat(const ssde_concat_args* a, void* stream);   /* (added under ABI 13) program op SSDE_OP_CONCAT */
 /* slices per image of the GroupNorm partials this launch would write (plan only, no device access); 0 = this
  * launch cannot produce them (a workgroup tile would span several images, or c_out % 4 != 0), or cannot run at all
  * (ssde_conv_lds_bytes says why) */
@@ -723,7 +735,8 @@ enum {
   SSDE_OP_ATTN_BWD = 19, SSDE_OP_PERTURB = 20, SSDE_OP_DSM_LOSS = 21, SSDE_OP_SUMSQ_FLAT = 22,
   SSDE_OP_ADAM = 23, SSDE_OP_MEMSET = 24, SSDE_OP_AXPY = 25, SSDE_OP_PACK = 26, SSDE_OP_PROJECT = 27,
   SSDE_OP_GN_FINALIZE = 28, SSDE_OP_PF_DRIFT = 29, SSDE_OP_HUTCH_DIV = 30, SSDE_OP_COLSUM_FINISH = 31, SSDE_OP_GN_BWD_FINISH = 32,
-  SSDE_OP_GN_APPLY = 33, SSDE_OP_GN_APPLY_BWD = 34
+  SSDE_OP_GN_APPLY = 33, SSDE_OP_GN_APPLY_BWD = 34,
+  SSDE_OP_CONCAT = 35   /* (added under ABI 13) */
 };
 typedef struct ssde_op {
   int32_t kind; int32_t flops_class;   /* flops_class: free tag echoed by timing */
@@ -740,6 +753,7 @@ typedef struct ssde_op {
     ssde_pf_drift_args pf_drift; ssde_hutch_div_args hutch_div;
     ssde_colsum_finish_args colsum_fin; ssde_gn_bwd_finish_args gn_bwd_fin;
     ssde_gn_apply_args gn_apply; ssde_gn_apply_bwd_args gn_apply_bwd;
+    ssde_concat_args concat;   /* (added under ABI 13) smaller than the union: sizeof(ssde_op) is unchanged */
   } u;
 } ssde_op;
 

@@ -30,7 +30,8 @@ GNBWDF_THREE_KERNELS, GNBWDF_DEFER_PARAMS = 1, 2
 (OP_CONV, OP_GN_STATS, OP_UPFIRDN, OP_ATTN, OP_EMBED, OP_TO_NHWC, OP_TO_NCHW, OP_BIAS_ACT, OP_SUMSQ,
  OP_RANDN, OP_LANGEVIN, OP_PREDICTOR, OP_FILL, OP_STEP_INC, OP_WGRAD, OP_COLSUM, OP_GN_BWD_REDUCE, OP_PROLOGUE_BWD,
  OP_ATTN_BWD, OP_PERTURB, OP_DSM_LOSS, OP_SUMSQ_FLAT, OP_ADAM, OP_MEMSET, OP_AXPY, OP_PACK, OP_PROJECT,
- OP_GN_FINALIZE, OP_PF_DRIFT, OP_HUTCH_DIV, OP_COLSUM_FINISH, OP_GN_BWD_FINISH, OP_GN_APPLY, OP_GN_APPLY_BWD) = range(1, 35)
+ OP_GN_FINALIZE, OP_PF_DRIFT, OP_HUTCH_DIV, OP_COLSUM_FINISH, OP_GN_BWD_FINISH, OP_GN_APPLY, OP_GN_APPLY_BWD,
+ OP_CONCAT) = range(1, 36)
 GNSTATF_ANY_WIDTH = 1
 FIRF_GENERAL, FIRF_TILED = 1, 2      # include/ssde.h: SSDE_FIRF_*
 FIR_MAX_TAPS = 16
@@ -74,6 +75,11 @@ class GnApplyBwdArgs(C.Structure):
     _fields_ = [("src", Src), ("dy", _fp), ("n", C.c_int32), ("hw", C.c_int32), ("sums", _fp), ("dgamma", _fp), ("dbeta", _fp),
                 ("scratch", _fp), ("slices", C.c_int32), ("_pad0", C.c_int32), ("g0", _fp), ("g1", _fp),
                 ("acc0", C.c_int32), ("acc1", C.c_int32)]
+
+
+class ConcatArgs(C.Structure):
+    """include/ssde.h: ssde_concat_args, dst[N, hw, c0 + c1] = cat(p0, p1)"""
+    _fields_ = [("p0", _fp), ("p1", _fp), ("dst", _fp), ("n", C.c_int32), ("hw", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32)]
 
 
 class RkCombineArgs(C.Structure):
@@ -303,6 +309,10 @@ OPS = [(OP_CONV, "conv", ConvArgs, "ssde_conv2d"), (OP_GN_STATS, "gn", GnStatsAr
        (OP_HUTCH_DIV, "hutch_div", HutchDivArgs, "ssde_hutch_div"), (OP_COLSUM_FINISH, "colsum_fin", ColsumFinishArgs, "ssde_colsum_finish"),
        (OP_GN_BWD_FINISH, "gn_bwd_fin", GnBwdFinishArgs, "ssde_gn_bwd_finish"), (OP_GN_APPLY, "gn_apply", GnApplyArgs, "ssde_gn_apply"),
        (OP_GN_APPLY_BWD, "gn_apply_bwd", GnApplyBwdArgs, "ssde_gn_apply_bwd")]
+# Kinds appended to the enum without a member of their own in this mirror: (op kind, argument structure, C entry point).  Every
+# member of a C union starts at its first byte, so such a record is written to and read from the head of `u` (make_op, args_of);
+# it has to fit the members above (checked below), which is also what keeps sizeof(ssde_op) where it was.
+TAIL_OPS = [(OP_CONCAT, ConcatArgs, "ssde_concat")]
 
 
 class _OpUnion(C.Union):
@@ -315,6 +325,8 @@ class Op(C.Structure):
 
 _UNION_FIELD = {kind: member for kind, member, _, _ in OPS}
 ARGS = {kind: args for kind, _, args, _ in OPS}
+ARGS.update({kind: args for kind, args, _ in TAIL_OPS})
+assert all(C.sizeof(args) <= C.sizeof(_OpUnion) and C.alignment(args) <= C.alignment(_OpUnion) for _, args, _ in TAIL_OPS)
 
 EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attention", "ssde_attention_route", "ssde_embed", "ssde_to_nhwc",
            "ssde_to_nchw", "ssde_fused_bias_act", "ssde_sumsq", "ssde_randn", "ssde_langevin_update",
@@ -324,7 +336,7 @@ EXPORTS = ["ssde_conv2d", "ssde_groupnorm_stats", "ssde_upfirdn2d", "ssde_attent
            "ssde_conv_wgrad", "ssde_colsum", "ssde_gn_bwd_reduce", "ssde_prologue_bwd", "ssde_attention_bwd",
            "ssde_perturb", "ssde_dsm_loss", "ssde_sumsq_flat", "ssde_adam_clip_ema", "ssde_memset", "ssde_axpy",
            "ssde_wgrad_scratch_floats", "ssde_wgrad_wants_winograd4", "ssde_pack_weights", "ssde_project_update", "ssde_gn_finalize", "ssde_conv_gn_slices", "ssde_conv_ws_floats", "ssde_rk_combine", "ssde_rk_error_norm", "ssde_rk_combine_rows", "ssde_rk_error_norm_rows", "ssde_pf_drift", "ssde_hutch_div", "ssde_sample_update", "ssde_mfma_probe", "ssde_colsum_finish", "ssde_gn_bwd_finish", "ssde_gn_bwd_scratch_rows",
-           "ssde_gn_apply", "ssde_gn_apply_bwd", "ssde_project_prepare", "ssde_wino4_input_transform",
+           "ssde_gn_apply", "ssde_gn_apply_bwd", "ssde_project_prepare", "ssde_wino4_input_transform", "ssde_concat",
            # plan-level entry points (csrc/plan.hip; argument types: plan_export.bind)
            "ssde_plan_load", "ssde_plan_load_file", "ssde_plan_destroy", "ssde_plan_info", "ssde_plan_param",
            "ssde_plan_refresh_weights", "ssde_unet_forward", "ssde_pc_reset", "ssde_pc_run", "ssde_pc_state",
@@ -434,7 +446,7 @@ def bind(lib):
     lib.ssde_graph_capture.argtypes = [C.POINTER(Op), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.ssde_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
     lib.ssde_graph_destroy.argtypes = [C.c_void_p]
-    for _, _, typ, name in OPS:
+    for typ, name in [(typ, name) for _, _, typ, name in OPS] + [(typ, name) for _, typ, name in TAIL_OPS]:
         if name is not None:
             getattr(lib, name).argtypes = [C.POINTER(typ), C.c_void_p]
     lib.ssde_rk_combine.argtypes = [C.POINTER(RkCombineArgs), C.c_void_p]
@@ -522,8 +534,20 @@ def make_op(kind, args, flops_class=0):
     op = Op()
     op.kind = kind
     op.flops_class = flops_class
-    setattr(op.u, _UNION_FIELD[kind], args)
+    if kind in _UNION_FIELD:
+        setattr(op.u, _UNION_FIELD[kind], args)
+    else:                                              # a kind of TAIL_OPS: its record is the head of the union
+        C.memmove(C.byref(op, Op.u.offset), C.byref(args), C.sizeof(args))
     return op
+
+
+def args_of(op):
+    """The argument record of an op as its kind's structure (a view of the op's own bytes): the named member of the union, or
+    for a kind of TAIL_OPS the head of the union."""
+    kind = int(op.kind)
+    if kind in _UNION_FIELD:
+        return getattr(op.u, _UNION_FIELD[kind])
+    return ARGS[kind].from_buffer(op, Op.u.offset)
 
 
 def make(kind, **fields):

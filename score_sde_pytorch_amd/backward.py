@@ -204,7 +204,8 @@ class TrainEngine(E.UNetEngine):
         if self.param_grads:
             b.add(L.OP_MEMSET, dict(dst=self.flat.grad, bytes=self.flat.numel * 4, value=0), FC_BWD)
         handlers = {L.OP_CONV: self._bwd_conv, L.OP_UPFIRDN: self._bwd_fir, L.OP_ATTN: self._bwd_attn,
-                    L.OP_TO_NCHW: self._bwd_to_nchw, L.OP_TO_NHWC: self._bwd_to_nhwc, L.OP_GN_APPLY: self._bwd_gn_apply}
+                    L.OP_TO_NCHW: self._bwd_to_nchw, L.OP_TO_NHWC: self._bwd_to_nhwc, L.OP_GN_APPLY: self._bwd_gn_apply,
+                    L.OP_CONCAT: self._bwd_concat}
         for kind, f, _, _ in reversed(fwd):
             h = handlers.get(kind)
             if h is not None:
@@ -334,6 +335,15 @@ class TrainEngine(E.UNetEngine):
             e0[1] = True
         if e1:
             e1[1] = True
+
+    def _bwd_concat(self, f):
+        """The adjoint of OP_CONCAT: the gradient of dst, sliced into the gradients of its two sources."""
+        e = self._G.get(id(f["dst"]))
+        if e is None:
+            return
+        ctot = f["c0"] + f["c1"]
+        self._accum(f["p0"], e[0], ctot, 0, f["c0"], f["n"], f["hw"], 1.0)
+        self._accum(f["p1"], e[0], ctot, f["c0"], f["c1"], f["n"], f["hw"], 1.0)
 
     def _bwd_gn_apply_norm(self, f, e, e0, e1):
         """OP_GN_APPLY_BWD of a source with a GroupNorm: dgamma, dbeta and the gradients of the sources that need one"""

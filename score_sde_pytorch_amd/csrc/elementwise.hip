@@ -316,6 +316,19 @@ __global__ void fill_kernel(float* __restrict__ dst, const float* __restrict__ t
 
 __global__ void step_inc_kernel(int* step_ptr, int delta) { *step_ptr += delta; }
 
+// ---- channel concatenation as a tensor (layerspp.Combine with method 'cat', layerspp.py:52-55) -----------------------
+// dst[r, :] = [p0[r, :], p1[r, :]] over rows r = (image, pixel); q0 / q1: channel quads per row of p0 / p1.  One 16-byte load
+// and one 16-byte store per quad, grid-stride; a copy, so the bits are the sources'.
+__global__ __launch_bounds__(256) void concat_kernel(const float4* __restrict__ p0, const float4* __restrict__ p1,
+                                                     float4* __restrict__ dst, size_t rows, int q0, int q1) {
+  const size_t qt = (size_t)(q0 + q1), total = rows * qt;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / qt;
+    const int q = (int)(i - r * qt);
+    dst[i] = q < q0 ? p0[r * q0 + q] : p1[r * q1 + (q - q0)];
+  }
+}
+
 inline unsigned grid_for(size_t total, int block = 256, unsigned cap = 256 * 16) {
   size_t b = (total + block - 1) / block;
   if (b < 1) b = 1;
@@ -645,6 +658,23 @@ extern "C" int ssde_project_prepare(const ssde_project_prepare_args* a, void* st
     hipLaunchKernelGGL(project_prepare_kernel, dim3(grid_for((size_t)a->n * a->c * a->hw)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        a->data, a->mask, a->prior, a->known, a->mask_out, a->x, a->x_mean, (size_t)a->n * a->c * a->hw);
   }
+  SSDE_LAUNCH_CHECK();
+  return SSDE_OK;
+}
+
+extern "C" int ssde_concat(const ssde_concat_args* a, void* stream) {
+  SSDE_REQUIRE(a && a->p0 && a->p1 && a->dst, "concat: null args");
+  SSDE_REQUIRE(a->n > 0 && a->hw > 0, "concat: bad shape (n %d, hw %d)", a->n, a->hw);
+  SSDE_REQUIRE(a->c0 > 0 && a->c1 > 0 && a->c0 % 4 == 0 && a->c1 % 4 == 0,
+               "concat: channel counts must be positive multiples of 4 (got %d and %d)", a->c0, a->c1);
+  SSDE_REQUIRE((reinterpret_cast<uintptr_t>(a->p0) | reinterpret_cast<uintptr_t>(a->p1) | reinterpret_cast<uintptr_t>(a->dst)) % 16 == 0,
+               "concat: p0, p1 and dst must be 16-byte aligned (they are read and written as float4)");
+  const size_t rows = (size_t)a->n * a->hw;
+  const int q0 = a->c0 / 4, q1 = a->c1 / 4;
+  // (workgroups: 16 per compute unit at the most, the grid-stride loop takes the rest)
+  hipLaunchKernelGGL(concat_kernel, dim3(grid_for(rows * (size_t)(q0 + q1), 256, (unsigned)ssde_num_cus() * 16)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), reinterpret_cast<const float4*>(a->p0), reinterpret_cast<const float4*>(a->p1),
+                     reinterpret_cast<float4*>(a->dst), rows, q0, q1);
   SSDE_LAUNCH_CHECK();
   return SSDE_OK;
 }

@@ -98,6 +98,7 @@ static int run_one(const ssde_op& op, void* stream) {
     case SSDE_OP_GN_BWD_FINISH: return ssde_gn_bwd_finish(&op.u.gn_bwd_fin, stream);
     case SSDE_OP_GN_APPLY: return ssde_gn_apply(&op.u.gn_apply, stream);
     case SSDE_OP_GN_APPLY_BWD: return ssde_gn_apply_bwd(&op.u.gn_apply_bwd, stream);
+    case SSDE_OP_CONCAT: return ssde_concat(&op.u.concat, stream);
   }
   ssde_set_error("program: unknown op kind %d", op.kind);
   return SSDE_EINVAL;

@@ -14,7 +14,8 @@ Fusions encoded in the program (per ResnetBlockBigGANpp, models/layerspp.py:242-
                       Dense_0 projections are ONE batched GEMM at the start)
   Conv_1 (+Conv_2) -> conv kernel; the 1x1 skip conv is an extra K-range of the same
                       GEMM; epilogue adds the identity skip and scales by 1/sqrt(2)
-  torch.cat        -> never materialised: a source is a pair of tensors
+  torch.cat        -> never materialised: a source is a pair of tensors (but layerspp.Combine's 'cat' feature map, which is
+                      read next to a third tensor: one OP_CONCAT writes it out)
 
 A GroupNorm whose channels-per-group is no multiple of 4 (nn.GroupNorm(min(C // 4, 32), C) on 192 = 128 + 64 channels: 32 groups
 of 6 -- the 1024-px configs, layerspp.py:219,231) is NOT fused: no consumer's prologue accepts a channel quad that spans two
@@ -1146,6 +1147,9 @@ class UNetEngine:
         pyr, pyr_c = (x0, cpad) if model.progressive_input != "none" else (None, 0)
         hs = [(h, nf, H, W)]
         cur_c = nf
+        # resblock_type = 'ddpm' (ncsnpp.py:158-161, 217-221): the blocks do not resample, layerspp.Downsample / Upsample stand
+        # where the BigGAN network has a resampling block
+        ddpm_blocks = getattr(model, "resblock_type", "biggan") == "ddpm"
 
         def is_attn(res):
             return res in model.attn_resolutions
@@ -1160,31 +1164,37 @@ class UNetEngine:
                 hs.append((h, cur_c, hh, ww))
             if lvl != model.num_resolutions - 1:
                 t, c, hh, ww = hs[-1]
-                h, cur_c = self._res(mods[idx], t, c, hh, ww); idx += 1
+                if ddpm_blocks:
+                    h, cur_c, _, _ = self._downsample(mods[idx], t, c, hh, ww); idx += 1
+                else:
+                    h, cur_c = self._res(mods[idx], t, c, hh, ww); idx += 1
                 hh, ww = hh // 2, ww // 2
                 if model.progressive_input == "input_skip":
                     taps = fir_taps(fk) if fir else fir_taps([1, 1])
                     pd = fir_pads(taps.shape[0])
                     pyr, _, _ = low.upfirdn(_src(pyr, pyr_c), pyr_c, hh * 2, ww * 2, taps, down=2, pad=pd, name="pyr_down")
                     comb = mods[idx]; idx += 1
-                    if comb.method != "sum":
-                        raise NotImplementedError("progressive_combine='cat' is not lowered (no shipped config uses it)")
-                    hn = b.buf(n, hh, ww, cur_c, name="combine")
-                    low.conv(hn, hh, ww, cur_c, aux=_src(pyr, pyr_c), w_aux=self._w1(comb.Conv_0, cin_pad=pyr_c),
-                             bias=self._bias(comb.Conv_0), resid=h, scale=1.0, stats=True)
-                    h = hn
+                    if comb.method == "sum":
+                        hn = b.buf(n, hh, ww, cur_c, name="combine")
+                        low.conv(hn, hh, ww, cur_c, aux=_src(pyr, pyr_c), w_aux=self._w1(comb.Conv_0, cin_pad=pyr_c),
+                                 bias=self._bias(comb.Conv_0), resid=h, scale=1.0, stats=True)
+                        h = hn
+                    elif comb.method == "cat":
+                        # cat([Conv1x1(pyramid), h], 1) (layerspp.py:52-55), written out: the 2C map is the level's h and its skip
+                        # entry, and a decoder block reads it next to a third tensor -- a source is a pair at the most
+                        pc = b.buf(n, hh, ww, cur_c, name="combine")
+                        low.conv(pc, hh, ww, cur_c, aux=_src(pyr, pyr_c), w_aux=self._w1(comb.Conv_0, cin_pad=pyr_c),
+                                 bias=self._bias(comb.Conv_0))
+                        hn = b.buf(n, hh, ww, 2 * cur_c, name="combine_cat")
+                        b.add(L.OP_CONCAT, dict(p0=pc, p1=h, dst=hn, n=n, hw=hh * ww, c0=cur_c, c1=cur_c))
+                        h, cur_c = hn, 2 * cur_c
+                    else:
+                        raise ValueError("Method %s not recognized." % comb.method)
                 elif model.progressive_input == "residual":
-                    down = mods[idx]; idx += 1
-                    if not fir:
-                        raise NotImplementedError("progressive_input='residual' without FIR is not lowered")
-                    # conv_downsample_2d: FIR with pad ((p+1)//2, p//2), p = taps - 2 + 3 - 1 -- (2,2) for four taps -- then
-                    # stride-2 VALID conv (up_or_down_sampling.py:144-178)
-                    pf, ph, pw = low.upfirdn(_src(pyr, pyr_c), pyr_c, hh * 2, ww * 2, fir_taps(fk), pad=fir_pads(len(fk), conv=3),
-                                             name="pyr_fir")
-                    hn = b.buf(n, hh, ww, cur_c, name="pyr")
-                    low.conv(hn, hh, ww, cur_c, main=_src(pf, pyr_c), w_main=self._w3(down.Conv2d_0, cin_pad=pyr_c),
-                             h_in=ph, w_in=pw, stride=2, pad=0, bias=self._bias(down.Conv2d_0), resid=h, scale=skip_scale,
-                             stats=True)
+                    # (pyramid' + h) [/ sqrt(2)] in the epilogue of the Downsample's convolution (ncsnpp.py:294-301); with FIR:
+                    # conv_downsample_2d, pad ((p+1)//2, p//2), p = taps - 2 + 3 - 1 -- (2,2) for four taps -- then the stride-2
+                    # VALID conv (up_or_down_sampling.py:144-178); without: ONE end-padded stride-2 launch
+                    hn, _, _, _ = self._downsample(mods[idx], pyr, pyr_c, hh * 2, ww * 2, resid=h, scale=skip_scale, name="pyr"); idx += 1
                     pyr, pyr_c, h = hn, cur_c, hn
                 hs.append((h, cur_c, hh, ww))
 
@@ -1216,8 +1226,11 @@ class UNetEngine:
                          h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=4), resid=up_pyr)
                 pyramid = pn
             if lvl != 0:
-                h, cur_c = self._res(mods[idx], h, cur_c, hh, ww); idx += 1
-                hh, ww = hh * 2, ww * 2
+                if ddpm_blocks:
+                    h, cur_c, hh, ww = self._upsample(mods[idx], h, cur_c, hh, ww); idx += 1
+                else:
+                    h, cur_c = self._res(mods[idx], h, cur_c, hh, ww); idx += 1
+                    hh, ww = hh * 2, ww * 2
         assert not hs
 
         # ---- head (ncsnpp.py:368-379)
@@ -1252,18 +1265,8 @@ class UNetEngine:
                     h = self._attn(mods[idx], h, cur_c, hh, ww); idx += 1
                 hs.append((h, cur_c, hh, ww))
             if lvl != model.num_resolutions - 1:
-                down = mods[idx]; idx += 1
                 t, c, hh, ww = hs[-1]
-                if down.with_conv:
-                    # F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 / no padding (layers.py:608-611): the zero row and column are the
-                    # launch's pad_end, never a tensor
-                    ho, wo = hh // 2, ww // 2
-                    h = b.buf(n, ho, wo, c, name="down")
-                    low.conv(h, ho, wo, c, main=_src(t, c), w_main=self._w3(down.Conv_0), h_in=hh, w_in=ww, stride=2, pad=0,
-                             pad_end=1, bias=self._bias(down.Conv_0), stats=True)
-                else:
-                    # F.avg_pool2d(x, 2, 2) (layers.py:613): the 2x2 box
-                    h, ho, wo = low.upfirdn(_src(t, c), c, hh, ww, fir_taps([1, 1]), down=2, pad=(0, 0), name="down")
+                h, c, ho, wo = self._downsample(mods[idx], t, c, hh, ww); idx += 1
                 hs.append((h, c, ho, wo))
 
         # ---- bottleneck (ddpm.py:147-153)
@@ -1281,15 +1284,7 @@ class UNetEngine:
             if is_attn(ww):
                 h = self._attn(mods[idx], h, cur_c, hh, ww); idx += 1
             if lvl != 0:
-                up = mods[idx]; idx += 1
-                # F.interpolate(nearest, x2) (layers.py:593): the box resampler with gain 4
-                h, hh, ww = low.upfirdn(_src(h, cur_c), cur_c, hh, ww, fir_taps([1, 1], gain=4.0), up=2, pad=(1, 0), name="up")
-                if up.with_conv:
-                    hn = b.buf(n, hh, ww, cur_c, name="up_conv")
-                    route = low.conv3_route(hh, ww, cur_c, cur_c)
-                    low.conv(hn, hh, ww, cur_c, main=_src(h, cur_c), w_main=self._w3(up.Conv_0, route=route), h_in=hh, w_in=ww,
-                             bias=self._bias(up.Conv_0), route=route, stats=True)
-                    h = hn
+                h, cur_c, hh, ww = self._upsample(mods[idx], h, cur_c, hh, ww); idx += 1
         assert not hs
 
         # ---- head (ddpm.py:168-170)
@@ -1297,6 +1292,51 @@ class UNetEngine:
         o = self._lower_head(gn_m, conv_m, h, cur_c, hh, ww)
         assert idx == len(mods), (idx, len(mods))
         return o, hh, ww
+
+    # -- Downsample / Upsample of both families: layers.py:584-615 (fir is not an attribute there) and layerspp.py:94-163.  An
+    #    epilogue (resid, scale) is what the residual input pyramid adds to its Downsample's convolution (ncsnpp.py:294-301)
+    def _downsample(self, m, t, c, hh, ww, resid=None, scale=1.0, name="down"):
+        """-> (tensor, channels, h, w).  The four forms without FIR and with it: the 2x2 box (F.avg_pool2d) | downsample_2d; ONE
+        end-padded stride-2 launch (F.pad(x, (0, 1, 0, 1)) + 3x3 / stride 2 / no padding: the zero row and column are the launch's
+        pad_end, never a tensor) | conv_downsample_2d, the FIR with pad ((p+1)//2, p//2), p = taps - 2 + 3 - 1, then the stride-2
+        VALID convolution (up_or_down_sampling.py:144-178)."""
+        b, low, n = self.b, self.low, self.n
+        fir = getattr(m, "fir", False)
+        ho, wo = hh // 2, ww // 2
+        if not m.with_conv:
+            assert resid is None
+            taps = fir_taps(m.fir_kernel) if fir else fir_taps([1, 1])
+            h, ho, wo = low.upfirdn(_src(t, c), c, hh, ww, taps, down=2, pad=fir_pads(taps.shape[0]), name=name)
+            return h, c, ho, wo
+        conv = m.Conv2d_0 if fir else m.Conv_0
+        cout = conv.weight.shape[0]
+        geom = dict(main=_src(t, c), h_in=hh, w_in=ww, pad_end=1)
+        if fir:
+            pf, ph, pw = low.upfirdn(_src(t, c), c, hh, ww, fir_taps(m.fir_kernel), pad=fir_pads(len(m.fir_kernel), conv=3),
+                                     name=name + "_fir")
+            geom = dict(main=_src(pf, c), h_in=ph, w_in=pw)
+        h = b.buf(n, ho, wo, cout, name=name)
+        low.conv(h, ho, wo, cout, w_main=self._w3(conv, cin_pad=c if conv.weight.shape[1] != c else None), stride=2, pad=0,
+                 bias=self._bias(conv), resid=resid, scale=scale, stats=True, **geom)
+        return h, cout, ho, wo
+
+    def _upsample(self, m, t, c, hh, ww, name="up"):
+        """-> (tensor, channels, h, w).  F.interpolate(nearest, x2) -- the box resampler with gain 4 -- or upsample_2d with the
+        module's FIR kernel; with_conv: a plain 3x3 convolution behind the nearest form (with FIR the constructor refuses)."""
+        b, low, n = self.b, self.low, self.n
+        fir = getattr(m, "fir", False)
+        assert not (fir and m.with_conv)
+        taps = fir_taps(m.fir_kernel, gain=4.0) if fir else fir_taps([1, 1], gain=4.0)
+        h, hh, ww = low.upfirdn(_src(t, c), c, hh, ww, taps, up=2, pad=fir_pads(taps.shape[0], up=True),
+                                name=name if not m.with_conv else name + "_nearest")
+        if not m.with_conv:
+            return h, c, hh, ww
+        cout = m.Conv_0.weight.shape[0]
+        hn = b.buf(n, hh, ww, cout, name=name)
+        route = low.conv3_route(hh, ww, cout, c)
+        low.conv(hn, hh, ww, cout, main=_src(h, c), w_main=self._w3(m.Conv_0, route=route), h_in=hh, w_in=ww,
+                 bias=self._bias(m.Conv_0), route=route, stats=True)
+        return hn, cout, hh, ww
 
     # -- packed parameter helpers
     def _w3(self, m, cin_pad=None, cout_pad=None, route=DIRECT):

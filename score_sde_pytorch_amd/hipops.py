@@ -112,6 +112,21 @@ def groupnorm_apply_bwd(dy, x, gn, x2=None, silu=True, drop=None, slices=1, g0=N
     return g0, g1, dgamma, dbeta
 
 
+def concat(x, x2):
+    """cat([x, x2], -1) of two NHWC tensors as one contiguous tensor (ssde_concat): a copy, bit for bit.  Channel counts are
+    positive multiples of 4; the library refuses anything else before it launches."""
+    _need_cuda(x, x2)
+    if tuple(x.shape[:-1]) != tuple(x2.shape[:-1]):
+        raise ValueError("concat: %s and %s differ outside the channel axis" % (tuple(x.shape), tuple(x2.shape)))
+    x, x2 = x.contiguous(), x2.contiguous()
+    out = torch.empty(tuple(x.shape[:-1]) + (x.shape[-1] + x2.shape[-1],), device=x.device)
+    a = L.ConcatArgs()
+    a.p0, a.p1, a.dst = _p(x), _p(x2), _p(out)
+    a.n, a.hw, a.c0, a.c1 = x.shape[0], int(np.prod(x.shape[1:-1])), x.shape[-1], x2.shape[-1]
+    L.check(L.load().ssde_concat(C.byref(a), _stream()), "ssde_concat")
+    return out
+
+
 def conv2d(x=None, weight=None, bias=None, stride=1, pad=1, x2=None, pro=L.PRO_NONE, gn=None,
            aux=None, aux2=None, aux_weight=None, aux_pro=L.PRO_NONE, aux_gn=None,
            chan_add=None, resid=None, scale=1.0, tile=L.TILE_AUTO, out_hw=None, flags=None, pad_end=0):

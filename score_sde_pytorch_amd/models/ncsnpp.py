@@ -88,6 +88,29 @@ class AttnBlockpp(nn.Module):
         self.skip_rescale = skip_rescale
 
 
+class ResnetBlockDDPMpp(nn.Module):
+    """DDPM's residual block with NCSN++'s group counts and rescale (models/layerspp.py:166-209): no resampling, an NIN
+    shortcut where the channel count changes.  conv_shortcut is never set by NCSNpp and is not built."""
+    kind = "res"
+
+    def __init__(self, in_ch, out_ch=None, temb_dim=None, dropout=0.1, skip_rescale=False, init_scale=0.0):
+        super().__init__()
+        out_ch = out_ch if out_ch else in_ch
+        self.GroupNorm_0 = _group_norm(in_ch)
+        self.Conv_0 = _conv(in_ch, out_ch, 3, padding=1)
+        if temb_dim is not None:
+            self.Dense_0 = _dense(temb_dim, out_ch)
+        self.GroupNorm_1 = _group_norm(out_ch)
+        self.Dropout_0 = nn.Dropout(dropout)
+        self.Conv_1 = _conv(out_ch, out_ch, 3, init_scale=init_scale, padding=1)
+        if in_ch != out_ch:
+            self.NIN_0 = NIN(in_ch, out_ch)
+        self.in_ch, self.out_ch = in_ch, out_ch
+        self.up = self.down = False
+        self.skip_rescale = skip_rescale
+        self.dropout = dropout
+
+
 class ResnetBlockBigGANpp(nn.Module):
     """BigGAN residual block with optional FIR / box 2x resampling (models/layerspp.py:212-274)."""
     kind = "res"
@@ -212,8 +235,9 @@ class NCSNpp(HipUNet):
         if m.nonlinearity.lower() not in _lib.ACT_BY_NAME:
             raise NotImplementedError("activation function does not exist!")
         self.act_kind = _lib.ACT_BY_NAME[m.nonlinearity.lower()]
-        if m.resblock_type.lower() != "biggan":
-            raise NotImplementedError("resblock_type=%r: every shipped ncsnpp config uses 'biggan'" % m.resblock_type)
+        self.resblock_type = m.resblock_type.lower()
+        if self.resblock_type not in ("biggan", "ddpm"):
+            raise ValueError("resblock type %s unrecognized." % self.resblock_type)
         self.register_buffer("sigmas", torch.tensor(utils.get_sigmas(config)))
         self.nf = nf = m.nf
         ch_mult = tuple(m.ch_mult)
@@ -223,7 +247,6 @@ class NCSNpp(HipUNet):
         self.all_resolutions = [config.data.image_size // (2 ** i) for i in range(nres)]
         self.conditional = m.conditional
         self.skip_rescale = m.skip_rescale
-        self.resblock_type = "biggan"
         self.progressive = m.progressive.lower()
         self.progressive_input = m.progressive_input.lower()
         self.embedding_type = m.embedding_type.lower()
@@ -236,8 +259,13 @@ class NCSNpp(HipUNet):
         if self.embedding_type not in ("fourier", "positional"):
             raise ValueError("embedding type %s unknown." % self.embedding_type)
         if self.progressive == "residual":
-            raise NotImplementedError("progressive='residual' needs Upsample(with_conv, fir) which the reference "
-                                      "cannot run either (SURVEY F7)")
+            raise NotImplementedError("progressive='residual' needs Upsample(with_conv=True) which the reference cannot run either: "
+                                      "with fir it reaches the broken upsample_conv_2d (SURVEY F7), without it F.interpolate is "
+                                      "called with the mode in place of scale_factor and raises (models/layerspp.py:117)")
+        if self.resblock_type == "ddpm" and not self.fir:
+            raise NotImplementedError("resblock_type='ddpm' with fir=False: the reference's first forward raises in "
+                                      "layerspp.Upsample (F.interpolate is called with the mode in place of scale_factor, "
+                                      "models/layerspp.py:117); with fir=True and resamp_with_conv=False it runs, and so does this")
 
         mods = []
         add = mods.append
@@ -252,7 +280,14 @@ class NCSNpp(HipUNet):
             add(_dense(embed_dim, nf * 4))
             add(_dense(nf * 4, nf * 4))
 
+        ddpm_blocks = self.resblock_type == "ddpm"
+        resamp = dict(with_conv=bool(m.resamp_with_conv), fir=self.fir, fir_kernel=self.fir_kernel)
+
         def res_block(in_ch, out_ch=None, up=False, down=False):
+            if ddpm_blocks:
+                assert not (up or down)
+                return ResnetBlockDDPMpp(in_ch, out_ch, temb_dim=nf * 4 if self.conditional else None, dropout=m.dropout,
+                                         skip_rescale=self.skip_rescale, init_scale=m.init_scale)
             return ResnetBlockBigGANpp(in_ch, out_ch, temb_dim=nf * 4 if self.conditional else None, up=up, down=down,
                                        dropout=m.dropout, fir=self.fir, fir_kernel=self.fir_kernel,
                                        skip_rescale=self.skip_rescale, init_scale=m.init_scale)
@@ -281,7 +316,7 @@ class NCSNpp(HipUNet):
                     add(attn_block(cur))
                 skip_chs.append(cur)
             if lvl != nres - 1:
-                add(res_block(cur, down=True))
+                add(Downsample(in_ch=cur, **resamp) if ddpm_blocks else res_block(cur, down=True))
                 if self.progressive_input == "input_skip":
                     add(Combine(dim1=pyr_ch, dim2=cur, method=self.combine_method))
                     if self.combine_method == "cat":
@@ -309,7 +344,7 @@ class NCSNpp(HipUNet):
                 add(_group_norm(cur))
                 add(_conv(cur, channels, 3, init_scale=m.init_scale, padding=1))
             if lvl != 0:
-                add(res_block(cur, up=True))
+                add(Upsample(in_ch=cur, **resamp) if ddpm_blocks else res_block(cur, up=True))
         assert not skip_chs
         if self.progressive != "output_skip":
             add(_group_norm(cur))
