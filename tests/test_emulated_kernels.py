@@ -232,9 +232,13 @@ def test_conv1x1_gemm_kernel(ops, n, h, c1, c2, cout, pro, extras, matrix, pipe,
 
 # rows per workgroup / load-ahead depth of the split kernel (SSDE_X6_BM, SSDE_X6_PF): the two-register-set loop issues every load
 # unconditionally with clamped stage indices -- odd and even stage counts, a ragged last stage, a single stage
-@pytest.mark.parametrize("bm,pf", [("128", "2"), ("64", "1"), ("64", "2")])
-@pytest.mark.parametrize("n,h,c1,c2,cout,pro,extras", [(3, 8, 40, 0, 96, 0, True), (1, 16, 32, 24, 200, 2, True), (2, 16, 64, 32, 256, 1, True),
-                                                       (5, 6, 8, 0, 130, 3, False), (2, 8, 16, 0, 128, 0, False)])
+GEMM1X1_ROWS_CASES = [(3, 8, 40, 0, 96, 0, True), (1, 16, 32, 24, 200, 2, True), (2, 16, 64, 32, 256, 1, True),
+                      (5, 6, 8, 0, 130, 3, False), (2, 8, 16, 0, 128, 0, False)]
+GEMM1X1_ROWS_SHAPES = [("128", "2"), ("64", "1"), ("64", "2")]
+
+
+@pytest.mark.parametrize("bm,pf", GEMM1X1_ROWS_SHAPES)
+@pytest.mark.parametrize("n,h,c1,c2,cout,pro,extras", GEMM1X1_ROWS_CASES)
 def test_conv1x1_gemm_kernel_rows_and_load_ahead(ops, n, h, c1, c2, cout, pro, extras, bm, pf, monkeypatch):
     monkeypatch.setenv("SSDE_X6_BM", bm)
     monkeypatch.setenv("SSDE_X6_PF", pf)
@@ -244,8 +248,10 @@ def test_conv1x1_gemm_kernel_rows_and_load_ahead(ops, n, h, c1, c2, cout, pro, e
 
 # the 128 x 256 tile of the split kernel (SSDE_X6_WIDE=1 forces it; it needs Cout % 256 == 0): ragged M and K, a virtual concat,
 # GroupNorm prologue, the whole epilogue, GroupNorm partials of the output checked through the next layer's statistics
-@pytest.mark.parametrize("n,h,c1,c2,cout,pro,extras", [(3, 8, 40, 0, 256, 0, True), (1, 16, 32, 24, 512, 2, True),
-                                                       (2, 16, 64, 32, 256, 1, True), (5, 4, 64, 0, 256, 3, False)])
+GEMM1X1_WIDE_CASES = [(3, 8, 40, 0, 256, 0, True), (1, 16, 32, 24, 512, 2, True), (2, 16, 64, 32, 256, 1, True), (5, 4, 64, 0, 256, 3, False)]
+
+
+@pytest.mark.parametrize("n,h,c1,c2,cout,pro,extras", GEMM1X1_WIDE_CASES)
 def test_conv1x1_gemm_kernel_wide_tile(ops, n, h, c1, c2, cout, pro, extras, monkeypatch):
     monkeypatch.setenv("SSDE_X6_WIDE", "1")
     test_conv1x1_gemm_kernel(ops, n, h, c1, c2, cout, pro, extras, "bf16x6", "0", monkeypatch)
