@@ -155,7 +155,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino_kernel(const WinoParams
 
   // GroupNorm tables in LDS: (mean, rstd) of every (tile image, group), gamma and beta of every channel
   float* gn_tab = raw + 8 * halo_px;         // [IMGS][groups][2]
-  float* gb_tab = gn_tab + 2 * IMGS * (kGn ? s.gn_groups : 0);   // [2][Ctot]
+  // (rounded up to whole float4s: gamma / beta are read four channels at a time, and IMGS * groups may be odd)
+  float* gb_tab = gn_tab + ((2 * IMGS * (kGn ? s.gn_groups : 0) + 3) & ~3);   // [2][Ctot]
   if (kGn) {
     for (int q = tid; q < IMGS * s.gn_groups; q += kThreads) {
       const int il = q / s.gn_groups, img = img0 + il < p.N ? img0 + il : 0;
@@ -498,7 +499,7 @@ int wino_plan(const ssde_conv_args* a, WinoParams* pp, ssde_conv_plan* pl) {
   const int halo_px = t.imgs * (2 * t.tht + 2) * (2 * t.twt + 2);
   SSDE_REQUIRE(halo_px * 2 <= kMaxRaw * kStagers, "conv(winograd): halo of %d pixels exceeds the staging plan", halo_px);
   pl->lds_bytes = (4 * kStageFloats + 4 * halo_px * 2) * 4;
-  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) pl->lds_bytes += (2 * t.imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
+  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) pl->lds_bytes += (((2 * t.imgs * s.gn_groups + 3) & ~3) + 2 * (s.c0 + s.c1)) * 4;
   SSDE_REQUIRE(pl->lds_bytes <= 160 * 1024, "conv(winograd): %d bytes of LDS", pl->lds_bytes);
   pl->ws_floats = 0;
   return SSDE_OK;

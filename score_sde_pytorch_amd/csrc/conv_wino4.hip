@@ -297,7 +297,8 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   };
   // GroupNorm tables in LDS: (mean, rstd) of every (tile image, group), gamma and beta of every channel
   float* gn_tab = rawb + 2 * raw_stride;       // [IMGS][groups][2]
-  float* gb_tab = gn_tab + 2 * IMGS * (kGn ? s.gn_groups : 0);   // [2][Ctot]
+  // (rounded up to whole float4s: gamma / beta are read four channels at a time, and IMGS * groups may be odd)
+  float* gb_tab = gn_tab + ((2 * IMGS * (kGn ? s.gn_groups : 0) + 3) & ~3);   // [2][Ctot]
   // halo loads of stage st: opaque to hipcc (SSDE_GLOAD16), their vmcnt accounting is the stage body's
   ssde_f32x4 rv[kMaxRaw];
   auto load_piece = [&](int st, int k) __attribute__((always_inline)) {
@@ -784,7 +785,7 @@ int wino4_plan(const ssde_conv_args* a, Wino4Params* pp, ssde_conv_plan* pl) {
   const int halo_px = t.imgs * (4 * t.tht + 2) * (4 * t.twt + 2);
   SSDE_REQUIRE(halo_px <= kMaxRaw * kThreads, "conv(winograd 4x4): halo of %d pixels exceeds the staging plan", halo_px);
   int lds = (2 * kVFloats + 2 * kUFloats + 2 * 2 * 2 * halo_px) * 4;
-  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) lds += (2 * t.imgs * s.gn_groups + 2 * (s.c0 + s.c1)) * 4;
+  if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) lds += (((2 * t.imgs * s.gn_groups + 3) & ~3) + 2 * (s.c0 + s.c1)) * 4;
   const int lds_epi = kPos * 16 * kLdm * 4;
   if (lds < lds_epi) lds = lds_epi;
   p.ticket_off = lds / 4;

@@ -20,19 +20,37 @@ differently), and a row whose flag falls back to another kernel is listed under 
 The tiling states each case is listed for (the `states` of a row) are restated from the plan functions below (wino_tiling,
 direct_tiling, wgrad_direct_tiling) and asserted by check_table_states, so a row cannot claim a state it does not hit.
 
+The fourth form of every forward row, "accumulate-in-place", is the launch the backward lowering issues for every input
+gradient (TrainEngine._bwd_branch): dst preloaded with a base, resid == dst, resid_post = 1, out_scale = 0.7, no bias / addend /
+partials, against fp64 0.7 conv + base.  Every kernel reads the residual it overwrites, and the split reductions use dst as
+the hand-over buffer between workgroups: the rows where the alias changes the plan (direct 128+0-64-4x8 t3, f4 128+0-64-8x12,
+f4r 128+128-64-8x12, f4p ks2 / ks4) are the point of the form -- see check_forward.  Two 1x1 rows force the persistent and the
+128 x 256 GEMM kernels, so that three GEMM kernels run aliased.
+
 Largest errors seen (every check prints its own); the bound is 2e-5 everywhere, 1e-5 / 1e-4 for the finalized mean / rstd:
-                                   emulator (exact fp32)   MI355X (both matrix modes)
+                                   emulator (exact fp32)   MI355X (both matrix modes; the first three forms)
   forward  f2                      2.7e-7                  2.7e-7
-           f4 / f4r / f4p          4.5e-6 / 6.7e-6 / 5.8e-6   5.0e-6 / 6.7e-6 / 6.0e-6
-           direct / small / 1x1    1.0e-6 / 3.5e-7 / 3.5e-7   1.0e-6 / 3.5e-7 / 3.5e-7
+           f4 / f4r / f4p          6.0e-6 / 6.7e-6 / 5.8e-6   5.0e-6 / 6.7e-6 / 6.0e-6
+           direct / small / 1x1    1.0e-6 / 3.5e-7 / 5.0e-7   1.0e-6 / 3.5e-7 / 3.5e-7
            partials: mean, rstd    7.5e-7, 5.3e-7          4.7e-7, 6.2e-7
+  of these, accumulate-in-place (not measured on the MI355X yet):
+           f2                      2.2e-7                  -
+           f4 / f4r / f4p          6.0e-6 / 6.5e-6 / 5.6e-6   -
+           direct / small / 1x1    1.0e-6 / 2.5e-7 / 4.5e-7   -
   wgrad    f4 / f2 / direct        1.7e-6 / 4.2e-7 / 5.5e-7   1.7e-6 / 2.7e-7 / 4.9e-7
-The sweep (emulator only): 330 draws, 23 refused, 23 to 30 accepted launches per route and form, largest error 4.0e-6.
-No case of the tables or of the sweep found a kernel wrong.
+The sweep (emulator only): 330 draws, 20 refused, 21 to 30 accepted launches per route and form of the weight gradient, 45 to 50
+forward launches per form, largest error 4.2e-6.  The forms are drawn from a stream of their own, so the drawn shapes are
+those of the sweep before the fourth form.
+The tables found no kernel wrong.  The sweep found one fault: conv_wino.hip and conv_wino4.hip put the gamma / beta table,
+which they read as float4, in LDS behind 2 x images x groups floats of (mean, rstd) -- 8 bytes off a 16-byte boundary when one
+image per workgroup meets an odd number of GroupNorm groups (12 channels in 3 groups on a 16x24 map: the emulator's aligned
+16-byte load faults; the networks' 32 groups never get there).  The kernels and their plans now round that table up to whole
+float4s; the f2 row 1-12+0-72-16x24 and the f4 row 1-12+0-40-20x32 keep the layout in the table.
 """
 import ctypes as C
 import functools
 import math
+import os
 import random
 import zlib
 from collections import namedtuple
@@ -136,7 +154,34 @@ TILE_OF = {"f2": L.TILE_WINOGRAD, "f4": L.TILE_WINOGRAD4, "f4r": L.TILE_WINOGRAD
 ROUTE_IN_MESSAGE = {"f2": "conv(winograd):", "f4": "conv(winograd 4x4):", "f4r": "conv(winograd 4x4, register-fed):",
                     "f4p": "conv(winograd 4x4, position-batched):", "direct": "conv:"}
 FLAG_NAMES = {L.CONVF_NO_KSPLIT: "noksplit", L.CONVF_BKC8: "bkc8", L.CONVF_KSPLIT2: "ks2", L.CONVF_KSPLIT4: "ks4",
-              L.CONVF_NO_SMALL_COUT: "nosmall"}
+              L.CONVF_NO_SMALL_COUT: "nosmall", L.CONVF_BF16X6: "x6", L.CONVF_GEMM_PIPE: "pipe", L.CONVF_X6_WIDE: "wide"}
+# the 1x1 rows that force a GEMM kernel of conv1x1.hip other than the one the launch would get (both exist in the 3-way bf16 split
+# only, so the rows pin that matrix mode): the persistent pipelined kernel on a pretend 3-CU device, where 8 workgroups share
+# the tiles and some own several (SSDE_NUM_CUS is read by the library at every plan), and the 128 x 256 tile
+GEMM_FORCED = L.CONVF_GEMM_PIPE | L.CONVF_X6_WIDE
+
+
+def row_env(c):
+    return {"SSDE_NUM_CUS": "3"} if c.route == "1x1" and c.flags & L.CONVF_GEMM_PIPE else {}
+
+
+class _Env:
+    """the environment of a row around its plan queries and launches, put back afterwards"""
+
+    def __init__(self, env):
+        self.env, self.saved = env, {}
+
+    def __enter__(self):
+        for k, v in self.env.items():
+            self.saved[k] = os.environ.get(k)
+            os.environ[k] = v
+
+    def __exit__(self, *exc):
+        for k, v in self.saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def fwd(route, n, c0, c1, cout, h, w, tile=None, flags=0, stride=1, pad=1, pad_end=0, out_hw=None, aux=None, drop=False, states=()):
@@ -176,11 +221,16 @@ def _wino_rows(route):
             fwd(route, 3, 8, 8, 64, 10, 14, states=[COL, ROW, IMGS_TAIL, MANY_TILES]),     # even, no multiple of 4: f2 only
             fwd(route, 2, 16, 0, 40, 20, 20, states=[COL, ROW, MANY_TILES]),             # one image per workgroup (16x16 px): partials
             fwd(route, 1, 8, 0, 64, 24, 16, states=[ROW, MANY_TILES]),                   # one image per workgroup, partial rows only
+            # 12 channels in 3 GroupNorm groups, one image per workgroup: an odd number of (mean, rstd) pairs in front of the
+            # gamma / beta table in LDS, which is read as float4 (it stood 8 bytes off a 16-byte boundary: the sweep found it)
+            fwd(route, 1, 12, 0, 72, 16, 24, states=[COL, MANY_TILES]),
         ]
     if route == "f4":
         # 128 channels on 8 workgroups: the reduction is split over two workgroups per tile (ssde_conv_wino4_splits), and not
         rows += [fwd(route, 2, 128, 0, 64, 8, 12, states=[COL, IMGS_TAIL, MANY_TILES]),
-                 fwd(route, 2, 128, 0, 64, 8, 12, flags=L.CONVF_NO_KSPLIT, states=[COL, IMGS_TAIL, MANY_TILES])]
+                 fwd(route, 2, 128, 0, 64, 8, 12, flags=L.CONVF_NO_KSPLIT, states=[COL, IMGS_TAIL, MANY_TILES]),
+                 # one image per workgroup (16x32 px) and 3 GroupNorm groups: the same LDS layout as the f2 row of 12 channels
+                 fwd(route, 1, 12, 0, 40, 20, 32, states=[ROW, MANY_TILES])]
     if route == "f4r":
         # 256 channels on 8 workgroups: the register-fed kernel's own split, four shares (ssde_conv_wino4r_splits), and not
         rows += [fwd(route, 2, 128, 128, 64, 8, 12, states=[COL, IMGS_TAIL, MANY_TILES]),
@@ -247,12 +297,18 @@ def _small_rows():
 def _gemm_rows():
     """the 1x1 row of the table: a 1x1-only launch of at least 128 rows onto at least 96 channels; rows = n * h * w are no
     multiple of the 64 / 128-row tiles"""
-    return [fwd("1x1", 3, 40, 0, 96, 7, 9), fwd("1x1", 1, 32, 32, 132, 12, 20), fwd("1x1", 5, 64, 0, 200, 6, 10, drop=True)]
+    return [fwd("1x1", 3, 40, 0, 96, 7, 9), fwd("1x1", 1, 32, 32, 132, 12, 20), fwd("1x1", 5, 64, 0, 200, 6, 10, drop=True),
+            # two more GEMM kernels, so that more than one runs with resid == dst (shapes of test_ops_gpu.py: GEMM1X1_CASES and the
+            # wide-tile cases).  The persistent kernel: 2 x 2 tiles of 128 x 128 on 8 workgroups, two of which own two tiles each,
+            # and it fetches a unit's residual rows while it still stores the unit before; the 128 x 256 tile: 192 = 128 + 64 rows
+            fwd("1x1", 1, 32, 24, 200, 16, 16, flags=L.CONVF_BF16X6 | L.CONVF_GEMM_PIPE),
+            fwd("1x1", 3, 40, 0, 256, 8, 8, flags=L.CONVF_BF16X6 | L.CONVF_X6_WIDE)]
 
 
 FWD_CASES = _wino_rows("f2") + _wino_rows("f4") + _wino_rows("f4r") + _f4p_rows() + _direct_rows() + _small_rows() + _gemm_rows()
 assert len(set(FWD_CASES)) == len(FWD_CASES)
-FORMS = ("plain", "fused-resid-before-scale", "fused-resid-after-scale")
+FORMS = ("plain", "fused-resid-before-scale", "fused-resid-after-scale", "accumulate-in-place")
+INPLACE, INPLACE_SCALE = FORMS[3], 0.7
 
 # Shapes just outside a route's limits: (row, a word of the message beyond the route's name).  The plan query refuses them; nothing
 # is launched.  (small has no refusal of its own: what it does not want goes to the direct kernel -- check_small_edges.)
@@ -291,7 +347,8 @@ def check_table_states():
         if c.route == "f4p":
             assert (c.n * (c.h // 4) * (c.w // 4)) % 64 != 0        # a partial block of GEMM rows
         if c.route == "1x1":
-            assert (c.n * c.h * c.w) % 64 != 0 and c.n * c.h * c.w >= 128 and c.cout >= 96
+            # (the rows that force a GEMM kernel take their shapes from test_ops_gpu.py, whole 64-row tiles among them)
+            assert ((c.n * c.h * c.w) % 64 != 0 or c.flags & GEMM_FORCED) and c.n * c.h * c.w >= 128 and c.cout >= 96
     for tile in DIRECT_TILES:
         assert any(c.route == "direct" and c.tile == tile for c in FWD_CASES)
     for form, cases in (("wgrad direct", [c for c in WGRAD_CASES if c.runs == "direct"]),):
@@ -373,7 +430,7 @@ def fwd_inputs(c):
 def _modes(c, form):
     """(prologue of main, prologue of aux, dropout armed) of a form: the fused forms put GroupNorm + SiLU on the (concatenated)
     k x k source -- on the 1x1 source of a 1x1-only launch -- and SiLU on the 1x1 source beside a k x k one"""
-    if form == "plain":
+    if form in ("plain", INPLACE):
         return L.PRO_NONE, L.PRO_NONE, False
     if c.route == "1x1":
         return L.PRO_NONE, L.PRO_GN_SILU, c.drop
@@ -394,8 +451,11 @@ def fwd_ref(c, form):
         if "aux" in k:
             s = k["aux"]
             y = y + _pro64(s["x"], pa, s["G"], s["gamma"], s["beta"], s["keep"] if drop else None) @ k["wa"].double().t()
-        y = y + k["bias"].double()
-        if form != "plain":
+        if form == INPLACE:
+            y = INPLACE_SCALE * y + k["resid"].double()
+        else:
+            y = y + k["bias"].double()
+        if form not in ("plain", INPLACE):
             y = y + k["chan_add"].double()[:, None, None, :]
             r, sc = k["resid"].double(), 1.0 / math.sqrt(2.0)
             y = (y + r) * sc if form == FORMS[1] else y * sc + r
@@ -436,6 +496,8 @@ def fwd_args(c, form, dev=None):
                 if mode in (L.PRO_GN, L.PRO_GN_SILU):
                     s.gn_groups, s.gn_mean, s.gn_rstd, s.gn_gamma, s.gn_beta = _groups(cc[0] + cc[1]), dummy, dummy, dummy, dummy
         a.w_main, a.w_aux, a.dst = (dummy if c.route != "1x1" else None), (dummy if aux else None), dummy
+        if form == INPLACE:
+            a.resid = a.dst
     else:
         ops, _ = _ops()
         k = fwd_inputs(c)
@@ -449,12 +511,16 @@ def fwd_args(c, form, dev=None):
             wa = pack_matrix(k["wa"].to(dev))
             a.w_aux = wa.data_ptr()
             keep.append(wa)
-        dst = torch.full((c.n, ho, wo, c.cout), float("nan")).to(dev)
-        a.dst = dst.data_ptr()
-        b = k["bias"].to(dev)
-        a.bias = b.data_ptr()
-        keep.append(b)
-        if form != "plain":
+        if form == INPLACE:
+            dst = k["resid"].clone().to(dev)
+            a.dst = a.resid = dst.data_ptr()
+        else:
+            dst = torch.full((c.n, ho, wo, c.cout), float("nan")).to(dev)
+            a.dst = dst.data_ptr()
+            b = k["bias"].to(dev)
+            a.bias = b.data_ptr()
+            keep.append(b)
+        if form not in ("plain", INPLACE):
             ca, r = k["chan_add"].to(dev), k["resid"].to(dev)
             a.chan_add, a.chan_add_ld, a.resid = ca.data_ptr(), c.cout, r.data_ptr()
             keep += [ca, r]
@@ -468,7 +534,9 @@ def fwd_args(c, form, dev=None):
         a.ksize, a.stride, a.pad = 0, 1, 0
     a.n, a.h_out, a.w_out, a.c_out, a.tile = c.n, ho, wo, c.cout, c.tile
     a.flags = L.conv_route_flags() | c.flags                    # (the matrix mode of the run: SSDE_MATRIX)
-    if form != "plain":
+    if form == INPLACE:
+        a.out_scale, a.resid_post = INPLACE_SCALE, 1
+    elif form != "plain":
         a.out_scale, a.resid_post = 1.0 / math.sqrt(2.0), int(form == FORMS[2])
     else:
         a.out_scale = 1.0
@@ -477,11 +545,21 @@ def fwd_args(c, form, dev=None):
 
 def fwd_plan(c, form="plain"):
     """the plan query on the shape alone: the LDS bytes of the launch; raises SsdeError with the library's message on a refusal"""
+    with _Env(row_env(c)):
+        return _fwd_plan(c, form)
+
+
+def _fwd_plan(c, form):
     _, lib = _ops()
     a, _, _ = fwd_args(c, form)
     rc = lib.ssde_conv_lds_bytes(C.byref(a))
     if rc < 0:
         raise L.SsdeError(lib.ssde_last_error().decode())
+    if c.route == "1x1" and c.flags & GEMM_FORCED:
+        # a forced GEMM kernel is not refused where it cannot run (gemm_plan's pipe_ok / wide_ok): the launch would get the kernel
+        # it gets anyway.  The three kernels ask for different amounts of LDS, so the plan tells whether the forced one runs
+        a.flags &= ~GEMM_FORCED
+        assert lib.ssde_conv_lds_bytes(C.byref(a)) != rc, (fwd_id(c), form, "the forced GEMM kernel does not take this launch", rc)
     # the two routes that are taken by shape rather than by tile do not refuse what they do not want: the direct kernel runs it.
     # A row listed for them must be theirs (ssde_conv1x1_wants restated; the small-cout kernel's plan is not the direct one's)
     if c.route == "1x1" and not (c.cout >= 96 and c.n * c.h * c.w >= 128):
@@ -495,7 +573,20 @@ def fwd_plan(c, form="plain"):
 
 def check_forward(dev, c, form):
     """one launch of a row in one form: planned, launched into NaN, compared with fp64; GroupNorm partials where the tiling
-    writes them, finalized and compared with the fp64 statistics of the fp64 reference output.  Returns the error."""
+    writes them, finalized and compared with the fp64 statistics of the fp64 reference output.  Returns the error.
+    The form "accumulate-in-place" is the launch the backward lowering issues for every input gradient (TrainEngine._bwd_branch):
+    dst preloaded with a base (the row's `resid` tensor), resid == dst, resid_post = 1, out_scale = 0.7 (neither 1 nor 1/sqrt(2):
+    (base + conv) s, conv s + base and the fused forms all differ), no bias, no per-image addend, no partials; the reference is
+    fp64 0.7 conv + base.  Every kernel reads the residual it is about to overwrite, and the split reductions hand partial sums
+    over between workgroups through dst itself: the rows `direct ... 128+0-64-4x8 t3`, `f4 ... 128+0-64-8x12`,
+    `f4r ... 128+128-64-8x12` and the f4p ks2 / ks4 rows, where the alias changes the plan (make_plan of conv_mfma.hip and
+    ssde_conv_wino4r_launch drop the split for resid == dst), are the point of the form.  Both plan queries are made on
+    arguments that carry the alias."""
+    with _Env(row_env(c)):
+        return _check_forward(dev, c, form)
+
+
+def _check_forward(dev, c, form):
     ops, lib = _ops()
     assert fwd_plan(c, form) > 0                                # (raises with the message: a listed case must be accepted)
     a, dst, keep = fwd_args(c, form, dev)
@@ -506,7 +597,7 @@ def check_forward(dev, c, form):
         assert need > 0, (fwd_id(c), lib.ssde_last_error())
         ws = torch.full((need,), float("nan")).to(dev)
         a.wino_ws, a.wino_ws_floats = ws.data_ptr(), need
-    sl = lib.ssde_conv_gn_slices(C.byref(a))
+    sl = lib.ssde_conv_gn_slices(C.byref(a)) if form != INPLACE else 0          # (the backward lowering asks for no partials)
     part = None
     if sl > 0:
         part = torch.full((c.n, sl, c.cout // 4, 3), float("nan")).to(dev)
@@ -534,7 +625,10 @@ def check_forward(dev, c, form):
         assert stats[0] < TOL_MEAN and stats[1] < TOL_RSTD, (fwd_id(c), form, stats)
     # a second launch on the same arguments into fresh NaN: a split reduction left its hand-over slots ready, and every route
     # sums in a fixed order -- the same bits (but where f4 / f4r hand a reduction over between workgroups in arrival order)
-    dst.fill_(float("nan"))
+    if form == INPLACE:
+        dst.copy_(fwd_inputs(c)["resid"])                        # (from the restored base)
+    else:
+        dst.fill_(float("nan"))
     if part is not None:
         first_part = part.clone()
         part.fill_(float("nan"))
@@ -549,7 +643,8 @@ def check_forward(dev, c, form):
 
 
 def check_forward_case(dev, c):
-    """a row plain, then fully fused with the residual before and after the scale"""
+    """a row plain, then fully fused with the residual before and after the scale, then as the in-place accumulation of an
+    input gradient"""
     return max(check_forward(dev, c, form) for form in FORMS)
 
 
@@ -879,10 +974,11 @@ def check_sweep(dev, seed=20240917):
     counted.  At most a quarter of the draws may be refused and every route / form must have run SWEEP_FLOOR cases, so the sweep
     cannot pass by skipping.  The time is bounded by the number of draws (SWEEP_DRAWS per route and form, small shapes)."""
     rng = random.Random(seed)
-    ran, refused, worst = {}, {}, 0.0
+    form_rng = random.Random(seed + 1)       # (the forms from a stream of their own: a form more or fewer leaves the drawn shapes alone)
+    ran, refused, worst, by_form = {}, {}, 0.0, {}
     for i in range(SWEEP_DRAWS):
         for route in SWEEP_FWD:
-            c, form = draw_forward(rng, route), rng.choice(FORMS)
+            c, form = draw_forward(rng, route), form_rng.choice(FORMS)
             ho, wo = out_size(c)
             try:
                 if ho < 1 or wo < 1:
@@ -893,6 +989,7 @@ def check_sweep(dev, seed=20240917):
                 continue
             worst = max(worst, check_forward(dev, c, form))
             ran[route] = ran.get(route, 0) + 1
+            by_form[form] = by_form.get(form, 0) + 1
         for form in SWEEP_WG:
             c = draw_wgrad(rng, form)
             try:
@@ -905,8 +1002,10 @@ def check_sweep(dev, seed=20240917):
             key = "wgrad-" + form if form in ("auto", route) else "wgrad-%s-fell-back" % form
             ran[key] = ran.get(key, 0) + 1
     drawn = SWEEP_DRAWS * (len(SWEEP_FWD) + len(SWEEP_WG))
-    print("sweep: %d drawn, %d refused (%s), ran %s, largest error %.3g" % (drawn, sum(refused.values()), refused, ran, worst))
+    print("sweep: %d drawn, %d refused (%s), ran %s, forward launches by form %s, largest error %.3g"
+          % (drawn, sum(refused.values()), refused, ran, by_form, worst))
     assert sum(refused.values()) <= SWEEP_REFUSED_MAX * drawn, (refused, drawn)
+    assert set(by_form) == set(FORMS), by_form
     for key in SWEEP_FWD + tuple("wgrad-" + f for f in SWEEP_WG):
         assert ran.get(key, 0) >= SWEEP_FLOOR, (key, ran)
     return ran, refused

@@ -507,8 +507,9 @@ def compare_param_grads(model, flat, ref, tol=TOL_GRAD):
     return worst
 
 
-def check_unet_grads(kind, dev, cfg=None, batch=2):
-    """All parameter gradients and the input gradient of a whole network vs autograd through the CPU oracle."""
+def check_unet_grads(kind, dev, cfg=None, batch=2, hw=None):
+    """All parameter gradients and the input gradient of a whole network vs autograd through the CPU oracle.  hw = (H, W): a
+    rectangular image instead of the square one of cfg.data.image_size (rect_cfg makes the config that goes with it)."""
     from score_sde_pytorch_amd.models import utils as mutils
     from score_sde_pytorch_amd import backward as B
     cfg = cfg or small_cfg(kind)
@@ -517,19 +518,95 @@ def check_unet_grads(kind, dev, cfg=None, batch=2):
     sd = {k: v.clone() for k, v in _util.load_seeded(model, seed=1).items()}
     sd["sigmas"] = model.sigmas.clone()
     model = model.to(dev)
-    R = cfg.data.image_size
+    H, W = hw or (cfg.data.image_size, cfg.data.image_size)
     g = torch.Generator().manual_seed(11)
-    x = torch.randn(batch, 3, R, R, generator=g) * 2
+    x = torch.randn(batch, 3, H, W, generator=g) * 2
     cond = torch.exp(torch.rand(batch, generator=g) * 4 - 2) if cfg.model.embedding_type == "fourier" \
         else torch.rand(batch, generator=g) * 900 + 50
-    gout = torch.randn(batch, 3, R, R, generator=g)
+    gout = torch.randn(batch, 3, H, W, generator=g)
     y_ref, gx_ref, ref = oracle_grads(cfg, sd, x, cond, gout)
-    eng = B.TrainEngine(model, batch, R, R, torch.device(dev), input_grad=True, dropout=False)
+    eng = B.TrainEngine(model, batch, H, W, torch.device(dev), input_grad=True, dropout=False)
     y = eng.forward_train(x.to(dev), cond.to(dev)).clone()
-    assert rel_err(y, y_ref) < 1e-4
+    e_fwd = rel_err(y, y_ref)
+    assert e_fwd < 1e-4, e_fwd
     eng.backward(gout.to(dev))
-    assert rel_err(eng.gx_view(), gx_ref) < TOL_GRAD
-    return compare_param_grads(model, eng.flat, ref)
+    e_gx = rel_err(eng.gx_view(), gx_ref)
+    assert e_gx < TOL_GRAD, e_gx
+    worst = compare_param_grads(model, eng.flat, ref)
+    print("%s %dx%d batch %d vs the oracle: forward %.3g, input gradient %.3g, worst parameter gradient %.3g" % (kind, H, W, batch, e_fwd, e_gx, worst))
+    return worst
+
+
+# Whole networks on rectangular images (h, w): cfg.data.image_size = w and attn_resolutions = (w // 2,), so the attention blocks
+# of the second level run on a rectangular map whose token count is no power of two.  The square cases leave all of this
+# unreached in the backward lowering: the crop geometry of the strided input gradients, the single pad pair of the FIR
+# adjoint, column sums, GroupNorm backward and attention backward on h != w.  Batch 3; the bounds are those of the square cases
+# (1e-4 forward, TOL_GRAD for the input gradient and every parameter gradient).  The three (1, 2, 2) cases have an odd 3x5
+# bottom map: FIR up and down on it and the fall-backs of the F(.,3x3) routes; in the ddpm family the end-padded stride-2
+# launch and its cropped transposed gradient on the 6x10 -> 3x5 step.
+# Largest errors seen, forward / input gradient / worst parameter gradient (bounds 1e-4 / 2e-4 / 2e-4):
+#                                emulator                      MI355X, f32 / bf16x6
+#   ncsnpp 20x12 (1, 2)          7.1e-7 / 1.0e-6 / 6.1e-6      not measured yet
+#   ddpmpp 24x8 (1, 2)           1.2e-6 / 3.7e-6 / 8.2e-6      not measured yet
+#   ddpm 8x24 (1, 1)             1.4e-6 / 1.6e-6 / 7.7e-6      not measured yet
+#   ncsnpp 12x20 (1, 2, 2)       (GPU only)                    not measured yet
+#   ddpmpp 12x20 (1, 2, 2)       (GPU only)                    not measured yet
+#   ddpm 12x20 (1, 2, 2)         (GPU only)                    not measured yet
+RECT_EMULATED = [("ncsnpp", (20, 12), (1, 2)), ("ddpmpp", (24, 8), (1, 2)), ("ddpm", (8, 24), (1, 1))]
+RECT_GPU_ONLY = [("ncsnpp", (12, 20), (1, 2, 2)), ("ddpmpp", (12, 20), (1, 2, 2)), ("ddpm", (12, 20), (1, 2, 2))]
+
+
+def rect_id(case):
+    return "%s-%dx%d-mult%s" % (case[0], case[1][0], case[1][1], "".join(map(str, case[2])))
+
+
+def rect_cfg(kind, hw, ch_mult):
+    if kind == "ddpm":
+        import _ddpm_util
+        cfg = _ddpm_util.small_config(ch_mult=tuple(ch_mult), attn_resolutions=(hw[1] // 2,))
+        cfg.data.image_size = hw[1]
+        return cfg
+    return _util.small_config(kind, image_size=hw[1], ch_mult=tuple(ch_mult), attn=(hw[1] // 2,))
+
+
+def check_rect_grads(dev, case):
+    kind, hw, ch_mult = case
+    cfg = rect_cfg(kind, hw, ch_mult)
+    assert cfg.data.image_size == hw[1] and tuple(cfg.model.attn_resolutions) == (hw[1] // 2,) and hw[0] != hw[1]
+    return check_ddpm_grads(dev, cfg, batch=3, hw=hw) if kind == "ddpm" else check_unet_grads(kind, dev, cfg=cfg, batch=3, hw=hw)
+
+
+def check_ddpm_grads(dev, cfg, batch=3, hw=None):
+    """check_unet_grads for the `ddpm` family: forward, input gradient and every parameter gradient against fp64 autograd
+    through the restatement, _ddpm_oracle.ddpm_forward(..., dtype=torch.float64)."""
+    import _ddpm_oracle
+    from score_sde_pytorch_amd.models import utils as mutils
+    from score_sde_pytorch_amd import backward as B
+    torch.manual_seed(0)
+    model = mutils.get_model("ddpm")(cfg)
+    sd = {k: v.clone() for k, v in _util.load_seeded(model, seed=1).items()}
+    sd["sigmas"] = model.sigmas.clone()
+    model = model.to(dev)
+    H, W = hw or (cfg.data.image_size, cfg.data.image_size)
+    g = torch.Generator().manual_seed(13)
+    x = torch.rand(batch, 3, H, W, generator=g) * 2 - 1 + 0.5 * torch.randn(batch, 3, H, W, generator=g)
+    labels = torch.randint(0, cfg.model.num_scales, (batch,), generator=g).float()
+    gout = torch.randn(batch, 3, H, W, generator=g)
+    sd_req = {k: (v.clone().requires_grad_() if k != "sigmas" else v) for k, v in sd.items()}
+    xr = x.clone().requires_grad_()
+    y_ref = _ddpm_oracle.ddpm_forward(cfg, sd_req, xr, labels, dtype=torch.float64)
+    y_ref.backward(gout.double())
+    ref = {k: v.grad for k, v in sd_req.items() if k != "sigmas"}
+    eng = B.TrainEngine(model, batch, H, W, torch.device(dev), input_grad=True, dropout=False)
+    y = eng.forward_train(x.to(dev), labels.to(dev)).clone()
+    e_fwd = rel_err(y, y_ref.detach())
+    assert e_fwd < 1e-4, e_fwd
+    eng.backward(gout.to(dev))
+    e_gx = rel_err(eng.gx_view(), xr.grad)
+    assert e_gx < TOL_GRAD, e_gx
+    worst = compare_param_grads(model, eng.flat, ref)
+    print("ddpm %dx%d batch %d vs the fp64 restatement: forward %.3g, input gradient %.3g, worst parameter gradient %.3g" % (H, W, batch, e_fwd, e_gx, worst))
+    return worst
 
 
 def check_deferred_finish_is_bit_identical(dev, monkeypatch, kind="ncsnpp"):

@@ -331,6 +331,15 @@ def test_emulated_small_network_forward_and_gradients():
 
 
 @needs_emu
+def test_emulated_whole_network_gradients_on_a_rectangular_image():
+    """8x24, attention on 4x12 = 48 tokens, against the fp64 restatement (tests/_train_checks.py: RECT_EMULATED)"""
+    import _train_checks as T
+    (case,) = [c for c in T.RECT_EMULATED if c[0] == "ddpm"]
+    with emu.emulated():
+        T.check_rect_grads("cpu", case)
+
+
+@needs_emu
 def test_emulated_training_loss_and_gradients_match_reference(monkeypatch):
     """the fused loss head + backward program on a DDPM model under the emulator, against the reference's loss.backward()"""
     from score_sde_pytorch_amd import losses

@@ -181,3 +181,10 @@ def test_whole_network_gradients_against_the_restatement():
     eng.backward(gout.cuda())
     assert rel_err(eng.gx_view(), xr.grad) < T.TOL_GRAD
     T.compare_param_grads(model, eng.flat, ref)
+
+
+@pytest.mark.parametrize("case", [c for c in T.RECT_EMULATED + T.RECT_GPU_ONLY if c[0] == "ddpm"], ids=T.rect_id)
+def test_whole_network_gradients_on_a_rectangular_image(case):
+    """h != w against the fp64 restatement: attention on a rectangular map; at 12x20 the end-padded stride-2 launch and its
+    cropped transposed gradient on the 6x10 -> 3x5 step (tests/_train_checks.py: RECT_*)"""
+    T.check_rect_grads("cuda", case)

@@ -68,6 +68,12 @@ def test_whole_network_gradients(kind):
     T.check_unet_grads(kind, "cpu")
 
 
+@pytest.mark.parametrize("case", [c for c in T.RECT_EMULATED if c[0] != "ddpm"], ids=T.rect_id)
+def test_whole_network_gradients_on_a_rectangular_image(case):
+    """the backward lowering on h != w, attention on a rectangular map (tests/_train_checks.py: RECT_EMULATED)"""
+    T.check_rect_grads("cpu", case)
+
+
 def test_whole_network_gradients_winograd_f4x4(monkeypatch):
     """forward and input-gradient convolutions on the F(4x4,3x3) kernel wherever it is legal"""
     monkeypatch.setenv("SSDE_WINOGRAD", "4")

@@ -49,6 +49,12 @@ def test_whole_network_gradients_small(kind):
     T.check_unet_grads(kind, "cuda", batch=3)
 
 
+@pytest.mark.parametrize("case", [c for c in T.RECT_EMULATED + T.RECT_GPU_ONLY if c[0] != "ddpm"], ids=T.rect_id)
+def test_whole_network_gradients_on_a_rectangular_image(case):
+    """the backward lowering on h != w, attention on a rectangular map, an odd 3x5 bottom map (tests/_train_checks.py: RECT_*)"""
+    T.check_rect_grads("cuda", case)
+
+
 def test_whole_network_gradients_cifar_ncsnpp():
     """the full BASELINE architecture (62.8 M parameters), batch 2"""
     T.check_unet_grads("ncsnpp", "cuda", cfg=_util.cfgs.get_config("ve/cifar10_ncsnpp_continuous", dropout=0.0), batch=2)
