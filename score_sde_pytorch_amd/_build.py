@@ -25,7 +25,7 @@ def _newer(src, dst):
 def build(force=False, verbose=False):
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "ssde_common.h"), os.path.join(HERE, "..", "include", "ssde.h")]
+    headers = [os.path.join(CSRC, "ssde_common.h"), os.path.join(CSRC, "wino4_common.h"), os.path.join(HERE, "..", "include", "ssde.h")]
     hdr_mtime = max(os.path.getmtime(h) for h in headers)
 
     def compile_one(name):

@@ -56,10 +56,8 @@
 // over all launches of the bench command): 0.40 in round 2 and in round 3 -- under rocprofv3 --pmc the kernel runs 26 %
 // slower than unprofiled (408 vs 323 us per launch in one process), so the ratio understates the unprofiled kernel and moved
 // less than the +7-10 % the same-box A/B shows.  The shader clock inside the kernel (s_memtime / s_memrealtime): 2.09-2.17 GHz.
-#include "ssde_common.h"
+#include "wino4_common.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // -DSSDE_W4_TRACE (tools/wino4_trace.py, a variant library only): s_memtime stamps of waves 0 and 7 of the first workgroup
 #ifdef SSDE_W4_TRACE
@@ -87,11 +85,6 @@ extern "C" int ssde_debug_w4_trace(void* buf) {
 #ifndef SSDE_W4_PF
 #define SSDE_W4_PF 3
 #endif
-// rows of the output tile a thread has in flight in the second round of the shared epilogue (residual loads issued before
-// the first use; the first round still holds half of the accumulators and keeps 4)
-#ifndef SSDE_W4_EPI_BATCH
-#define SSDE_W4_EPI_BATCH 8
-#endif
 
 namespace {
 
@@ -102,7 +95,6 @@ constexpr int kWaves = 8;
 constexpr int kThreads = kWaves * 64;
 constexpr int kNP = 72 / kWaves;                   // positions per wave
 constexpr int kPS = kWaves / 2;                    // wave (q, h) owns positions q + kPS * j
-constexpr int kEpiThreads = 512;                   // threads of the output transform and of the shared epilogue
 constexpr int kPos = 36, kTiles = 32, kKc = 4;
 // LDS paddings, A/B-timed (profiles/r2_wino4_ab_lds_padding.txt): a V pitch of 128 + 24 (second transform pass free of bank
 // conflicts instead of the first) and raw channel-pair planes 32 banks apart are both neutral: 35 % of the LDS cycles are
@@ -117,53 +109,31 @@ constexpr int kUFloats = kPos * 64 * kKc;           // 9216: one U stage
 constexpr int kURegion = kNP * 32 * kKc;            // 1152: the floats of a stage only wave (q, h) reads: [9 positions][32 couts][4]
 static_assert(SSDE_W4_VPAD >= 16, "lanes 48-63 of the transform write the padding columns of V");
 constexpr int kMaxRaw = 2;                          // float4 halo items per thread per stage (halo <= 1024 pixels)
-constexpr int kLdm = 66;                            // row pitch of the product exchange [pos][16 tiles][64 couts]
-constexpr int kLdt = 68;                            // row pitch of the parked output tile [256 pixels][64 couts]
+static_assert(kThreads == kW4Threads && kNP == kW4Blocks, "wino4_epilogue");
 
-struct Wino4Params {
+struct Wino4Params : Wino4Shared {
   ssde_src src;
   const float* wpk;        // [ceil(C/4)][n_tiles][8 waves][9][32][4] (LDS image per stage, a wave's 4.5 KB contiguous)
-  int N, H, W, Cout;
-  int lTWt, lTHt;          // log2 tiles per patch row / column
-  int tiles_x, tiles_per_img, m_tiles, n_tiles;
-  const float* bias; const float* chan_add; int chan_add_ld;
-  const float* resid; int resid_post;
-  float scale;
-  float* dst;
-  float* gn_part;
-  int ksplit;              // 1, 2 or 4 workgroups per tile, each reducing its share of the channel stages (the kernel's kKs)
-  unsigned* sync;          // ksplit > 1: this launch's (shares started, shares handed over) pairs, one per tile, from
-                           // conv_mfma.hip's g_conv_sync (zero before and after)
-  int ticket_off;          // float index of the hand-over ticket in LDS (behind everything else)
   float* wino_v;           // kEmitV: V[pos][t][Ctot] = B^T pro(x) B for the F(4x4,3x3) weight gradient (ssde_conv_args.wino_v)
-  int T, tiles_h, tiles_w; // 4x4 tiles of the whole batch / per image column / per image row
 };
 
-// 1-D input transform (one column / row of B^T d, B^T rows: [4,0,-5,0,1,0] [0,-4,-4,1,1,0] [0,4,-4,-1,1,0]
-// [0,-2,-1,2,1,0] [0,2,-1,-2,1,0] [0,4,0,-5,0,1]), two channels at once
-__device__ __forceinline__ void bt6(const float2 (&d)[6], float2 (&o)[6]) {
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const float d0 = e ? d[0].y : d[0].x, d1 = e ? d[1].y : d[1].x, d2 = e ? d[2].y : d[2].x;
-    const float d3 = e ? d[3].y : d[3].x, d4 = e ? d[4].y : d[4].x, d5 = e ? d[5].y : d[5].x;
-    const float t1 = d4 - 4.f * d2, t2 = d3 - 4.f * d1, t3 = d4 - d2, t4 = d3 - d1;
-    const float o0 = 4.f * d0 - 5.f * d2 + d4, o1 = t1 + t2, o2 = t1 - t2, o3 = t3 + 2.f * t4, o4 = t3 - 2.f * t4;
-    const float o5 = 4.f * d1 - 5.f * d3 + d5;
-    if (e) { o[0].y = o0; o[1].y = o1; o[2].y = o2; o[3].y = o3; o[4].y = o4; o[5].y = o5; }
-    else   { o[0].x = o0; o[1].x = o1; o[2].x = o2; o[3].x = o3; o[4].x = o4; o[5].x = o5; }
+// What wino4_epilogue (wino4_common.h) asks of this kernel
+struct Wino4Epi : Wino4EpiNoTrace {
+  // wave (q, h) owns positions q + kPS j of cout half h
+  static __device__ __forceinline__ int position(int wave, int j) { return (wave >> 1) + kPS * j; }
+  static __device__ __forceinline__ int half(int wave, int) { return wave & 1; }
+  static __device__ __forceinline__ void barrier() { __syncthreads(); }
+  static __device__ __forceinline__ void lane_index(int tid, int& li, int& lh) { const int lane = tid & 63; li = lane & 31; lh = lane >> 5; }
+#ifdef SSDE_W4_TRACE
+  bool tr_on; int tr_base;
+  // slots 100-106 and 4 of round 0, 5 and the 100 MHz counter at the end
+  __device__ __forceinline__ void stamp(int phase, int rnd) const {
+    constexpr int kSlot[] = {100, 101, 102, 103, 104, 105, -1, -1, -1, 106, 4, 5};
+    if (rnd == 0 && kSlot[phase] >= 0) SSDE_TR(kSlot[phase]);
+    if (phase == kW4Done) SSDE_TRR(111);
   }
-}
-
-// the same, on packed f32 pairs (v_pk_*)
-__device__ __forceinline__ void bt6(const ssde_f32x2 (&d)[6], ssde_f32x2 (&o)[6]) {
-  const ssde_f32x2 t1 = d[4] - 4.f * d[2], t2 = d[3] - 4.f * d[1], t3 = d[4] - d[2], t4 = d[3] - d[1];
-  o[0] = 4.f * d[0] - 5.f * d[2] + d[4];
-  o[1] = t1 + t2;
-  o[2] = t1 - t2;
-  o[3] = t3 + 2.f * t4;
-  o[4] = t3 - 2.f * t4;
-  o[5] = 4.f * d[1] - 5.f * d[3] + d[5];
-}
+#endif
+};
 
 // kKs = 2 or 4: that many workgroups per tile, each reducing its share of the channel stages (own instantiations: the
 // hand-over costs the epilogue registers, and the unsplit kernel is the one the big layers run).  The shares are dealt in
@@ -208,10 +178,8 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   const int halo_px = IMGS * HH * HWd;
   const int raw_plane = 2 * halo_px;           // floats between the two channel-pair planes of a raw buffer
   const int raw_stride = 2 * raw_plane;        // floats per raw buffer
-  const int img0 = (mt / p.tiles_per_img) * IMGS;
-  const int trem = mt % p.tiles_per_img;
-  const int ty = trem / p.tiles_x, tx = trem % p.tiles_x;
-  const int n0 = nt * 64;
+  const Wino4TileMap tm(p, mt);
+  const int img0 = tm.img0, ty = tm.ty, tx = tm.tx;
 
   const ssde_src& s = p.src;
   const int Ctot = s.c0 + s.c1;
@@ -262,8 +230,8 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   const int t_tile = t_item >> 1, t_pair = t_item & 1;
   int t_base;
   {
-    const int il = t_tile >> (p.lTWt + p.lTHt);
-    const int tr = (t_tile >> p.lTWt) & (THt - 1), tc = t_tile & (TWt - 1);
+    int il, tr, tc;
+    tm.decode(t_tile, il, tr, tc);
     t_base = (il * HH + 4 * tr) * HWd + 4 * tc;
   }
   const int t_vcol = t_real ? t_tile * 4 + t_pair * 2 : kTiles * kKc + (lane & 7) * 2;
@@ -275,9 +243,8 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   uint32_t ev_off = 0xFFFFFFFFu;
   const uint32_t ev_lds = (uint32_t)(((tid >> 5) * kVP + (tid & 31) * 4) * 4);
   if constexpr (kEmitV) {
-    const int etile = tid & 31;
-    const int eil = etile >> (p.lTWt + p.lTHt);
-    const int etr = (etile >> p.lTWt) & (THt - 1), etc = etile & (TWt - 1);
+    int eil, etr, etc;
+    tm.decode(tid & 31, eil, etr, etc);
     const int eimg = img0 + eil, eyy = ty * THt + etr, exx = tx * TWt + etc;
     // layout [pos][Ctot / 4][t][4]: the 32 tiles of a workgroup are consecutive t for every map the networks have (a patch is
     // whole tile rows of one image, or whole images) -> one 512-byte run per position and stage.  (As [pos][t][Ctot], the
@@ -578,167 +545,14 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv_wino4_kernel(const 
   }
   SSDE_TR(3);
 
-  // ---- epilogue, 16 tiles (= accumulator rows r < 8, then r >= 8 of every wave) at a time ----
-  // The products of a round go to LDS as M[pos][tile 16][64 couts] (pitch kLdm), every thread applies A^T M A to one
-  // (tile, cout pair), parks the 4x4 outputs as [256 pixels][64 couts] and the shared epilogue stores them.  All waves
-  // take part in both rounds and each round retires half of a wave's accumulators, so nothing spills.  (Rounds over
-  // the two 32-cout halves instead kept 144 accumulators live through the transform of the other half: 81 scratch
-  // stores per lane and 105 k cycles of epilogue per workgroup, tools/wino4_trace.py.)
-  SsdeEpi e{p.bias, p.chan_add, p.chan_add_ld, p.resid, p.resid_post, p.scale, p.dst, p.Cout, p.gn_part};
-  // GroupNorm partials: one entry per (image, workgroup tile, round) when the tile is part of one image; per image when a
-  // round holds IMGS / 2 whole images (IMGS >= 2: 16 / (tiles per image) images per round)
-  const int gn_base = !p.gn_part ? -1 : (IMGS == 1 ? (img0 * p.tiles_per_img + trem) * 2 : img0);
-  const int rpi_log2 = IMGS > 2 ? 8 - (4 - p.lTWt - p.lTHt) : 30;             // rows per image in a round: 256 / (IMGS / 2)
-  const bool e_on = tid < kEpiThreads;                                       // waves 8-11 (if any) only hand over products
-  const int wh = wave & 1;
-  const int e_tl = e_on ? tid >> 5 : 0, e_cp = tid & 31;
-  float* park = smem;                                                         // [256][kLdt], aliases the products
-  // split reduction: share 0 leaves its raw 4x4 outputs in the tile's own part of dst, shares 1 .. kKs - 2 add theirs to
-  // them in turn, the last share adds its own and runs the epilogue.  sy[1] counts the shares that have handed over.
-#pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
-#pragma unroll
-    for (int j = 0; j < kNP; ++j)
-#pragma unroll
-      for (int r8 = 0; r8 < 8; ++r8) {
-        const int r = rnd * 8 + r8;
-        const int tl = (r & 3) + 4 * lh + 8 * ((r >> 2) & 1);
-        smem[((wq + kPS * j) * 16 + tl) * kLdm + wh * 32 + li] = acc[j][r];
-      }
-    if (rnd == 0) SSDE_TR(100);
-    __syncthreads();
-    if (rnd == 0) SSDE_TR(101);
-    // Y = A^T M A for (tile, couts 2 cp, 2 cp + 1); A^T rows [1,1,1,1,1,0] [0,1,-1,2,-2,0] [0,1,1,4,4,0] [0,1,-1,8,-8,1]
-    float2 y[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) y[a][b] = make_float2(0.f, 0.f);
-    const float* mp = smem + e_tl * kLdm + 2 * e_cp;
-#pragma unroll
-    for (int px = 0; px < 6; ++px) {
-      float2 m[6];
-#pragma unroll
-      for (int py = 0; py < 6; ++py) m[py] = *reinterpret_cast<const float2*>(mp + (py * 6 + px) * (16 * kLdm));
-      float2 t[4];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const float m0 = c ? m[0].y : m[0].x, m1 = c ? m[1].y : m[1].x, m2 = c ? m[2].y : m[2].x;
-        const float m3 = c ? m[3].y : m[3].x, m4 = c ? m[4].y : m[4].x, m5 = c ? m[5].y : m[5].x;
-        const float s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-        const float t0 = m0 + s1 + s2, t1 = d1 + 2.f * d2, t2 = s1 + 4.f * s2, t3 = d1 + 8.f * d2 + m5;
-        if (c) { t[0].y = t0; t[1].y = t1; t[2].y = t2; t[3].y = t3; }
-        else   { t[0].x = t0; t[1].x = t1; t[2].x = t2; t[3].x = t3; }
-      }
-      // column px of A: (1, 0, 0, 0), (1, 1, 1, 1), (1, -1, 1, -1), (1, 2, 4, 8), (1, -2, 4, -8), (0, 0, 0, 1)
-      constexpr float kA[6][4] = {{1.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}, {1.f, -1.f, 1.f, -1.f},
-                                  {1.f, 2.f, 4.f, 8.f}, {1.f, -2.f, 4.f, -8.f}, {0.f, 0.f, 0.f, 1.f}};
-#pragma unroll
-      for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 4; ++dx)
-          if (kA[px][dx] != 0.f) { y[dy][dx].x += kA[px][dx] * t[dy].x; y[dy][dx].y += kA[px][dx] * t[dy].y; }
-    }
-    if (rnd == 0) SSDE_TR(102);
-    __syncthreads();                           // every thread has read its products: the parked tile may overwrite them
-    if (rnd == 0) SSDE_TR(103);
-    if (e_on) {
-#pragma unroll
-      for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 4; ++dx)
-          *reinterpret_cast<float2*>(park + (e_tl * 16 + dy * 4 + dx) * kLdt + 2 * e_cp) = y[dy][dx];
-    }
-    if (rnd == 0) SSDE_TR(104);
-    __syncthreads();
-    if (rnd == 0) SSDE_TR(105);
-    const int gn_entry = gn_base < 0 ? -1 : (IMGS == 1 ? gn_base + rnd : gn_base + rnd * (IMGS >> 1));
-    auto pixfn = [&](int row, size_t& pix, int& img) {
-      const int tile = rnd * 16 + (row >> 4), dy = (row >> 2) & 3, dx = row & 3;
-      const int il = tile >> (p.lTWt + p.lTHt);
-      const int tr = (tile >> p.lTWt) & (THt - 1), tc = tile & (TWt - 1);
-      img = img0 + il;
-      const int oy = (ty * THt + tr) * 4 + dy, ox = (tx * TWt + tc) * 4 + dx;
-      if (img >= p.N || oy >= p.H || ox >= p.W) return false;
-      pix = ((size_t)img * p.H + oy) * p.W + ox;
-      return true;
-    };
-    const int gn_max = IMGS == 1 ? p.N * p.tiles_per_img * 2 : p.N;
-    if constexpr (kSplit) {
-      const bool first = ks == 0, last = ks == kKs - 1;
-      // The sums travel as agent-scope dword accesses, coherent at the device level by themselves (no __threadfence():
-      // that is a write-back of the whole L2 per workgroup, conv_mfma.hip)
-      if (!first && rnd == 0) {
-        if (tid == 0)
-          while (__hip_atomic_load(sy + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned)ks) __builtin_amdgcn_s_sleep(4);
-        __syncthreads();
-      }
-      // (4 float4 of a thread at a time: round 0 still holds half of the accumulators)
-      constexpr int kIters = 256 * 16 / kThreads, kBatch = 4;
-#pragma unroll
-      for (int ib = 0; ib < kIters; ib += kBatch) {
-        float* tp[kBatch];
-        float* dp[kBatch];
-#pragma unroll
-        for (int it = 0; it < kBatch; ++it) {
-          const int q = tid + (ib + it) * kThreads;
-          const int row = q >> 4, j = (q & 15) * 4;
-          size_t pix; int img;
-          const bool ok = pixfn(row, pix, img) && n0 + j < p.Cout;       // c_out % 4 == 0 on this path
-          tp[it] = park + row * kLdt + j;
-          dp[it] = ok ? p.dst + pix * p.Cout + n0 + j : nullptr;
-        }
-        float o[kBatch][4];
-        if (!first) {
-          // the batch's loads in flight before the first add
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              o[it][k] = dp[it] ? __hip_atomic_load(dp[it] + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[it][k] += tp[it][k];            // (sum so far) + own share
-        } else {
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[it][k] = tp[it][k];
-        }
-        if (last) {
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) tp[it][k] = o[it][k];
-        } else {
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it)
-            if (dp[it]) {
-#pragma unroll
-              for (int k = 0; k < 4; ++k) __hip_atomic_store(dp[it] + k, o[it][k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-      }
-      if (!last) {
-        if (rnd == 0) { __syncthreads(); continue; }                     // (park is refilled by round 1)
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0);      // every store of this thread is acknowledged ...
-        __syncthreads();                    // ... and every thread's
-        if (tid == 0) atomicAdd(sy + 1, 1u);
-        return;
-      }
-      __syncthreads();
-      if (rnd == 1 && tid == 0) { sy[0] = 0u; sy[1] = 0u; }              // ready for the next launch that is dealt these slots
-    }
-    // round 1 has no accumulators left: all 8 rows of a thread (residual loads) in flight instead of 4
-    if (rnd == 0) ssde_store_tile<256, 64, kEpiThreads, 4, 0>(park, kLdt, n0, e, pixfn, gn_entry, rpi_log2, gn_max);
-    else ssde_store_tile<256, 64, kEpiThreads, SSDE_W4_EPI_BATCH, 0>(park, kLdt, n0, e, pixfn, gn_entry, rpi_log2, gn_max);
-    if (rnd == 0) SSDE_TR(106);
-    if (rnd == 0) { __syncthreads(); SSDE_TR(4); }
-  }
-  SSDE_TR(5);
-  SSDE_TRR(111);
+  // ---- epilogue (wino4_common.h).  The 36 positions of an output live in 4 waves: the workgroup exchanges the products
+  // through LDS, 16 tiles at a time ----
+#ifdef SSDE_W4_TRACE
+  const Wino4Epi epi{{}, tr_on, tr_base};
+#else
+  const Wino4Epi epi{};
+#endif
+  wino4_epilogue<kKs>(acc, smem, p, tm, wave, nt, ks, sy, epi);
 }
 
 }  // namespace
@@ -759,35 +573,24 @@ namespace {
 // Everything a launch needs, without touching a device: the parameter block (but for the split of the reduction, which takes
 // hand-over slots), and the plan the queries report.
 int wino4_plan(const ssde_conv_args* a, Wino4Params* pp, ssde_conv_plan* pl) {
-  SSDE_REQUIRE(a && a->dst && a->main.p0 && a->w_main, "conv(winograd 4x4): null args");
-  SSDE_REQUIRE(a->ksize == 3 && a->stride == 1 && a->pad == 1, "conv(winograd 4x4): needs 3x3, stride 1, pad 1");
-  SSDE_REQUIRE(a->aux.p0 == nullptr, "conv(winograd 4x4): fused 1x1 source not supported (issue it as a second conv)");
-  SSDE_REQUIRE(a->h_in == a->h_out && a->w_in == a->w_out && a->h_out % 4 == 0 && a->w_out % 4 == 0 && a->h_out >= 8 && a->w_out >= 8,
-               "conv(winograd 4x4): same-size output, multiples of 4, at least 8x8 (got %dx%d)", a->h_out, a->w_out);
+  constexpr const char* kRoute = "conv(winograd 4x4)";
+  if (int rc = wino4_check_shape(a, kRoute, 8)) return rc;
   const ssde_src& s = a->main;
-  if (int rc = ssde_src_check(s, "conv(winograd 4x4)", "", 4, SSDE_SRC_ALL)) return rc;
+  if (int rc = ssde_src_check(s, kRoute, "", 4, SSDE_SRC_ALL)) return rc;
   // the halo loads address a source as scalar base + 32-bit byte offset
   SSDE_REQUIRE((unsigned long long)a->n * a->h_in * a->w_in * (unsigned)(s.c0 > s.c1 ? s.c0 : s.c1) * 4ull < (1ull << 32),
                "conv(winograd 4x4): a source of 4 GB or more is not addressable by this kernel");
   Wino4Params& p = *pp;
-  p.src = s; p.wpk = a->w_main;
-  p.N = a->n; p.H = a->h_out; p.W = a->w_out; p.Cout = a->c_out;
-  const ssde_wino_tiling t = ssde_wino_tiling_fill(p, a, 4, kTiles);
-  ssde_fill_epilogue(p, a);
-  p.wino_v = a->wino_v; p.tiles_h = a->h_out / 4; p.tiles_w = a->w_out / 4; p.T = a->n * p.tiles_h * p.tiles_w;
-  SSDE_REQUIRE(!a->wino_v || 36ull * (unsigned long long)p.T * (unsigned)(s.c0 + s.c1) * 4ull < (1ull << 32),
+  p.src = s; p.wpk = a->w_main; p.wino_v = a->wino_v;
+  SSDE_REQUIRE(!a->wino_v || 36ull * (unsigned long long)(a->n * (a->h_out / 4) * (a->w_out / 4)) * (unsigned)(s.c0 + s.c1) * 4ull < (1ull << 32),
                "conv(winograd 4x4): a transformed-input by-product of 4 GB or more is not addressable by this kernel");
-  // GroupNorm partials: a workgroup tile is part of one image (two epilogue rounds: 2 x tiles_per_img slices of 8 wave
-  // entries) or holds `imgs` >= 2 whole images (imgs / 2 per round; 512 / imgs rows per image >= the 32 rows of one
-  // epilogue trip)
-  SSDE_REQUIRE(!a->gn_part || t.gn_ok, "conv(winograd 4x4): GroupNorm partials not available for this tiling");
-  pl->gn_slices = t.gn_ok ? (t.imgs == 1 ? 2 * p.tiles_per_img : 1) * (kEpiThreads / 64) : 0;
+  ssde_wino_tiling t;
+  if (int rc = wino4_fill_shared(p, a, kRoute, &t, &pl->gn_slices)) return rc;
   const int halo_px = t.imgs * (4 * t.tht + 2) * (4 * t.twt + 2);
   SSDE_REQUIRE(halo_px <= kMaxRaw * kThreads, "conv(winograd 4x4): halo of %d pixels exceeds the staging plan", halo_px);
   int lds = (2 * kVFloats + 2 * kUFloats + 2 * 2 * 2 * halo_px) * 4;
   if (s.pro_mode == SSDE_PRO_GN || s.pro_mode == SSDE_PRO_GN_SILU) lds += (((2 * t.imgs * s.gn_groups + 3) & ~3) + 2 * (s.c0 + s.c1)) * 4;
-  const int lds_epi = kPos * 16 * kLdm * 4;
-  if (lds < lds_epi) lds = lds_epi;
+  if (lds < kW4EpiLds) lds = kW4EpiLds;
   p.ticket_off = lds / 4;
   lds += 16;
   SSDE_REQUIRE(lds <= 160 * 1024, "conv(winograd 4x4): %d bytes of LDS", lds);
@@ -796,15 +599,11 @@ int wino4_plan(const ssde_conv_args* a, Wino4Params* pp, ssde_conv_plan* pl) {
   return SSDE_OK;
 }
 
-// the instantiation of a launch: GroupNorm prologue, shares of the reduction, V written as a by-product
+// the instantiation of a launch: GroupNorm prologue, V written as a by-product; wino4_launch_split: the shares of the reduction
 template <bool kGn, bool kV>
-int wino4_launch_as(const Wino4Params& p, dim3 grid, int lds, hipStream_t st) {
-  constexpr const char* kRoute = "conv(winograd 4x4)";
-  switch (p.ksplit) {
-    case 4: return ssde_launch_lds<conv_wino4_kernel<kGn, 4, kV>>(kRoute, grid, dim3(kThreads), lds, st, p);
-    case 2: return ssde_launch_lds<conv_wino4_kernel<kGn, 2, kV>>(kRoute, grid, dim3(kThreads), lds, st, p);
-    default: return ssde_launch_lds<conv_wino4_kernel<kGn, 1, kV>>(kRoute, grid, dim3(kThreads), lds, st, p);
-  }
+int wino4_launch_as(const Wino4Params& p, int wgs, int lds, hipStream_t st) {
+  return wino4_launch_split<conv_wino4_kernel<kGn, 1, kV>, conv_wino4_kernel<kGn, 2, kV>, conv_wino4_kernel<kGn, 4, kV>>(
+      "conv(winograd 4x4)", p, wgs, lds, st);
 }
 
 }  // namespace
@@ -819,13 +618,7 @@ int ssde_conv_wino4_launch(const ssde_conv_args* a, hipStream_t st) {
   Wino4Params p;
   ssde_conv_plan pl;
   if (int rc = wino4_plan(a, &p, &pl)) return rc;
-  // Split the reduction when the launch would leave half of the CUs or more without a workgroup (8x8 maps at batch 256:
-  // 128 tiles of 8 images x 64 couts)
-  const int wgs = ssde_cdiv(p.m_tiles, 8) * 8 * p.n_tiles;
-  p.ksplit = a->resid != a->dst ? ssde_conv_wino4_splits(wgs, p.src.c0 + p.src.c1, a->c_out, a->flags) : 1;
-  p.sync = p.ksplit > 1 ? ssde_conv_sync_slots(p.m_tiles * p.n_tiles) : nullptr;
-  if (!p.sync) p.ksplit = 1;
-  const dim3 grid(wgs * p.ksplit);
+  const int grid = wino4_split_setup(p, a, ssde_conv_wino4_splits);
   const bool gn = p.src.pro_mode == SSDE_PRO_GN || p.src.pro_mode == SSDE_PRO_GN_SILU;
   if (a->wino_v) return gn ? wino4_launch_as<true, true>(p, grid, pl.lds_bytes, st) : wino4_launch_as<false, true>(p, grid, pl.lds_bytes, st);
   return gn ? wino4_launch_as<true, false>(p, grid, pl.lds_bytes, st) : wino4_launch_as<false, false>(p, grid, pl.lds_bytes, st);

@@ -22,12 +22,10 @@
 // The output pass: one wave = one tile x 64 couts.  It sums the slabs of the tile in a fixed order (deterministic, no
 // atomics), applies A^T M A, parks the 4x4 outputs in LDS and ends in ssde_store_tile (bias, chan_add, residual, out_scale,
 // GroupNorm partials: one slice per tile, i.e. per image on the 4x4 maps).
-#include "ssde_common.h"
+#include "wino4_common.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kGemmWaves = 4;                 // waves of a GEMM workgroup (independent blocks: no LDS, no barrier)
 constexpr int kBM = 64, kBN = 64;             // tiles x couts of one wave
@@ -152,24 +150,16 @@ __global__ __launch_bounds__(64) void wino4p_out_kernel(const Wino4pOutParams p)
 #pragma unroll
     for (int pos = 0; pos < 36; ++pos) mm[pos] += mp[k * slab + pos * plane];
   }
-  // Y = A^T M A with M[a][b] = mm[6 a + b] (a: row of the 6x6 tile); over the rows of every column first, as conv_wino4r.hip
+  // Y = A^T M A with M[a][b] = mm[6 a + b] (a: row of the 6x6 tile); over the rows of every column first (wino4_common.h)
   float y[4][4];
 #pragma unroll
   for (int dy = 0; dy < 4; ++dy)
 #pragma unroll
     for (int dx = 0; dx < 4; ++dx) y[dy][dx] = 0.f;
-  constexpr float kA[6][4] = {{1.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}, {1.f, -1.f, 1.f, -1.f},
-                              {1.f, 2.f, 4.f, 8.f}, {1.f, -2.f, 4.f, -8.f}, {0.f, 0.f, 0.f, 1.f}};
 #pragma unroll
   for (int px = 0; px < 6; ++px) {
-    const float m0 = mm[px], m1 = mm[6 + px], m2 = mm[12 + px], m3 = mm[18 + px], m4 = mm[24 + px], m5 = mm[30 + px];
-    const float s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-    const float tt[4] = {m0 + s1 + s2, d1 + 2.f * d2, s1 + 4.f * s2, d1 + 8.f * d2 + m5};
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx)
-        if (kA[px][dx] != 0.f) y[dy][dx] += kA[px][dx] * tt[dy];
+    const float m[6] = {mm[px], mm[6 + px], mm[12 + px], mm[18 + px], mm[24 + px], mm[30 + px]};
+    wino4_out_column(px, m, y);
   }
 #pragma unroll
   for (int dy = 0; dy < 4; ++dy)
@@ -217,13 +207,10 @@ int w4p_splits(int waves1, int Q, unsigned flags) {
 
 // the shape of a launch and the plan the queries report, without touching a device
 int w4p_shape(const ssde_conv_args* a, W4pShape* s, ssde_conv_plan* pl) {
-  SSDE_REQUIRE(a && a->main.p0 && a->w_main && a->dst, "conv(winograd 4x4, position-batched): null args");
-  SSDE_REQUIRE(a->ksize == 3 && a->stride == 1 && a->pad == 1, "conv(winograd 4x4, position-batched): needs 3x3, stride 1, pad 1");
-  SSDE_REQUIRE(a->aux.p0 == nullptr, "conv(winograd 4x4, position-batched): fused 1x1 source not supported (issue it as a second conv)");
-  SSDE_REQUIRE(a->n > 0 && a->h_in == a->h_out && a->w_in == a->w_out && a->h_out % 4 == 0 && a->w_out % 4 == 0 && a->h_out > 0 && a->w_out > 0,
-               "conv(winograd 4x4, position-batched): same-size output, multiples of 4 (got %dx%d)", a->h_out, a->w_out);
+  constexpr const char* kRoute = "conv(winograd 4x4, position-batched)";
+  if (int rc = wino4_check_shape(a, kRoute, 0)) return rc;        // (maps below 8x8 are this route's)
   const ssde_src& src = a->main;
-  if (int rc = ssde_src_check(src, "conv(winograd 4x4, position-batched)", "", 4, SSDE_SRC_NEEDS_C0)) return rc;   // (the prologue: wino4_xform.hip)
+  if (int rc = ssde_src_check(src, kRoute, "", 4, SSDE_SRC_NEEDS_C0)) return rc;   // (the prologue: wino4_xform.hip)
   const int ctot = src.c0 + src.c1;
   SSDE_REQUIRE(ctot % (8 * kKC) == 0, "conv(winograd 4x4, position-batched): input channels must be a multiple of %d (got %d)", 8 * kKC, ctot);
   SSDE_REQUIRE(a->c_out > 0 && a->c_out % 4 == 0, "conv(winograd 4x4, position-batched): output channels must be a multiple of 4");

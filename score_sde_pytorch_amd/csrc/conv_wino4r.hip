@@ -25,12 +25,9 @@
 // that consumed it in stage st (two register sets), so every load has two whole stages to land, ~18 loads are in flight per wave
 // at any time, and the only synchronisation is the wave's own counted s_waitcnt vmcnt (five per stage).  Waves drift freely: a
 // late V piece stalls one wave while its SIMD sibling keeps the matrix pipe busy.  LDS is used by the epilogue only
-// (conv_wino4.hip's: products -> LDS, A^T M A, parked tile, shared coalesced store with GroupNorm partials).
-#include "ssde_common.h"
-#include <atomic>
+// (wino4_common.h's wino4_epilogue: products -> LDS, A^T M A, parked tile, shared coalesced store with GroupNorm partials).
+#include "wino4_common.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // -DSSDE_W4R_TRACE (a variant library only): s_memtime stamps of waves 0 and 7 of the first workgroup
 #ifdef SSDE_W4R_TRACE
@@ -50,37 +47,44 @@ namespace {
 
 constexpr int kNP = 9;                              // accumulator blocks per wave: (4 positions) x (2 cout halves) + 1
 constexpr int kNV = 5;                              // positions a wave loads V for
-constexpr int kPos = 36, kTiles = 32;
 constexpr int kURegion = kNP * 32 * 4;              // floats of a stage's weight image only wave (q, h) reads (4.5 KB)
 constexpr int kUFloats = 8 * kURegion;              // one (stage, 64-cout tile) of the image
 // 8 waves, 32 tiles x 64 couts, one workgroup per CU (conv_wino4.hip's shape).  A 4-wave form with two workgroups per CU, the
 // second one started half a tile late so that one's epilogue would run under the other's MFMAs, was built and measured level:
 // the epilogue is VALU / issue work and fp32 MFMAs share the VALU datapath (tools/experiments/conv_wino4r_two_workgroups_per_cu/)
 constexpr int kWaves = 8, kThreads = 64 * kWaves, kBN = 64;
-constexpr int kLdm = kBN + 2, kLdt = kBN + 4;       // pitches of the product exchange and of the parked output tile
-constexpr int kLds = kPos * 16 * kLdm * 4;          // the epilogue's product exchange (the parked tile fits inside)
-static_assert(256 * kLdt <= kPos * 16 * kLdm, "parked tile");
+constexpr int kLds = kW4EpiLds;                     // the epilogue's product exchange (the parked tile fits inside)
+static_assert(kThreads == kW4Threads && kNP == kW4Blocks && kBN == 64, "wino4_epilogue");
 
-struct Wino4rParams {
+struct Wino4rParams : Wino4Shared {
   const float* v;          // [36][Ctot / 4][T][4]
   const float* wpk;        // SSDE_PACK_WINO4R: [Ctot / 4][n_tiles][8 waves][4 positions x [64 lanes][4] | [64 lanes][2]]
-  int N, H, W, Cout, Ctot;
-  int lTWt, lTHt;
-  int tiles_x, tiles_per_img, m_tiles, n_tiles;
-  const float* bias; const float* chan_add; int chan_add_ld;
-  const float* resid; int resid_post;
-  float scale;
-  float* dst;
-  float* gn_part;
-  int T, tiles_h, tiles_w;
-  int ksplit;              // 1, 2 or 4 workgroups per tile, each reducing its share of the channel stages (the kernel's kKs)
-  unsigned* sync;          // ksplit > 1: this launch's (shares started, shares handed over) pairs, one per tile (conv_mfma.hip's
-                           // g_conv_sync: zero before and after)
-  int ticket_off;          // float index of the hand-over ticket in LDS (behind the epilogue's exchange area)
+  int Ctot;
 };
 
-// kKs = 2 or 4: that many workgroups per tile, each reducing its share of the channel stages (conv_wino4.hip's split, the same
-// protocol: shares are dealt in the order the workgroups START -- an atomic counter per tile -- so share k only ever waits for
+// What wino4_epilogue (wino4_common.h) asks of this kernel
+struct Wino4rEpi : Wino4EpiNoTrace {
+  // wave w: positions 4 w + i (i = 0..3), both cout halves -> blocks 2 i, 2 i + 1; position 32 + (w >> 1), cout half w & 1 -> block 8
+  static __device__ __forceinline__ int position(int wave, int j) { return j < 8 ? 4 * wave + (j >> 1) : 32 + (wave >> 1); }
+  static __device__ __forceinline__ int half(int wave, int j) { return j < 8 ? (j & 1) : (wave & 1); }
+  // LDS-only barriers throughout: a __syncthreads() would wait out the previous round's global stores
+  static __device__ __forceinline__ void barrier() { SSDE_LDS_BARRIER(); }
+  // li / lh derived from tid rather than lane: the same values, but from lane hipcc keeps them live across the matrix loop --
+  // 240 VGPRs instead of 210
+  static __device__ __forceinline__ void lane_index(int tid, int& li, int& lh) { li = tid & 31; lh = (tid >> 5) & 1; }
+#ifdef SSDE_W4R_TRACE
+  bool tr_on; int tr_base;
+  // slots 32 + 4 rnd .. (products written, there, transformed, parked), 40 / 42 / 44 + rnd (split), 4 and 5
+  __device__ __forceinline__ void stamp(int phase, int rnd) const {
+    constexpr int kSlot[] = {32, 33, 34, -1, -1, 35, 40, 42, 44, -1, 4, 5};
+    constexpr int kPerRound[] = {4, 4, 4, 0, 0, 4, 1, 1, 1, 0, 0, 0};
+    if (kSlot[phase] >= 0) SSDE_RT(kSlot[phase] + kPerRound[phase] * rnd);
+  }
+#endif
+};
+
+// kKs = 2 or 4: that many workgroups per tile, each reducing its share of the channel stages (conv_wino4.hip's split, the hand-over
+// is wino4_common.h's: shares are dealt in the order the workgroups START -- an atomic counter per tile -- so share k only ever waits for
 // shares < k, which are resident or done; the sums are formed in the fixed order ((s0 + s1) + s2) + s3).  The maps this is for
 // are the 8x8 ones at batch 256: 1024 tiles = 32 workgroup tiles x 4 cout tiles = 128 workgroups on 256 CUs; two shares each
 // cover the chip with one workgroup per CU, and the matrix loop of a share is half as long.  (Eight shares on the 4x4 maps -- one
@@ -98,7 +102,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino4r_kernel(const Wino4rPa
   // wave w: positions 4 w + i (i = 0..3), both cout halves -> blocks 2 i, 2 i + 1; position 32 + (w >> 1), cout half w & 1 -> block 8
   auto pos_of = [&](int i) { return i < 4 ? 4 * wave + i : 32 + (wave >> 1); };
   const int TWt = 1 << p.lTWt, THt = 1 << p.lTHt;
-  const int IMGS = kTiles >> (p.lTWt + p.lTHt);
   // ---- operand addresses of a tile.  A: the lane's byte offset of position slot j inside one stage's [36][Q][T][4] view of V
   // (32-bit: the launcher checks V < 4 GB); the stage rides in the scalar base.  Tiles outside the batch / the image read tile 0's
   // run (a valid address; their outputs are never stored).  B: the wave's 4.5 KB of a stage, lane-major; four 1 KB pieces at
@@ -136,10 +139,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino4r_kernel(const Wino4rPa
   SSDE_RT(0);
   if (mt >= p.m_tiles) return;                   // (the grid is padded to whole groups of 8 pixel tiles)
 
-  const int img0 = (mt / p.tiles_per_img) * IMGS;
-  const int trem = mt % p.tiles_per_img;
-  const int ty = trem / p.tiles_x, tx = trem % p.tiles_x;
-  const int n0 = nt * kBN;
+  const Wino4TileMap tm(p, mt);
+  const int img0 = tm.img0, ty = tm.ty, tx = tm.tx;
   // this workgroup's share of the reduction: stages st_off .. st_off + nst (an even count: the launcher splits only channel
   // counts that are multiples of 8 kKs)
   int nst = p.Ctot >> 2, ks = 0, st_off = 0;
@@ -155,8 +156,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino4r_kernel(const Wino4rPa
   }
   // (a lambda rather than a plain block: as a block, hipcc arranges this address arithmetic differently)
   auto operands = [&]() {
-    const int il = li >> (p.lTWt + p.lTHt);
-    const int tr = (li >> p.lTWt) & (THt - 1), tc = li & (TWt - 1);
+    int il, tr, tc;
+    tm.decode(li, il, tr, tc);
     const int img = img0 + il, yy = ty * THt + tr, xx = tx * TWt + tc;
     const uint32_t t = (img < p.N && yy < p.tiles_h && xx < p.tiles_w) ? (uint32_t)((img * p.tiles_h + yy) * p.tiles_w + xx) : 0u;
     const uint32_t QT = (uint32_t)(p.Ctot >> 2) * (uint32_t)p.T;
@@ -236,152 +237,13 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wino4r_kernel(const Wino4rPa
 #undef SSDE_W4R_LOADV
   SSDE_RT(3);
 
-  // ---- epilogue (conv_wino4.hip): 16 tiles (accumulator rows r < 8, then r >= 8 of every wave) at a time: products -> LDS
-  // M[pos][16 tiles][64 couts], A^T M A per (tile, cout pair), parked 4x4 outputs, shared coalesced store ----
-  SsdeEpi e{p.bias, p.chan_add, p.chan_add_ld, p.resid, p.resid_post, p.scale, p.dst, p.Cout, p.gn_part};
-  const int gn_base = !p.gn_part ? -1 : (IMGS == 1 ? (img0 * p.tiles_per_img + trem) * 2 : img0);
-  const int rpi_log2 = IMGS > 2 ? 8 - (4 - p.lTWt - p.lTHt) : 30;
-  // (li / lh again, derived from tid rather than lane: the same values, but from lane hipcc keeps them live across the matrix
-  //  loop -- 240 VGPRs instead of 210)
-  const int li_e = tid & 31, lh_e = (tid >> 5) & 1;
-  const int e_tl = tid / (kBN / 2), e_cp = tid % (kBN / 2);
-  float* park = smem;
-#pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
-    auto pixfn = [&](int row, size_t& pix, int& img) {
-      const int tile = rnd * 16 + (row >> 4), dy = (row >> 2) & 3, dx = row & 3;
-      const int il = tile >> (p.lTWt + p.lTHt);
-      const int tr = (tile >> p.lTWt) & (THt - 1), tc = tile & (TWt - 1);
-      img = img0 + il;
-      const int oy = (ty * THt + tr) * 4 + dy, ox = (tx * TWt + tc) * 4 + dx;
-      if (img >= p.N || oy >= p.H || ox >= p.W) return false;
-      pix = ((size_t)img * p.H + oy) * p.W + ox;
-      return true;
-    };
-#pragma unroll
-    for (int j = 0; j < kNP; ++j)
-#pragma unroll
-      for (int r8 = 0; r8 < 8; ++r8) {
-        const int r = rnd * 8 + r8;
-        const int tl = (r & 3) + 4 * lh_e + 8 * ((r >> 2) & 1);
-        const int pos = pos_of(j >> 1), half = j < 8 ? (j & 1) : (wave & 1);      // block j of this wave
-        smem[(pos * 16 + tl) * kLdm + half * 32 + li_e] = acc[j][r];
-      }
-    SSDE_RT(32 + rnd * 4);   // products written (before the barrier)
-    SSDE_LDS_BARRIER();      // (LDS-only barriers throughout: a __syncthreads() would wait out the previous round's global stores)
-    SSDE_RT(33 + rnd * 4);
-    float2 y[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) y[a][b] = make_float2(0.f, 0.f);
-    const float* mp = smem + e_tl * kLdm + 2 * e_cp;
-#pragma unroll
-    for (int px = 0; px < 6; ++px) {
-      float2 m[6];
-#pragma unroll
-      for (int py = 0; py < 6; ++py) m[py] = *reinterpret_cast<const float2*>(mp + (py * 6 + px) * (16 * kLdm));
-      float2 t[4];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const float m0 = c ? m[0].y : m[0].x, m1 = c ? m[1].y : m[1].x, m2 = c ? m[2].y : m[2].x;
-        const float m3 = c ? m[3].y : m[3].x, m4 = c ? m[4].y : m[4].x, m5 = c ? m[5].y : m[5].x;
-        const float s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-        const float t0 = m0 + s1 + s2, t1 = d1 + 2.f * d2, t2 = s1 + 4.f * s2, t3 = d1 + 8.f * d2 + m5;
-        if (c) { t[0].y = t0; t[1].y = t1; t[2].y = t2; t[3].y = t3; }
-        else   { t[0].x = t0; t[1].x = t1; t[2].x = t2; t[3].x = t3; }
-      }
-      constexpr float kA[6][4] = {{1.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}, {1.f, -1.f, 1.f, -1.f},
-                                  {1.f, 2.f, 4.f, 8.f}, {1.f, -2.f, 4.f, -8.f}, {0.f, 0.f, 0.f, 1.f}};
-#pragma unroll
-      for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 4; ++dx)
-          if (kA[px][dx] != 0.f) { y[dy][dx].x += kA[px][dx] * t[dy].x; y[dy][dx].y += kA[px][dx] * t[dy].y; }
-    }
-    SSDE_RT(34 + rnd * 4);                     // output transform done
-    SSDE_LDS_BARRIER();                        // every thread has read its products: the parked tile may overwrite them
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx)
-        *reinterpret_cast<float2*>(park + (e_tl * 16 + dy * 4 + dx) * kLdt + 2 * e_cp) = y[dy][dx];
-    SSDE_LDS_BARRIER();
-    SSDE_RT(35 + rnd * 4);                     // tile parked: the store phase starts
-    const int gn_entry = gn_base < 0 ? -1 : (IMGS == 1 ? gn_base + rnd : gn_base + rnd * (IMGS >> 1));
-    const int gn_max = IMGS == 1 ? p.N * p.tiles_per_img * 2 : p.N;
-    if constexpr (kSplit) {
-      // split reduction (conv_wino4.hip's hand-over): share 0 leaves its raw 4x4 outputs in the tile's own part of dst, shares
-      // 1 .. kKs - 2 add theirs to them in turn, the last share adds its own and runs the epilogue, round by round.  The sums
-      // travel as agent-scope 16-byte accesses, coherent at the device level by themselves (no __threadfence(): that is a
-      // write-back of the whole L2 per workgroup, conv_mfma.hip)
-      const bool first = ks == 0, last = ks == kKs - 1;
-      // (sy[1]: the shares that have handed over round 0 in its low half, round 1 in its high half -- share k starts adding to
-      //  round 0 while share k - 1 is still busy with its round 1)
-      if (!first) {
-        if (tid == 0)
-          while (((__hip_atomic_load(sy + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (16 * rnd)) & 0xffffu) != (unsigned)ks)
-            __builtin_amdgcn_s_sleep(4);
-        __syncthreads();
-      }
-      SSDE_RT(40 + rnd);                     // (split) the previous share's round is there
-      constexpr int kIters = 256 * 16 / kThreads, kBatch = 4;      // (4 float4 of a thread at a time: round 0 still holds half of the accumulators)
-      static_assert(kBatch == 4, "SSDE_WAIT_VMCNT_FOR4");
-#pragma unroll
-      for (int ib = 0; ib < kIters; ib += kBatch) {
-        float* tp[kBatch];
-        float* dp[kBatch];
-#pragma unroll
-        for (int it = 0; it < kBatch; ++it) {
-          const int q = tid + (ib + it) * kThreads;
-          const int row = q >> 4, j = (q & 15) * 4;
-          size_t pix; int img;
-          const bool ok = pixfn(row, pix, img) && n0 + j < p.Cout;       // c_out % 4 == 0 on this path
-          tp[it] = park + row * kLdt + j;
-          dp[it] = ok ? p.dst + pix * p.Cout + n0 + j : nullptr;
-        }
-        // (16 bytes per access at agent scope: as dword atomics -- conv_wino4.hip's form -- the hand-over was 64 loads and 64
-        //  stores per thread and share)
-        ssde_f32x4 o[kBatch];
-        if (!first) {
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it) SSDE_GLOAD16_AGENT(o[it], dp[it] ? dp[it] : p.dst);     // the batch's loads in flight before the first add
-          SSDE_WAIT_VMCNT_FOR4(0, o[0], o[1], o[2], o[3]);
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it) o[it] += *reinterpret_cast<const ssde_f32x4*>(tp[it]);   // (sum so far) + own share
-        } else {
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it) o[it] = *reinterpret_cast<const ssde_f32x4*>(tp[it]);
-        }
-        if (last) {
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it) *reinterpret_cast<ssde_f32x4*>(tp[it]) = o[it];
-        } else {
-#pragma unroll
-          for (int it = 0; it < kBatch; ++it)
-            if (dp[it]) SSDE_GSTORE16_AGENT(dp[it], o[it]);
-        }
-      }
-      SSDE_RT(42 + rnd);                     // (split) sums formed: handed on, or parked for the epilogue
-      if (!last) {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0);      // every store of this thread is acknowledged ...
-        __syncthreads();                    // ... and every thread's (and park may be refilled by round 1)
-        if (tid == 0) atomicAdd(sy + 1, rnd == 0 ? 1u : 0x10000u);
-        SSDE_RT(44 + rnd);                   // (split) stores acknowledged, round signalled
-        if (rnd == 0) continue;
-        return;
-      }
-      __syncthreads();
-      if (rnd == 1 && tid == 0) { sy[0] = 0u; sy[1] = 0u; }              // ready for the next launch that is dealt these slots
-    }
-    // (Fetching the residual rows ahead of the exchange / transform / park phases was built twice and measured neutral:
-    //  profiles/r6_w4r_epilogue_prefetch_v1_in_scratch_rejected.txt, r6_w4r_epilogue_prefetch_v2_neutral.txt)
-    if (rnd == 0) ssde_store_tile<256, kBN, kThreads, 4, 0>(park, kLdt, n0, e, pixfn, gn_entry, rpi_log2, gn_max);
-    else ssde_store_tile<256, kBN, kThreads, 8, 0>(park, kLdt, n0, e, pixfn, gn_entry, rpi_log2, gn_max);
-    if (rnd == 0) { SSDE_LDS_BARRIER(); SSDE_RT(4); }
-  }
-  SSDE_RT(5);
+  // ---- epilogue (wino4_common.h): products -> LDS, A^T M A per (tile, cout pair), parked 4x4 outputs, shared coalesced store ----
+#ifdef SSDE_W4R_TRACE
+  const Wino4rEpi epi{{}, tr_on, tr_base};
+#else
+  const Wino4rEpi epi{};
+#endif
+  wino4_epilogue<kKs>(acc, smem, p, tm, wave, nt, ks, sy, epi);
 }
 
 }  // namespace
@@ -406,23 +268,15 @@ namespace {
 // Everything a launch needs, without touching a device: the parameter block (but for the split of the reduction, which takes
 // hand-over slots), and the plan the queries report.  The source's prologue is the transform pass's business (wino4_xform.hip).
 int wino4r_plan(const ssde_conv_args* a, Wino4rParams* pp, ssde_conv_plan* pl) {
-  SSDE_REQUIRE(a && a->dst && a->main.p0 && a->w_main, "conv(winograd 4x4, register-fed): null args");
-  SSDE_REQUIRE(a->ksize == 3 && a->stride == 1 && a->pad == 1, "conv(winograd 4x4, register-fed): needs 3x3, stride 1, pad 1");
-  SSDE_REQUIRE(a->aux.p0 == nullptr, "conv(winograd 4x4, register-fed): fused 1x1 source not supported (issue it as a second conv)");
-  SSDE_REQUIRE(a->h_in == a->h_out && a->w_in == a->w_out && a->h_out % 4 == 0 && a->w_out % 4 == 0 && a->h_out >= 8 && a->w_out >= 8,
-               "conv(winograd 4x4, register-fed): same-size output, multiples of 4, at least 8x8 (got %dx%d)", a->h_out, a->w_out);
+  constexpr const char* kRoute = "conv(winograd 4x4, register-fed)";
+  if (int rc = wino4_check_shape(a, kRoute, 8)) return rc;
   const ssde_src& s = a->main;
-  if (int rc = ssde_src_check(s, "conv(winograd 4x4, register-fed)", "", 4, SSDE_SRC_NEEDS_C0)) return rc;
+  if (int rc = ssde_src_check(s, kRoute, "", 4, SSDE_SRC_NEEDS_C0)) return rc;
   SSDE_REQUIRE((s.c0 + s.c1) % 8 == 0, "conv(winograd 4x4, register-fed): input channels must be a multiple of 8 (the stage loop runs in pairs)");
   Wino4rParams& p = *pp;
-  p.v = a->wino_v; p.wpk = a->w_main;
-  p.N = a->n; p.H = a->h_out; p.W = a->w_out; p.Cout = a->c_out; p.Ctot = s.c0 + s.c1;
-  static_assert(kBN == 64, "ssde_wino_tiling_fill: 64 output channels per workgroup");
-  const ssde_wino_tiling t = ssde_wino_tiling_fill(p, a, 4, kTiles);
-  ssde_fill_epilogue(p, a);
-  p.tiles_h = a->h_out / 4; p.tiles_w = a->w_out / 4; p.T = a->n * p.tiles_h * p.tiles_w;
-  SSDE_REQUIRE(!a->gn_part || t.gn_ok, "conv(winograd 4x4, register-fed): GroupNorm partials not available for this tiling");
-  pl->gn_slices = t.gn_ok ? (t.imgs == 1 ? 2 * p.tiles_per_img : 1) * (kThreads / 64) : 0;
+  p.v = a->wino_v; p.wpk = a->w_main; p.Ctot = s.c0 + s.c1;
+  ssde_wino_tiling t;
+  if (int rc = wino4_fill_shared(p, a, kRoute, &t, &pl->gn_slices)) return rc;
   p.ticket_off = kLds / 4;
   pl->lds_bytes = kLds + 16;
   static_assert(kLds + 16 <= 160 * 1024, "LDS of a CU");
@@ -446,17 +300,7 @@ int ssde_conv_wino4r_launch(const ssde_conv_args* a, hipStream_t st) {
   SSDE_REQUIRE(a->wino_v, "conv(winograd 4x4, register-fed): the transformed-input buffer (ssde_conv_args.wino_v) is missing");
   SSDE_REQUIRE(36ull * (unsigned long long)p.T * (unsigned)p.Ctot * 4ull < (1ull << 32),
                "conv(winograd 4x4, register-fed): a transformed input of 4 GB or more is not addressable by this kernel");
-  // Split the reduction when the launch would leave half of the CUs or more without a workgroup (8x8 maps at batch 256: 128
-  // tiles of 8 images x 64 couts): ssde_conv_wino4r_splits, the rule engine.Lowering.conv3_route mirrors.  (dst is the hand-over
-  // buffer: not when the residual aliases it)
-  const int wgs = ssde_cdiv(p.m_tiles, 8) * 8 * p.n_tiles;
-  p.ksplit = a->resid != a->dst ? ssde_conv_wino4r_splits(wgs, p.Ctot, a->c_out, a->flags) : 1;
-  p.sync = p.ksplit > 1 ? ssde_conv_sync_slots(p.m_tiles * p.n_tiles) : nullptr;
-  if (!p.sync) p.ksplit = 1;
-  const dim3 grid(wgs * p.ksplit);
-  switch (p.ksplit) {
-    case 4: return ssde_launch_lds<conv_wino4r_kernel<4>>(kRoute, grid, dim3(kThreads), pl.lds_bytes, st, p);
-    case 2: return ssde_launch_lds<conv_wino4r_kernel<2>>(kRoute, grid, dim3(kThreads), pl.lds_bytes, st, p);
-    default: return ssde_launch_lds<conv_wino4r_kernel<1>>(kRoute, grid, dim3(kThreads), pl.lds_bytes, st, p);
-  }
+  // the shares of the reduction: ssde_conv_wino4r_splits, the rule engine.Lowering.conv3_route mirrors
+  const int grid = wino4_split_setup(p, a, ssde_conv_wino4r_splits);
+  return wino4_launch_split<conv_wino4r_kernel<1>, conv_wino4r_kernel<2>, conv_wino4r_kernel<4>>(kRoute, p, grid, pl.lds_bytes, st);
 }

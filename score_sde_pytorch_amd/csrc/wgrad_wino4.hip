@@ -34,10 +34,8 @@
 //                                                            over workgroups into slabs
 //   wgrad4_sum_splits_kernel, wgrad4_reduce_kernel    dw += scale G^T (sum_splits dU) G  fixed order (deterministic)
 // The transformed operands live in the launch's scratch (2.25 x (input + output gradient) of the layer).
-#include "ssde_common.h"
+#include "wino4_common.h"
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // -DSSDE_WG4_TRACE (tools/wgrad4_trace.py, a variant library only): s_memtime stamps of wave 0 of the first GEMM workgroup
 #ifdef SSDE_WG4_TRACE
@@ -81,26 +79,7 @@ struct W4Params {
 // stores in flight per thread.  VEC = 2 (8-byte accesses, 112-126 registers, four waves per SIMD) is 3-7 % faster per layer
 // than VEC = 1; four channels per thread (16-byte accesses, 256 registers, two waves per SIMD) measured 5-12 % SLOWER end to
 // end: profiles/r3_wgrad_wino4_ab.txt. ----
-// B^T rows [4,0,-5,0,1,0] [0,-4,-4,1,1,0] [0,4,-4,-1,1,0] [0,-2,-1,2,1,0] [0,2,-1,-2,1,0] [0,4,0,-5,0,1]
-__device__ __forceinline__ void bt6(const float (&d)[6], float (&o)[6]) {
-  const float t1 = d[4] - 4.f * d[2], t2 = d[3] - 4.f * d[1], t3 = d[4] - d[2], t4 = d[3] - d[1];
-  o[0] = 4.f * d[0] - 5.f * d[2] + d[4];
-  o[1] = t1 + t2;
-  o[2] = t1 - t2;
-  o[3] = t3 + 2.f * t4;
-  o[4] = t3 - 2.f * t4;
-  o[5] = 4.f * d[1] - 5.f * d[3] + d[5];
-}
-// A rows [1,0,0,0] [1,1,1,1] [1,-1,1,-1] [1,2,4,8] [1,-2,4,-8] [0,0,0,1]
-__device__ __forceinline__ void at6(const float (&d)[4], float (&o)[6]) {
-  const float s = d[0] + d[2], t = d[1] + d[3], u = d[0] + 4.f * d[2], v = 2.f * d[1] + 8.f * d[3];
-  o[0] = d[0];
-  o[1] = s + t;
-  o[2] = s - t;
-  o[3] = u + v;
-  o[4] = u - v;
-  o[5] = d[3];
-}
+// (bt6 and at6: wino4_common.h)
 
 // VEC = channels per thread (1, or 2 with 8-byte accesses: SSDE_WGRAD4_XVEC, A/B in profiles/r3_wgrad_wino4_ab.txt)
 template <int VEC> struct XfVec;

@@ -6,7 +6,7 @@
 // matrix cycles), and every 64-cout workgroup of a pixel tile repeats them.  The price of the split is the extra pass: x read
 // once more and V (2.25 x) written and read; it is paid back where a V tile feeds four or more cout tiles (the 256-cout layers)
 // and in training programs, where V is wanted anyway by the F(4x4,3x3) weight gradient (ssde_wgrad_args.v_pre).
-#include "ssde_common.h"
+#include "wino4_common.h"
 
 namespace {
 
@@ -39,23 +39,7 @@ struct XformVqParams {
 };
 constexpr int kXfPairs = 64;                   // (image, group) pairs of a workgroup, at most
 
-// The fused multiply-adds are written out and the compiler adds none (as ssde_stat_merge, ssde_common.h): left to -ffp-contract,
-// two instantiations of the kernel that differ in their stores alone were contracted differently (1 ulp in 4 % of V on the
-// device), and V must be the same bits whichever instantiation a launch takes.
-__device__ __forceinline__ void bt6q(const float4 (&d)[6], float4 (&o)[6]) {
-#pragma clang fp contract(off)
-#define SSDE_BT6_LANE(c)                                                                                             \
-  {                                                                                                                  \
-    const float t1 = __builtin_fmaf(-4.f, d[2].c, d[4].c), t2 = __builtin_fmaf(-4.f, d[1].c, d[3].c);                 \
-    const float t3 = d[4].c - d[2].c, t4 = d[3].c - d[1].c;                                                           \
-    o[0].c = __builtin_fmaf(4.f, d[0].c, __builtin_fmaf(-5.f, d[2].c, d[4].c));                                       \
-    o[1].c = t1 + t2; o[2].c = t1 - t2; o[3].c = __builtin_fmaf(2.f, t4, t3); o[4].c = __builtin_fmaf(-2.f, t4, t3);  \
-    o[5].c = __builtin_fmaf(4.f, d[1].c, __builtin_fmaf(-5.f, d[3].c, d[5].c));                                       \
-  }
-  SSDE_BT6_LANE(x) SSDE_BT6_LANE(y) SSDE_BT6_LANE(z) SSDE_BT6_LANE(w)
-#undef SSDE_BT6_LANE
-}
-
+// (B^T: bt6q of wino4_common.h, the form with its fused multiply-adds written out)
 constexpr int kXfThreads = 256;
 
 typedef float xf_v4f __attribute__((ext_vector_type(4)));

@@ -33,7 +33,7 @@ def build(verbose=False):
     os.makedirs(OUT, exist_ok=True)
     srcs = _sources()
     deps = [os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "rocrand", "rocrand_kernel.h"),
-            os.path.join(CSRC, "ssde_common.h"), os.path.join(ROOT, "include", "ssde.h")]
+            os.path.join(CSRC, "ssde_common.h"), os.path.join(CSRC, "wino4_common.h"), os.path.join(ROOT, "include", "ssde.h")]
     dep_m = max(os.path.getmtime(d) for d in deps)
 
     def one(src):
