@@ -153,8 +153,12 @@ enum { SSDE_CONVF_V_GIVEN = 1u,      /* SSDE_TILE_WINOGRAD4R: wino_v already hol
        SSDE_CONVF_X6_NO_WIDE = 1024u,/* bf16x6 GEMM: never take it */
        SSDE_CONVF_KSPLIT2 = 2048u,   /* SSDE_TILE_WINOGRAD4P: two reduction shares where the channel count allows (else one) */
        SSDE_CONVF_KSPLIT4 = 4096u,   /* SSDE_TILE_WINOGRAD4P: four shares (else two, else one); SSDE_CONVF_NO_KSPLIT: one */
-       SSDE_CONVF_XFORM_PLAIN = 8192u };/* SSDE_TILE_WINOGRAD4R: the transform pass writes V with plain stores everywhere (default:
+       SSDE_CONVF_XFORM_PLAIN = 8192u, /* SSDE_TILE_WINOGRAD4R: the transform pass writes V with plain stores everywhere (default:
                                          non-temporal stores where they were measured to pay, wino4_xform.hip; A/B runs, tests) */
+       SSDE_CONVF_SMALL_COUT_WIDE = 16384u };/* conv_small.hip also takes 5 <= c_out <= 16 (two or four quads of output channels per
+                                         workgroup: the image heads of data with more than four channels), under its other conditions
+                                         unchanged.  Without the flag -- and for c_out > 16 with it -- such a launch goes to the direct
+                                         kernel as before; c_out <= 4 is not affected either way */
 enum { SSDE_TILE_AUTO = 0, SSDE_TILE_256x64 = 1, SSDE_TILE_128x64 = 2, SSDE_TILE_64x64 = 3, SSDE_TILE_256x32 = 4,
        /* Winograd F(2x2,3x3) kernel (3x3, stride 1, pad 1, even output, no aux): w_main must then be packed as
         * [ceil(Cin/8)][ceil(Cout/64)][16 positions][4 channel pairs][64 couts, bit 4 ^= pair parity][2], G g G^T */

@@ -140,7 +140,15 @@ def get_pc_colorizer(sde, predictor, corrector, inverse_scaler, snr, n_steps=1, 
     run = _controlled_pc(sde, predictor, corrector, inverse_scaler, snr, n_steps, probability_flow, continuous, denoise,
                          eps, decouple, couple, dict(M=M.flatten().tolist(), invM=invM.flatten().tolist()))
 
+    def check_channels(shape):
+        # the colour-space form is a 3x3 matrix over the channels (M above): no other count has a behaviour in the reference
+        # either (its einsum raises); said here, before anything is lowered or launched
+        if len(shape) != 4 or shape[1] != 3:
+            raise ValueError("colorization mixes exactly 3 channels (RGB -> a luminance axis and two colour axes): got an image "
+                             "of shape %s, %s channels (config.data.num_channels)" % (tuple(shape), shape[1] if len(shape) > 1 else "no"))
+
     def pc_colorizer(model, gray_scale_img, prior=None, noises=None, seed=None, use_graph=True, max_steps=None):
+        check_channels(gray_scale_img.shape)
         with torch.no_grad():
             shape = gray_scale_img.shape
             mask = get_mask(gray_scale_img)
@@ -150,6 +158,10 @@ def get_pc_colorizer(sde, predictor, corrector, inverse_scaler, snr, n_steps=1, 
             pc_colorizer.last_path = run.last_path
             return inverse_scaler(x_mean if denoise else x)
 
+    def engine(model, shape, device=None):
+        check_channels(shape)
+        return run.engine(model, shape, device)
+
     pc_colorizer.last_path = None
-    pc_colorizer.engine = run.engine
+    pc_colorizer.engine = engine
     return pc_colorizer

@@ -1,4 +1,5 @@
-// 3x3 / stride 1 / pad 1 convolutions with at most FOUR output channels: the image heads of the network --
+// 3x3 / stride 1 / pad 1 convolutions with at most FOUR output channels (one channel quad; with SSDE_CONVF_SMALL_COUT_WIDE up to
+// sixteen: two or four quads, see "Wider heads" below): the image heads of the network --
 // `conv3x3(act(GroupNorm(h)))` onto the 3 image channels at models/ncsnpp.py:368-375 (every configuration) and the
 // output-skip pyramid convolutions of the progressive architectures (ncsnpp.py:329-337: FFHQ / CelebA-HQ / LSUN NCSN++, one per
 // resolution level up to 256x256 and 1024x1024).
@@ -18,6 +19,20 @@
 //   reduction  the 16 slices of a pixel are summed through LDS in slice order (fixed: deterministic), one thread per
 //              (pixel, cout), then bias / per-image addend / residual / scale as everywhere else (ssde_store_tile's order)
 // fp32 FMA chains throughout: closer to the direct sum than the Winograd kernels (tests: the direct kernel's tolerance).
+//
+// Wider heads (config.data.num_channels > 4; SSDE_CONVF_SMALL_COUT_WIDE): the kernel is instantiated for Q = 1, 2 or 4 quads of
+// output channels per workgroup (c_out <= 4, <= 8, <= 16; three quads run as four).  The halo tile is staged and the prologue
+// applied ONCE per chunk for all quads -- the input read and the prologue are the bounds above, so the quads are a loop inside
+// the workgroup (16 Q accumulators per thread), not a grid dimension.  The kernel is bound by latency, not by its FMAs (one
+// quad: ~1 us of pk_fma in the ~11 us a workgroup lives), so what it must keep is its TWO workgroups per CU: the quads take
+// turns in the ONE weights area -- per chunk and quad: barrier, the quad's [tap][slice][8 ci][4 co] image in, barrier, the
+// same 9-tap loop on the staged halo -- and in the one slice-partials area at the end.  LDS, for every Q:
+//   halo 51200 + weights 20736 (pitch 36) + GroupNorm tables 1280 = 73216 bytes: 2 workgroups per CU (160 KiB); the slice
+//   partials [16 slices][64 px][4] = 16384 bytes alias the halo, one quad at a time.
+// (The first form kept all quads' weights resident -- pitch 32 Q + 4, 91648 / 128512 bytes for Q = 2 / 4, partials 32 / 64 KiB
+//  over halo and weights -- which is ONE workgroup per CU: measured 5 % and 60 % SLOWER than the direct kernel)
+// Every output channel sees the same (chunk, tap, channel) order and the same slice order whatever Q is, so a channel's bits
+// do not depend on Q, and Q = 1 is the kernel as it was: no extra barrier, the same arithmetic in the same order.
 #include "ssde_common.h"
 
 namespace {
@@ -29,7 +44,9 @@ constexpr int kWPitch = 36;                                            // floats
 constexpr int kHaloFloats = kHaloPx * kChunk;                          // 12800
 constexpr int kWFloats = 9 * kSlices * kWPitch;                        // 5184
 constexpr int kGnFloats = 64 + 2 * kChunk;                             // (mean, rstd) per channel quad, gamma, beta of a chunk
-constexpr int kLdsBytes = (kHaloFloats + kWFloats + kGnFloats) * 4;    // 73216: two workgroups per CU
+constexpr int kLdsBytes = (kHaloFloats + kWFloats + kGnFloats) * 4;    // 73216: two workgroups per CU, for every quad count
+constexpr int kMaxQuads = 4;                                           // output channel quads of the widest instantiation
+static_assert(2 * kLdsBytes <= 160 * 1024, "two workgroups per CU");
 static_assert(kSlices * kTile * kTile * 4 <= kHaloFloats, "the slice partials reuse the halo area");
 
 struct SmallParams {
@@ -43,6 +60,7 @@ struct SmallParams {
   float* dst;
 };
 
+template <int Q>
 __global__ __launch_bounds__(kThreads, 2) void conv_small_cout_kernel(const SmallParams p) {
   SSDE_LDS(smem);
   float* halo = smem;                       // [px][half][slice][4]
@@ -62,9 +80,25 @@ __global__ __launch_bounds__(kThreads, 2) void conv_small_cout_kernel(const Smal
   // compute role: slice sl of the chunk, pixels (row, col0 .. col0 + 3) of the tile
   const int sl = lane & 15, strip = wave * 4 + (lane >> 4);
   const int row = strip >> 1, col0 = (strip & 1) * 4;
-  ssde_f32x2 acc[4][2];
+  ssde_f32x2 acc[Q][4][2];                  // [quad][pixel][cout pair]
 #pragma unroll
-  for (int j = 0; j < 4; ++j) { acc[j][0] = ssde_f32x2{0.f, 0.f}; acc[j][1] = ssde_f32x2{0.f, 0.f}; }
+  for (int qd = 0; qd < Q; ++qd)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { acc[qd][j][0] = ssde_f32x2{0.f, 0.f}; acc[qd][j][1] = ssde_f32x2{0.f, 0.f}; }
+  // the chunk's weights of one quad of couts: global [ci8 chunk][tap][CoutPad][8 ci] -> LDS [tap][slice][ci][co]
+  auto stage_weights = [&](int c_base, int qd) {
+    for (int it = tid; it < 9 * kSlices * 8; it += kThreads) {
+      const int ci = it & 7, ts = it >> 3;
+      const int sx = ts % kSlices, tap = ts / kSlices;
+      const int c8 = (c_base >> 3) + sx;
+      float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c8 * 8 < Ctot) {
+        const float* g = p.wpk + (((size_t)c8 * 9 + tap) * p.CoutPad + qd * 4) * 8 + ci;
+        w4 = make_float4(g[0], g[8], g[16], g[24]);          // couts 4 qd .. 4 qd + 3 (CoutPad >= 64: rows past Cout are zero)
+      }
+      *reinterpret_cast<float4*>(wl + (tap * kSlices + sx) * kWPitch + ci * 4) = w4;
+    }
+  };
 
   constexpr int kItems = (kHaloPx * (kChunk / 4) + kThreads - 1) / kThreads;      // 13 halo float4s per thread and chunk
   float* gnl = wl + kWFloats;               // this chunk's GroupNorm tables: [32 quads](mean, rstd) | gamma[128] | beta[128]
@@ -100,18 +134,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_small_cout_kernel(const Smal
       const bool second = ok && c >= s.c0;                  // (c0 % 4 == 0: a quad never straddles the sources)
       hv[k] = *reinterpret_cast<const float4*>(second ? s.p1 + pix * s.c1 + (c - s.c0) : s.p0 + pix * s.c0 + (ok ? c : 0));
     }
-    // ---- the chunk's weights: global [ci8 chunk][tap][CoutPad][8 ci] -> LDS [tap][slice][ci][co]
-    for (int it = tid; it < 9 * kSlices * 8; it += kThreads) {
-      const int ci = it & 7, ts = it >> 3;
-      const int sx = ts % kSlices, tap = ts / kSlices;
-      const int c8 = (c_base >> 3) + sx;
-      float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c8 * 8 < Ctot) {
-        const float* g = p.wpk + (((size_t)c8 * 9 + tap) * p.CoutPad) * 8 + ci;
-        w4 = make_float4(g[0], g[8], g[16], g[24]);          // couts 0..3 (CoutPad >= 64: rows past Cout are zero)
-      }
-      *reinterpret_cast<float4*>(wl + (tap * kSlices + sx) * kWPitch + ci * 4) = w4;
-    }
+    // ---- the chunk's weights of the first quad (the other quads follow it through the same area, below)
+    stage_weights(c_base, 0);
     if (pro.gn) __syncthreads();            // the GroupNorm tables are in place
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
@@ -138,7 +162,14 @@ __global__ __launch_bounds__(kThreads, 2) void conv_small_cout_kernel(const Smal
       *reinterpret_cast<float4*>(halo + hp * kChunk + ((q & 1) * kSlices + (q >> 1)) * 4) = v;
     }
     __syncthreads();
-    // ---- 9 taps x 8 channels x 4 pixels x 4 couts
+    // ---- per quad: 9 taps x 8 channels x 4 pixels x 4 couts
+#pragma unroll
+    for (int qd = 0; qd < Q; ++qd) {
+    if (qd) {                               // the next quad's weights take the area once every wave is done with the last one's
+      __syncthreads();
+      stage_weights(c_base, qd);
+      __syncthreads();
+    }
     if (c_base + sl * 8 < Ctot) {
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy) {
@@ -166,26 +197,31 @@ __global__ __launch_bounds__(kThreads, 2) void conv_small_cout_kernel(const Smal
 #pragma unroll
             for (int ci = 0; ci < 8; ++ci) {
               const ssde_f32x2 xx = ssde_f32x2{xv[ci], xv[ci]};
-              acc[j][0] = __builtin_elementwise_fma(xx, w[ci][0], acc[j][0]);
-              acc[j][1] = __builtin_elementwise_fma(xx, w[ci][1], acc[j][1]);
+              acc[qd][j][0] = __builtin_elementwise_fma(xx, w[ci][0], acc[qd][j][0]);
+              acc[qd][j][1] = __builtin_elementwise_fma(xx, w[ci][1], acc[qd][j][1]);
             }
           }
         }
       }
     }
+    }
   }
-  // ---- sum the slices (fixed order), then the epilogue of one (pixel, cout) per thread
-  __syncthreads();
+  // ---- per quad: sum the slices (fixed order), then the epilogue of one (pixel, cout) per thread
   float* red = smem;                        // [slice][64 px][4]
+  const int px = tid >> 2;
+  const int oy = oy0 + (px >> 3), ox = ox0 + (px & 7);
+#pragma unroll
+  for (int qd = 0; qd < Q; ++qd) {
+  __syncthreads();                          // the halo (the previous quad's partials) has been consumed
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    *reinterpret_cast<float4*>(red + (sl * 64 + row * kTile + col0 + j) * 4) = make_float4(acc[j][0].x, acc[j][0].y, acc[j][1].x, acc[j][1].y);
+    *reinterpret_cast<float4*>(red + (sl * 64 + row * kTile + col0 + j) * 4) =
+        make_float4(acc[qd][j][0].x, acc[qd][j][0].y, acc[qd][j][1].x, acc[qd][j][1].y);
   __syncthreads();
-  const int px = tid >> 2, co = tid & 3;
+  const int co = qd * 4 + (tid & 3);
   float v = 0.f;
 #pragma unroll
-  for (int k = 0; k < kSlices; ++k) v += red[(k * 64 + px) * 4 + co];
-  const int oy = oy0 + (px >> 3), ox = ox0 + (px & 7);
+  for (int k = 0; k < kSlices; ++k) v += red[(k * 64 + px) * 4 + (tid & 3)];
   if (co < p.Cout && oy < p.H && ox < p.W) {
     const size_t pix = ((size_t)img * p.H + oy) * p.W + ox;
     if (p.bias) v += p.bias[co];
@@ -196,16 +232,22 @@ __global__ __launch_bounds__(kThreads, 2) void conv_small_cout_kernel(const Smal
     if (p.resid_post) v += r;
     p.dst[pix * p.Cout + co] = v;
   }
+  }
 }
+
+// quads of output channels per workgroup of the instantiation that runs c_out channels: 1, 2 or 4 (three quads run as four)
+int quads_for(int c_out) { return c_out <= 4 ? 1 : c_out <= 8 ? 2 : kMaxQuads; }
 
 }  // namespace
 
 // Does ssde_conv2d hand this launch to the kernel above?  (plain 3x3 / stride 1 / pad 1, no fused 1x1 source, at most four
-// output channels, input channels a multiple of 8, nobody asked for GroupNorm partials of the result or for another tile)
+// output channels -- sixteen where the launch carries SSDE_CONVF_SMALL_COUT_WIDE --, input channels a multiple of 8, nobody asked
+// for GroupNorm partials of the result or for another tile)
 bool ssde_conv_small_wants(const ssde_conv_args* a) {
   if (!a || (a->flags & SSDE_CONVF_NO_SMALL_COUT) || a->tile != SSDE_TILE_AUTO) return false;
   const int ctot = a->main.c0 + a->main.c1;
-  return a->ksize == 3 && a->stride == 1 && a->pad == 1 && a->pad_end == 0 && a->aux.p0 == nullptr && a->main.p0 && a->c_out >= 1 && a->c_out <= 4 &&
+  const int cout_max = (a->flags & SSDE_CONVF_SMALL_COUT_WIDE) ? 4 * kMaxQuads : 4;
+  return a->ksize == 3 && a->stride == 1 && a->pad == 1 && a->pad_end == 0 && a->aux.p0 == nullptr && a->main.p0 && a->c_out >= 1 && a->c_out <= cout_max &&
          a->h_in == a->h_out && a->w_in == a->w_out && ctot >= 8 && ctot % 8 == 0 && a->main.c0 % 4 == 0 && a->gn_part == nullptr;
 }
 
@@ -231,5 +273,12 @@ int ssde_conv_small_launch(const ssde_conv_args* a, hipStream_t st) {
   p.resid = a->resid; p.resid_post = a->resid_post; p.scale = a->out_scale; p.dst = a->dst;
   const long long wgs = (long long)a->n * p.tiles_x * p.tiles_y;
   SSDE_REQUIRE(wgs > 0 && wgs < (1ll << 31), "conv(small cout): bad grid");
-  return ssde_launch_lds<conv_small_cout_kernel>("conv(small cout)", dim3((unsigned)wgs), dim3(kThreads), pl.lds_bytes, st, p);
+  // (one group: the first launch raises the LDS limit of all three instantiations, outside any stream capture)
+  using Group = ssde_lds_kernels<conv_small_cout_kernel<1>, conv_small_cout_kernel<2>, conv_small_cout_kernel<4>>;
+  const dim3 grid((unsigned)wgs), block(kThreads);
+  switch (quads_for(a->c_out)) {
+    case 1: return ssde_launch_lds<conv_small_cout_kernel<1>, Group>("conv(small cout)", grid, block, pl.lds_bytes, st, p);
+    case 2: return ssde_launch_lds<conv_small_cout_kernel<2>, Group>("conv(small cout, 2 quads)", grid, block, pl.lds_bytes, st, p);
+    default: return ssde_launch_lds<conv_small_cout_kernel<4>, Group>("conv(small cout, 4 quads)", grid, block, pl.lds_bytes, st, p);
+  }
 }

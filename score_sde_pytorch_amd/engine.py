@@ -47,6 +47,29 @@ FC_OTHER, FC_CONV3, FC_CONV1, FC_ATTN, FC_GN, FC_FIR = 0, 1, 2, 3, 4, 5
 # Smaller batches were not measured and stay on the direct kernel.
 W4P_MIN_BATCH = 16
 
+# Image heads of more than four channels (config.data.num_channels > 4: _lower_head, the output-pyramid convolutions): the quad
+# counts (padded channels / 4) whose launches carry SSDE_CONVF_SMALL_COUT_WIDE, i.e. run on conv_small.hip's wide instantiations
+# instead of the direct kernel.  Measured, GroupNorm + SiLU prologue, ms flagged -> unflagged (tools/conv_head_bench.py, DESIGN.md
+# 26, profiles/chan_head_bench.txt; medians of 15 alternating rounds, min .. max of a figure within 2.6 % of it):
+#   2 quads:  128->8  @32x32 batch 256  0.124 -> 0.181    128->8  @256x256 batch 8  0.255 -> 0.349     adopted
+#   3 quads:  128->12 @32x32 batch 256  0.196 -> 0.181    (runs as four)                                 not adopted
+#   4 quads:  128->16 @32x32 batch 256  0.197 -> 0.181    128->16 @256x256 batch 8  0.405 -> 0.351     not adopted
+# A count that is not listed keeps the direct kernel, as does every count above 4 quads.
+HEAD_WIDE_QUADS = (2,)
+
+
+def image_cpad(channels):
+    """Channels of the image as the program stores it: NHWC, padded with zeros to whole quads.  (C + 3) // 4 * 4."""
+    if int(channels) != channels or channels < 1:
+        raise ValueError("config.data.num_channels = %r: the image needs at least one channel" % (channels,))
+    return (int(channels) + 3) // 4 * 4
+
+
+def head_flags(cpad):
+    """The extra SSDE_CONVF_* bits of an image-head launch onto cpad channels (0 for the one-quad heads: their op records stay
+    what they were)."""
+    return L.CONVF_SMALL_COUT_WIDE if cpad // 4 in HEAD_WIDE_QUADS and cpad > 4 else 0
+
 
 class Buf:
     """A symbolic activation buffer; storage is assigned by ProgramBuilder.finalize()."""
@@ -823,12 +846,13 @@ class Lowering:
 
     def conv(self, dst, h_out, w_out, c_out, main=None, w_main=None, h_in=0, w_in=0, stride=1, pad=1,
              aux=None, w_aux=None, bias=None, chan_add=None, chan_add_ld=0, resid=None, scale=1.0, resid_post=0, route=None,
-             stats=False, pad_end=0):
+             stats=False, pad_end=0, flags=0):
         """route (a row of CONV3_ROUTES; None: DIRECT): w_main is packed for it; a Winograd route runs a fused 1x1 source as a second launch.
         pad_end: zero rows / columns after the last input row / column on top of pad (the one-sided F.pad(x, (0, 1, 0, 1)) of
         DDPM's Downsample, models/layers.py:608-611); direct kernel only.
         stats=True: dst feeds a GroupNorm later -- when the launch plan allows it (ssde_conv_gn_slices) the epilogue
-        also writes the tensor's partial statistics and gn_stats() turns into a finalize of a few thousand floats."""
+        also writes the tensor's partial statistics and gn_stats() turns into a finalize of a few thousand floats.
+        flags: SSDE_CONVF_* bits of this launch on top of the environment's A/B switches (0: the op record is what it always was)."""
         route = route or DIRECT
         assert route is DIRECT or (main is not None and stride == 1 and pad == 1 and pad_end == 0 and (h_in, w_in) == (h_out, w_out))
         split_tmp = self.b.buf(self.n, h_out, w_out, c_out, name="wino_tmp") if route is not DIRECT and aux is not None else None
@@ -844,6 +868,8 @@ class Lowering:
             ksize=3 if main is not None else 0, stride=stride, pad=pad, pad_end=pad_end, tile=route.tile, bias=bias, chan_add=chan_add,
             chan_add_ld=chan_add_ld, resid_post=resid_post, resid=resid, out_scale=float(scale), dst=dst, gn_part=None,
             wino_v=None, _split_tmp=split_tmp)
+        if flags:
+            fields["flags"] = L.conv_route_flags() | flags
         if route.takes_v:
             # the transformed input B^T pro(x) B in HBM (2.25x the input): the two-kernel form (wino4_xform.hip + conv_wino4r.hip) cannot do without
             # it; in a training forward the one-kernel form leaves it behind as a by-product when the layer's weight gradient
@@ -1014,6 +1040,8 @@ class UNetEngine:
         # F(4x4,3x3) launches leave their transformed input behind for the weight gradients
         self.low.emit_wino_v = bool(getattr(self, "param_grads", False))
         self.channels = model.channels
+        # the image travels through the program as NHWC with its channels padded to whole quads (every kernel reads float4s)
+        self.cpad = image_cpad(self.channels)
         # static I/O (addresses are baked into the program / graph)
         self.x_in = self.b.buf(batch, self.channels, height, width, name="x_in", persistent=True)
         self.cond = self.b.buf(batch, name="cond", persistent=True)
@@ -1035,6 +1063,14 @@ class UNetEngine:
         self._lower()
         if finalize:
             self.program = self.b.finalize()
+            if self.cpad > 4:
+                # a count beyond the one-quad image: every launch plan is checked here, so that what a count cannot lower is
+                # said at construction and by name, not by the first run
+                try:
+                    self.validate_plans()
+                except L.SsdeError as e:
+                    raise ValueError("config.data.num_channels = %d (stored as %d channels) cannot be lowered: %s"
+                                     % (self.channels, self.cpad, e)) from e
 
     @property
     def cond_only_ops(self):
@@ -1051,7 +1087,7 @@ class UNetEngine:
         o, hh, ww = body(idx)
         mode = 2 if self.vp_score else (1 if self.cfg.model.scale_by_sigma else 0)
         vec = self.std if mode == 2 else (self.sig if mode == 1 else None)
-        self.b.add(L.OP_TO_NCHW, dict(src=o, dst=self.out, n=self.n, c=self.channels, h=hh, w=ww, c_src=4, mode=mode, v=vec))
+        self.b.add(L.OP_TO_NCHW, dict(src=o, dst=self.out, n=self.n, c=self.channels, h=hh, w=ww, c_src=self.cpad, mode=mode, v=vec))
 
     def _lower_cond(self):
         """Time embedding, the two Linear layers and every Dense_0 projection (ncsnpp.py:236-257, ddpm.py:113-122); returns the
@@ -1112,11 +1148,11 @@ class UNetEngine:
         return idx
 
     def _lower_input(self, conv_in):
-        """Input boundary: NCHW -> NHWC (C padded to 4), 2x-1 for un-centred data, and the first 3x3 convolution
+        """Input boundary: NCHW -> NHWC (C padded to whole quads), 2x-1 for un-centred data, and the first 3x3 convolution
         (ncsnpp.py:259-267, ddpm.py:124-132)."""
         b, n, nf = self.b, self.n, self.model.nf
         H, W = self.h, self.w
-        cpad = 4
+        cpad = self.cpad
         x0 = b.buf(n, H, W, cpad, name="x_nhwc")
         self._x0 = x0
         a, sh = (1.0, 0.0) if self.cfg.data.centered else (2.0, -1.0)
@@ -1127,11 +1163,12 @@ class UNetEngine:
         return h
 
     def _lower_head(self, gn_m, conv_m, h, cur_c, hh, ww):
-        """act(GroupNorm(h)) -> 3x3 convolution onto the image channels, padded to 4 (ncsnpp.py:368-375, ddpm.py:168-170)."""
+        """act(GroupNorm(h)) -> 3x3 convolution onto the image channels, padded to whole quads (ncsnpp.py:368-375, ddpm.py:168-170)."""
         gn = self.low.gn_stats(h, cur_c, hh * ww, gn_m)
-        o = self.b.buf(self.n, hh, ww, 4, name="head")
-        self.low.conv(o, hh, ww, 4, main=self.low.src(h, cur_c, hh * ww, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
-                      h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=4))
+        cpad = self.cpad
+        o = self.b.buf(self.n, hh, ww, cpad, name="head")
+        self.low.conv(o, hh, ww, cpad, main=self.low.src(h, cur_c, hh * ww, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=cpad),
+                      h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=cpad), flags=head_flags(cpad))
         return o
 
     def _lower_ncsnpp(self, idx):
@@ -1141,7 +1178,7 @@ class UNetEngine:
         skip_scale = INV_SQRT2 if model.skip_rescale else 1.0
         fir, fk = model.fir, model.fir_kernel
         H, W = self.h, self.w
-        cpad = 4
+        cpad = self.cpad
         h = self._lower_input(mods[idx]); idx += 1
         x0 = self._x0
         pyr, pyr_c = (x0, cpad) if model.progressive_input != "none" else (None, 0)
@@ -1219,11 +1256,11 @@ class UNetEngine:
                 if pyramid is not None:
                     taps = fir_taps(fk, gain=4.0) if fir else fir_taps([1, 1], gain=4.0)
                     pd = fir_pads(taps.shape[0], up=True)
-                    up_pyr, _, _ = low.upfirdn(_src(pyramid, 4), 4, hh // 2, ww // 2, taps, up=2, pad=pd, name="pyr_up")
+                    up_pyr, _, _ = low.upfirdn(_src(pyramid, cpad), cpad, hh // 2, ww // 2, taps, up=2, pad=pd, name="pyr_up")
                 gn = low.gn_stats(h, cur_c, hh * ww, gn_m)
-                pn = b.buf(n, hh, ww, 4, name="pyramid")
-                low.conv(pn, hh, ww, 4, main=low.src(h, cur_c, hh * ww, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=4),
-                         h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=4), resid=up_pyr)
+                pn = b.buf(n, hh, ww, cpad, name="pyramid")
+                low.conv(pn, hh, ww, cpad, main=low.src(h, cur_c, hh * ww, pro=L.PRO_GN_SILU, gn=gn), w_main=self._w3(conv_m, cout_pad=cpad),
+                         h_in=hh, w_in=ww, bias=self._bias(conv_m, pad_to=cpad), resid=up_pyr, flags=head_flags(cpad))
                 pyramid = pn
             if lvl != 0:
                 if ddpm_blocks:

@@ -430,7 +430,7 @@ def integrate_ode(fun, t_span, y0, rtol, atol, method):
         inner = fun
 
         def fun(t, y):                                   # host scipy loop around the fused right-hand side
-            inner.x32.copy_(y.to(torch.float32))
+            inner.x32.copy_(y[: inner.n32].to(torch.float32))    # (the likelihood state carries B more values behind the image)
             out = torch.empty_like(y)
             inner(t, y, out=out)
             return out
